@@ -5,7 +5,7 @@ Metric (BASELINE.json): Mpoints/s per repel iteration (k=21 k-NN + Miotti force)
 fp32 points per GPU, rebuild_every=1 (hash rebuild + fused sweep + reductions every step), with
 the achieved fraction of the HBM roofline of the dominant kernel next to it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--points P] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--points P] [--no-cpu] [--dump-outputs DIR]
 
 One step = one pass of the hot path (src/repel.jl:244-293) over the whole cloud, coordinates
 resident in HBM.  N > 1: one rank per GPU — either under torch.distributed.run, or, when WORLD_SIZE is not
@@ -489,6 +489,25 @@ def rehearse_threads(args) -> int:
     return 0
 
 
+DUMP_ROWS = 1 << 20   # rows written of a larger cloud (36 B per row over the five arrays: 36 MiB at most)
+DUMP_SEED = 20261015  # fixed: the same rows on every run, so two builds compare row for row
+
+
+def dump_outputs(out_dir, sess, np):
+    """--dump-outputs: what the timed path hands its caller after its last step — the moved coordinates and that
+    sweep's per-point data (force norm, nearest-neighbour distance and id) — as out_dir/<name>.npy in float32 /
+    float64.  A cloud of more than DUMP_ROWS points is cut to a seeded sample of rows, listed in sample_rows."""
+    p = sess.positions()
+    pd = sess.point_data()
+    n = len(p)
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+    arrays = {"positions": p[rows], "forces": pd["forces"][rows], "nn_dist": pd["nn_dist"][rows],
+              "nn_id": pd["nn_id"][rows].astype(np.float64), "sample_rows": rows.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+
+
 def ctx_rho() -> float:
     try:
         return float(os.environ.get("WTP_RHO", "9"))   # the library's default (csrc/wtp_internal.hpp)
@@ -512,7 +531,13 @@ def main():
     ap.add_argument("--no-e2e", action="store_true", help="skip the 1000-iteration end-to-end leg and the graded-cloud legs")
     ap.add_argument("--cpu-points", type=int, default=4_000_000)
     ap.add_argument("--cpu-iters", type=int, default=6)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps, write what the last step computed to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         rc = self_launch(args.gpus)  # nothing has touched a GPU yet
@@ -667,6 +692,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     tm = ctx.timers()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sess, np)
 
     # Same workload once more through the explicit k-selection path (WTP_FULL_SELECT=1: every query
     # runs the 64-key network), N=1 only: the default path above certifies by counting that the

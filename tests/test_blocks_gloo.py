@@ -37,7 +37,7 @@ def _worker(rank, grid, port, n_total, iters, q, margin):
     if rank == 0:
         q.put((conv, allp.numpy(), [h["n_ghost"] for h in drv.history], [h["n_move"] for h in drv.history],
                drv.migrations))
-    dist.barrier()
+    dist.monitored_barrier()  # host-side: dist.barrier() would probe for (and open) a GPU in this CPU-only rank
     dist.destroy_process_group()
 
 

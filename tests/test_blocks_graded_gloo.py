@@ -81,7 +81,7 @@ def _worker(rank, grid, port, n_total, iters, q):
     dist.all_gather(counts, torch.tensor([len(gid)]))
     if rank == 0:
         q.put((conv, allp.numpy(), [int(c) for c in counts], drv.migrations))
-    dist.barrier()
+    dist.monitored_barrier()  # host-side: dist.barrier() would probe for (and open) a GPU in this CPU-only rank
     dist.destroy_process_group()
 
 

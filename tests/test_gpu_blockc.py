@@ -250,3 +250,33 @@ def test_bench_rehearsal_eight_ranks_as_threads():
     out = _bench_line(["--gpus", "8", "--steps", "4", "--warmup", "2", "--total-points", "1600000", "--no-cpu"])
     assert out["n_gpus"] == 8 and out["scaling"] == "strong" and out["value"] > 0
     assert out["block_info"]["n_peers"] == 7
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(wtp, tmp_path):
+    """bench.py --gpus 1 --dump-outputs: the arrays are a plain session's on the same cloud after warmup + steps sweeps
+    (so --steps sets the timed sweeps), at the seeded sample of rows a cloud above 2^20 points is cut to."""
+    import os
+
+    import torch
+
+    n, warm, steps = 1_200_000, 2, 3
+    out = _bench_line(["--gpus", "1", "--points", str(n), "--steps", str(steps), "--warmup", str(warm), "--no-cpu",
+                       "--no-full-select", "--no-other-paths", "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == steps and out["ms_per_step"] > 0
+    names = ("positions", "forces", "nn_dist", "nn_id", "sample_rows")
+    got = {f: np.load(tmp_path / f"{f}.npy") for f in names}
+    assert sum(os.path.getsize(tmp_path / f"{f}.npy") for f in names) <= 64 << 20
+    rows = got["sample_rows"].astype(np.int64)
+    assert len(rows) == 1 << 20 and np.all(np.diff(rows) > 0) and rows[-1] < n
+    assert got["positions"].dtype == np.float32 and got["positions"].shape == (len(rows), 3)
+    s = float(n) ** (-1.0 / 3.0)
+    with wtp.Context(0) as c:
+        x = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+        c.gen_uniform_dev(wtp.synth.SEED, 0, n, 3, np.float32, x.data_ptr())
+        with c.relax(None, 0, s, FORCE, K, s / 2000, s / 20, device_ptr=(x.data_ptr(), n, 3, np.float32)) as sess:
+            sess.run(warm + steps, 1)
+            p, pd = sess.positions(), sess.point_data()
+        del x
+    assert np.array_equal(got["positions"], p[rows])
+    for f in ("forces", "nn_dist", "nn_id"):
+        assert np.array_equal(got[f], pd[f][rows]), f

@@ -1,6 +1,6 @@
 import os, sys
 import numpy as np
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import wtp_amd as w
 n = int(float(sys.argv[1])) if len(sys.argv) > 1 else 1000000
 rng = np.random.default_rng(5)

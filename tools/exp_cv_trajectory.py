@@ -1,5 +1,5 @@
-import sys, math, numpy as np
-sys.path.insert(0, "/root/repo")
+import os, sys, math, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import wtp_amd as w
 ctx = w.Context(0)
 F = dict(kind=2, beta=0.2, u0=1.0, gamma=3.0)

@@ -2,7 +2,7 @@
 # Per-kernel device times (rocprofv3 --kernel-trace --stats) of tools/exp_sweep.py: tools/kstats.sh <tag> [N] [steps]
 set -o pipefail
 TAG=${1:-x}; N=${2:-1e7}; STEPS=${3:-10}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/kstats_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

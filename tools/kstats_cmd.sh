@@ -2,7 +2,7 @@
 # Per-kernel device times (rocprofv3 --kernel-trace --stats) of an arbitrary python tool: tools/kstats_cmd.sh <tag> <script> [args...]
 set -o pipefail
 TAG=$1; shift
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/kstats_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

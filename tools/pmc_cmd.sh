@@ -2,7 +2,7 @@
 # SQ counter passes of an arbitrary python tool: tools/pmc_cmd.sh <tag> <script> [args...]  -> gpurun_out/pmc_<tag>/summary.txt
 set -o pipefail
 TAG=$1; shift
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -3,7 +3,7 @@
 # LDS activity / bank conflicts, VALU busy and wait cycles.  Output: gpurun_out/pmc_<tag>/summary.txt
 set -o pipefail
 TAG=${1:-q}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -5,7 +5,7 @@
 # Outputs land in gpurun_out/prof_<tag>/; the summaries are copied to profiles/ by hand.
 set -o pipefail
 TAG=${1:-r01f}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
