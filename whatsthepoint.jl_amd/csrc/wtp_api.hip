@@ -298,7 +298,7 @@ static void ksel_geometry(wtp_ctx* ctx, double n, double ncells, int n0, double 
     hc = (hc + 63) / 64 * 64;
     *bx_out = bx;
     *hcap_out = hc < 512 ? 512 : (hc > 3072 ? 3072 : hc);
-    if (getenv("WTP_DEBUG"))
+    if (ctx->debug)
         fprintf(stderr, "[wtp] ksel geometry: rho_cell %.3f (box average %.3f), %d columns -> bricks of %d, LDS point area %d\n",
                 rho_cell, ncells > 0 ? n / ncells : 0.0, n0, *bx_out, *hcap_out);
 }
@@ -307,8 +307,7 @@ static void ksel_geometry(wtp_ctx* ctx, double n, double ncells, int n0, double 
 // 41 columns, 77 % of the lanes; 1.1 fills 90 %).  Model per query: (one brick round, two with probability p2) / Q own
 // points, times the round's cost (a scan in proportion to the occupancy on top of a fixed part), plus the hand-backs that
 // grow as the provable radius 2c shrinks.  `n0`, `c`: the grid just built with occupancy rho_cur.
-static double ksel_pick_rho(const wtp_ctx* ctx, double n, double ncells, int n0, double rho_cur, double rho_eff) {
-    if (getenv("WTP_RHO_KSEL")) return rho_cur; // the caller fixed it
+static double ksel_pick_rho(double n, double ncells, int n0, double rho_cur, double rho_eff) {
     double fill_cur = ncells > 0 ? n / ncells : rho_cur; // points per cell, box average
     if (rho_eff - 1.0 > fill_cur) fill_cur = rho_eff - 1.0;
     double best = 1e300, best_rho = rho_cur;
@@ -340,14 +339,14 @@ static double ksel_pick_rho(const wtp_ctx* ctx, double n, double ncells, int n0,
 
 // occupancy of the wtp_ksel.hip grid for kq = k + self: in proportion to kq (the cell edge follows r_k), capped where a run of
 // 173 cells still fits the 256 slots of the hit masks
-static double ksel_rho_for(const wtp_ctx* ctx, int kq) {
-    const double rho = ctx->rho_ksel * (double)kq / 22.0;
+static double ksel_rho_for(int kq) {
+    const double rho = kRhoKsel * (double)kq / 22.0;
     return rho > 1.26 ? 1.26 : rho;
 }
 // points the first filter ball is expected to hold: k + self plus the same number of standard deviations as
-// cap_ksel leaves at 22
-static double ksel_cap_count(const wtp_ctx* ctx, int kq) {
-    return (double)kq + (ctx->cap_ksel - 22.0) / std::sqrt(22.0) * std::sqrt((double)kq);
+// kCapKsel leaves at 22
+static double ksel_cap_count(int kq) {
+    return (double)kq + (kCapKsel - 22.0) / std::sqrt(22.0) * std::sqrt((double)kq);
 }
 
 template <typename T>
@@ -372,7 +371,7 @@ static int knn_dev_t(wtp_ctx* ctx, const T* d_xyz, int64_t n, int dim, int k, in
     // fp32 3-D clouds with k + self <= 24 (the reference's k = 21 among them): the x-slowest layout of wtp_ksel.hip —
     // cells of ~1.2 points, the k nearest inside the 5 x 5 x 5 block around the query's cell
     const bool ksel = sizeof(T) == 4 && dim == 3 && ctx->ksel && !ctx->force_generic && kq <= ksel_kmax() && n >= 4096;
-    const double rho_direct = ksel ? ksel_rho_for(ctx, kq) : 0.0;
+    const double rho_direct = ksel ? ksel_rho_for(kq) : 0.0;
     ctx->topology_build = true;
     if (ctx->knn_tune_n == n && ctx->knn_tune_dim == dim && ctx->knn_tune_k == kq && !ctx->knn_tune_boxed &&
         ctx->knn_tune_ksel == (int)ksel) {
@@ -390,7 +389,7 @@ static int knn_dev_t(wtp_ctx* ctx, const T* d_xyz, int64_t n, int dim, int k, in
         }
         ctx->knn_tune_rho = rho_direct;
         if (ksel) { // the occupancy whose grid fills the bricks' lanes best: one more measured build, this call only
-            const double pick = ksel_pick_rho(ctx, (double)n, (double)hg.ncells, hg.n[0], rho_direct, rho_eff);
+            const double pick = ksel_pick_rho((double)n, (double)hg.ncells, hg.n[0], rho_direct, rho_eff);
             if (std::fabs(pick - rho_direct) > 0.01 * rho_direct) {
                 scale = 1.0;
                 if ((rc = build_hash_tuned<T>(ctx, raw, sorted, n, dim, kq, 0.0, pick, 0.0, &scale, &rho_eff, &hg))) {
@@ -432,12 +431,12 @@ static int knn_dev_t(wtp_ctx* ctx, const T* d_xyz, int64_t n, int dim, int k, in
     if (ksel) {
         a.ksel_bx = ctx->knn_tune_bx;
         a.brick_hcap = ctx->knn_tune_hcap;
-        a.cap_count = (float)ksel_cap_count(ctx, kq);
+        a.cap_count = (float)ksel_cap_count(kq);
     }
     sp = span_begin(ctx, 1);
     rc = launch_topology<T>(ctx, a);
     span_end(ctx, sp);
-    if (!rc && getenv("WTP_DEBUG")) { // hand-backs of the brick kernel to the exact path
+    if (!rc && ctx->debug) { // hand-backs of the brick kernel to the exact path
         int32_t h[2] = {0, 0};
         hipMemcpyAsync(&h[0], a.fb_count, 4, hipMemcpyDeviceToHost, ctx->stream);
         hipMemcpyAsync(&h[1], a.fb2_count, 4, hipMemcpyDeviceToHost, ctx->stream);
@@ -491,7 +490,7 @@ static int knn_dev_f64(wtp_ctx* ctx, const double* d_xyz, int64_t n, int dim, in
     Grid<float> hg;
     // the fp32 candidate search takes the x-slowest layout of wtp_ksel.hip where that applies (3-D, k + self + 2 <= 24)
     const bool ksel = dim == 3 && ctx->ksel && kc <= ksel_kmax() && n >= 4096;
-    double rho_direct = ksel ? ksel_rho_for(ctx, kc) : 0.0;
+    double rho_direct = ksel ? ksel_rho_for(kc) : 0.0;
     ctx->topology_build = true;
     // the measured cell scale (and the brick geometry that goes with it) of the last fp64 call is reused for a cloud of the
     // same size, as in the fp32 calls: it only affects speed, and saves two occupancy passes and a host synchronisation
@@ -503,7 +502,7 @@ static int knn_dev_f64(wtp_ctx* ctx, const double* d_xyz, int64_t n, int dim, in
     } else {
         rc = build_hash_tuned<float>(ctx, raw32, sorted32, n, dim, kc, 0.0, rho_direct, 0.0, &scale, &rho_eff, &hg);
         if (!rc && ksel) {
-            const double pick = ksel_pick_rho(ctx, (double)n, (double)hg.ncells, hg.n[0], rho_direct, rho_eff);
+            const double pick = ksel_pick_rho((double)n, (double)hg.ncells, hg.n[0], rho_direct, rho_eff);
             if (std::fabs(pick - rho_direct) > 0.01 * rho_direct) {
                 rho_direct = pick;
                 scale = 1.0;
@@ -545,11 +544,11 @@ static int knn_dev_f64(wtp_ctx* ctx, const double* d_xyz, int64_t n, int dim, in
             ksel_geometry(ctx, (double)n, (double)hg.ncells, hg.n[0], rho_eff, &ctx->knn64_tune_bx, &ctx->knn64_tune_hcap);
         a.ksel_bx = ctx->knn64_tune_bx;
         a.brick_hcap = ctx->knn64_tune_hcap;
-        a.cap_count = (float)ksel_cap_count(ctx, kc);
+        a.cap_count = (float)ksel_cap_count(kc);
     }
     sp = span_begin(ctx, 1);
     // k = 21 without self (kc = 24): search and re-ranking in slot order (see refine_f64_slots_kernel)
-    const bool slots = kc == 24 && !ctx->force_generic && getenv("WTP_F64_SLOTS_OFF") == nullptr;
+    const bool slots = kc == 24;
     double4* slot64 = (double4*)ctx->pts[1].p;
     if (slots && (rc = launch_relabel_slots(ctx, raw64, sorted32, slot64, n))) return rc;
     rc = launch_topology<float>(ctx, a);
@@ -649,25 +648,19 @@ WTP_API int wtp_create(const int* device_ordinals, int n_dev, wtp_ctx** out) {
     }
     ctx->stream = ctx->own_stream;
     if (const char* e = getenv("WTP_RHO")) ctx->rho = atof(e) > 0 ? atof(e) : ctx->rho;
-    if (const char* e = getenv("WTP_GAMMA_CAP")) ctx->gamma_cap = atof(e) > 0 ? atof(e) : ctx->gamma_cap;
-    if (const char* e = getenv("WTP_GAMMA_CAP_SWEEP")) ctx->gamma_cap_sweep = atof(e) > 0 ? atof(e) : ctx->gamma_cap_sweep;
-    if (const char* e = getenv("WTP_TNN")) ctx->tnn_frac = atof(e) > 0 && atof(e) < 0.99 ? atof(e) : ctx->tnn_frac;
     if (const char* e = getenv("WTP_FORCE_GENERIC")) ctx->force_generic = atoi(e);
     if (const char* e = getenv("WTP_FULL_SELECT")) ctx->full_select = atoi(e);
-    if (const char* e = getenv("WTP_CS2")) ctx->cs2 = atoi(e);
     if (const char* e = getenv("WTP_KSEL")) ctx->ksel = atoi(e);
-    if (const char* e = getenv("WTP_F64_KSEL")) ctx->f64_ksel = atoi(e);
     if (const char* e = getenv("WTP_BALL64")) ctx->ball64 = atoi(e);
-    if (const char* e = getenv("WTP_RHO_KSEL")) ctx->rho_ksel = atof(e) > 0 ? atof(e) : ctx->rho_ksel;
-    if (const char* e = getenv("WTP_CAP_KSEL")) ctx->cap_ksel = atof(e) > 0 ? atof(e) : ctx->cap_ksel;
-    if (const char* e = getenv("WTP_RHO_CS")) ctx->rho_cs2 = atof(e) >= 1.0 ? atof(e) : ctx->rho_cs2;
-    if (const char* e = getenv("WTP_STYP_SIGMA")) ctx->styp_sigma = atof(e);
+    if (const char* e = getenv("WTP_F64_KSEL")) ctx->f64_ksel = atoi(e);
+    if (const char* e = getenv("WTP_RADIUS_DENSE")) ctx->radius_dense = atoi(e);
+    if (const char* e = getenv("WTP_BLOCK_OVERLAP")) ctx->block_overlap = atoi(e);
+    ctx->debug = getenv("WTP_DEBUG") != nullptr;
+    ctx->debug_kd = getenv("WTP_DEBUG_KD") != nullptr;
     if (const char* e = getenv("WTP_TIMING")) {
         ctx->timing = atoi(e) != 0;
         ctx->timing_forced = true;
     }
-    if (const char* e = getenv("WTP_MESH_PACKET")) ctx->mesh_packet = atoi(e);
-    if (const char* e = getenv("WTP_GRID_REUSE")) ctx->grid_reuse_max = atoi(e) >= 0 ? atoi(e) : ctx->grid_reuse_max;
     *out = ctx;
     return WTP_OK;
 }
@@ -859,41 +852,35 @@ template <typename T> static int radius_count_t(wtp_ctx* ctx, int64_t n, int dim
     a.fb_list = (int32_t*)ctx->fb_list.p; // queries the brick kernel hands back to the wave kernel
     a.fb_count = (int32_t*)ctx->fb_count.p;
     // fp32: the brick kernel parks the rows it finds (32 ids per query) and marks the query, so that wtp_radius_fill copies
-    // them instead of running the whole search a second time (128 B per point of scratch; WTP_RADIUS_CACHE=0 switches it off)
-    ctx->rad_rows_cached = false;
-    if (ctx->force_generic != 2 && !(getenv("WTP_RADIUS_CACHE") && atoi(getenv("WTP_RADIUS_CACHE")) == 0)) {
-        if ((rc = ensure(ctx, ctx->rad_done, (size_t)n + 64))) return rc;
-        WTP_HIP(ctx, hipMemsetAsync(ctx->rad_done.p, 0, (size_t)n, ctx->stream));
-        a.rad_done = (uint8_t*)ctx->rad_done.p;
-        if (sizeof(T) == 4 && !ctx->force_generic) { // the brick kernel's rows: 32 ids per query
-            if ((rc = ensure(ctx, ctx->rad_tmp, sizeof(int32_t) * 32 * (size_t)n))) return rc;
-            a.rad_tmp = (int32_t*)ctx->rad_tmp.p;
-        }
-        // the wave kernel's rows (any length up to its list), where it serves every query (fp64; fp32 grids whose rows are
-        // expected to outgrow the brick kernel, Grid::rad_wave_only; WTP_FORCE_GENERIC=1): an arena of 48 ids per point,
-        // shared out evenly among the waves; a row that does not fit any more is simply searched again by the fill phase.
-        // (For the hand-backs of the fp32 brick kernel it buys nothing: measured 2.07 -> 2.14 ms per graded 1 M cloud —
-        // ranking in the count phase costs what it saves in the fill phase; the kernel decides by the grid's flag.)
-        {
-            const int64_t arena_cap = 48 * n;
-            if ((rc = ensure(ctx, ctx->rad_arena, sizeof(int32_t) * (size_t)arena_cap))) return rc;
-            if ((rc = ensure(ctx, ctx->rad_arena_off, sizeof(int64_t) * (size_t)(n + 2)))) return rc;
-            a.rad_arena = (int32_t*)ctx->rad_arena.p;
-            a.rad_arena_off = (int64_t*)ctx->rad_arena_off.p;
-            if ((rc = ensure(ctx, ctx->rad_pos, 64))) return rc;
-            WTP_HIP(ctx, hipMemsetAsync(ctx->rad_pos.p, 0, 16, ctx->stream));
-            if ((rc = ensure(ctx, ctx->rad_bricks, sizeof(int32_t) * (size_t)(n + 64)))) return rc;
-            a.rad_bricks = (int32_t*)ctx->rad_bricks.p;
-            a.rad_arena_pos = (unsigned long long*)ctx->rad_pos.p; // the dense kernel takes pieces of the arena (wtp_radb.hip)
-            a.rad_arena_cap = arena_cap;
-        }
-        ctx->rad_rows_cached = true;
+    // them instead of running the whole search a second time (128 B per point of scratch)
+    if ((rc = ensure(ctx, ctx->rad_done, (size_t)n + 64))) return rc;
+    WTP_HIP(ctx, hipMemsetAsync(ctx->rad_done.p, 0, (size_t)n, ctx->stream));
+    a.rad_done = (uint8_t*)ctx->rad_done.p;
+    if (sizeof(T) == 4 && !ctx->force_generic) { // the brick kernel's rows: 32 ids per query
+        if ((rc = ensure(ctx, ctx->rad_tmp, sizeof(int32_t) * 32 * (size_t)n))) return rc;
+        a.rad_tmp = (int32_t*)ctx->rad_tmp.p;
     }
+    // the wave kernel's rows (any length up to its list), where it serves every query (fp64; fp32 grids whose rows are
+    // expected to outgrow the brick kernel, Grid::rad_wave_only; WTP_FORCE_GENERIC=1): an arena of 48 ids per point,
+    // shared out evenly among the waves; a row that does not fit any more is simply searched again by the fill phase.
+    // (For the hand-backs of the fp32 brick kernel it buys nothing: measured 2.07 -> 2.14 ms per graded 1 M cloud —
+    // ranking in the count phase costs what it saves in the fill phase; the kernel decides by the grid's flag.)
+    const int64_t arena_cap = 48 * n;
+    if ((rc = ensure(ctx, ctx->rad_arena, sizeof(int32_t) * (size_t)arena_cap))) return rc;
+    if ((rc = ensure(ctx, ctx->rad_arena_off, sizeof(int64_t) * (size_t)(n + 2)))) return rc;
+    a.rad_arena = (int32_t*)ctx->rad_arena.p;
+    a.rad_arena_off = (int64_t*)ctx->rad_arena_off.p;
+    if ((rc = ensure(ctx, ctx->rad_pos, 64))) return rc;
+    WTP_HIP(ctx, hipMemsetAsync(ctx->rad_pos.p, 0, 16, ctx->stream));
+    if ((rc = ensure(ctx, ctx->rad_bricks, sizeof(int32_t) * (size_t)(n + 64)))) return rc;
+    a.rad_bricks = (int32_t*)ctx->rad_bricks.p;
+    a.rad_arena_pos = (unsigned long long*)ctx->rad_pos.p; // the dense kernel takes pieces of the arena (wtp_radb.hip)
+    a.rad_arena_cap = arena_cap;
     sp = span_begin(ctx, 1);
     rc = launch_radius_count<T>(ctx, a, (T)r, d_counts);
     ctx->rad_dense_used = a.rad_dense > 0;
     span_end(ctx, sp);
-    if (!rc && a.rad_dense > 0 && getenv("WTP_DEBUG")) {
+    if (!rc && a.rad_dense > 0 && ctx->debug) {
         int32_t h[4] = {0, 0, 0, 0};
         WTP_HIP(ctx, hipMemcpyAsync(h, ctx->rad_pos.p, 16, hipMemcpyDeviceToHost, ctx->stream));
         WTP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -914,16 +901,13 @@ template <typename T> static int radius_fill_t(wtp_ctx* ctx, const int64_t* d_of
     a.fb2_count = (int32_t*)ctx->fb2_count.p;
     a.fb_list = (int32_t*)ctx->fb_list.p; // ensured by the count phase
     a.fb_count = (int32_t*)ctx->fb_count.p;
-    if (ctx->rad_rows_cached) { // (set by the count phase of this very cloud: rad_valid guards the pair of calls)
-        a.rad_tmp = sizeof(T) == 4 && !ctx->force_generic ? (int32_t*)ctx->rad_tmp.p : nullptr;
-        a.rad_done = (uint8_t*)ctx->rad_done.p;
-        {
-            a.rad_arena = (int32_t*)ctx->rad_arena.p;
-            a.rad_arena_off = (int64_t*)ctx->rad_arena_off.p;
-            a.rad_arena_cap = 48 * ctx->rad_n;
-        }
-        a.rad_dense = ctx->rad_dense_used ? 1 : 0; // (the hand-back list of the count phase is what is left to search)
-    }
+    // the rows the count phase of this very cloud parked (rad_valid guards the pair of calls)
+    a.rad_tmp = sizeof(T) == 4 && !ctx->force_generic ? (int32_t*)ctx->rad_tmp.p : nullptr;
+    a.rad_done = (uint8_t*)ctx->rad_done.p;
+    a.rad_arena = (int32_t*)ctx->rad_arena.p;
+    a.rad_arena_off = (int64_t*)ctx->rad_arena_off.p;
+    a.rad_arena_cap = 48 * ctx->rad_n;
+    a.rad_dense = ctx->rad_dense_used ? 1 : 0; // (the hand-back list of the count phase is what is left to search)
     int sp = span_begin(ctx, 1);
     int rc = launch_radius_fill<T>(ctx, a, (T)ctx->rad_r, d_off, d_idx);
     span_end(ctx, sp);
@@ -1269,7 +1253,7 @@ static int cs2_tune(wtp_ctx* ctx, RelaxState& r, const Grid<float>& hg, double r
     hc = (hc + 63) / 64 * 64;
     r.brick_hcap = hc < 256 ? 256 : (hc > 1920 ? 1920 : hc);
     r.cs2_bx = bx;
-    if (getenv("WTP_DEBUG"))
+    if (ctx->debug)
         fprintf(stderr, "[wtp] cs2 geometry: BX=%d hcap=%d (q97=%d h999=%d rho_est=%.3f grid %dx%dx%d c=%g)\n", bx,
                 r.brick_hcap, q97, h999, rho_est, hg.n[0], hg.n[1], hg.n[2], (double)hg.c);
     return WTP_OK;
@@ -1308,11 +1292,11 @@ static int relax_f64_ksel_sweep(wtp_ctx* ctx, SearchArgs<double>& a) {
     if (tuned) {
         rc = build_hash<float>(ctx, raw32, sorted32, n, 3, kc, 0.0, r.f64k_rho, 0.0, r.f64k_scale);
     } else { // once per session: cell scale and occupancy measured on the float copy (host reads)
-        double scale = 1.0, rho_eff = 0, rho_direct = ksel_rho_for(ctx, kc);
+        double scale = 1.0, rho_eff = 0, rho_direct = ksel_rho_for(kc);
         Grid<float> hg;
         rc = build_hash_tuned<float>(ctx, raw32, sorted32, n, 3, kc, 0.0, rho_direct, 0.0, &scale, &rho_eff, &hg);
         if (!rc) {
-            const double pick = ksel_pick_rho(ctx, (double)n, (double)hg.ncells, hg.n[0], rho_direct, rho_eff);
+            const double pick = ksel_pick_rho((double)n, (double)hg.ncells, hg.n[0], rho_direct, rho_eff);
             if (std::fabs(pick - rho_direct) > 0.01 * rho_direct) {
                 rho_direct = pick;
                 scale = 1.0;
@@ -1349,7 +1333,7 @@ static int relax_f64_ksel_sweep(wtp_ctx* ctx, SearchArgs<double>& a) {
         b.diag = a.diag;
         b.ksel_bx = r.f64k_bx;
         b.brick_hcap = r.f64k_hcap;
-        b.cap_count = (float)ksel_cap_count(ctx, kc);
+        b.cap_count = (float)ksel_cap_count(kc);
         WTP_HIP(ctx, hipMemsetAsync(ctx->f64k_cnt.p, 0, 64, ctx->stream));
         b.counters_cleared = 1;
         rc = launch_topology<float>(ctx, b);
@@ -1395,25 +1379,23 @@ template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_ste
                      !ctx->force_generic && !r.cs_disabled;
         // round-2 sweep (wtp_cs2.hip, fp32 3-D): the nearest neighbour comes from the support or from a
         // per-wave follow-up, so the cells only cover the support: rho ~ 1
-        const bool cs2 = r.cs_sweep && ctx->cs2 && sizeof(T) == 4 && r.dim == 3;
-        double rho_cs = r.cs_sweep ? (cs2 ? ctx->rho_cs2 : 3.5 * (ctx->rho / 9.0)) : 0.0;
+        const bool cs2 = r.cs_sweep && sizeof(T) == 4 && r.dim == 3;
+        double rho_cs = r.cs_sweep ? (cs2 ? kRhoCs2 : 3.5 * (ctx->rho / 9.0)) : 0.0;
         // every other law (and ClippedSpacingForce with WTP_FULL_SELECT=1 or over-full support cells): the sweep with the
         // explicit k-selection — on the x-slowest layout of wtp_ksel.hip where that applies (fp32, 3-D, k <= 22)
         const bool ksel_ok = sizeof(T) == 4 && r.dim == 3 && ctx->ksel && !ctx->force_generic && r.k >= 2 &&
                              r.k <= ksel_kmax() && r.n >= 4096;
         r.ksel_sweep = !r.cs_sweep && ksel_ok;
-        if (r.ksel_sweep) rho_cs = r.grid_tuned && r.ksel_rho > 0 ? r.ksel_rho : ksel_rho_for(ctx, r.k);
+        if (r.ksel_sweep) rho_cs = r.grid_tuned && r.ksel_rho > 0 ? r.ksel_rho : ksel_rho_for(r.k);
         if (r.spacing_typ <= 0) { // once per session: the spacing a typical point asks for
             r.spacing_typ = r.spacing_const;
             if (r.spacing_kind != WTP_SPACING_CONSTANT) {
                 if ((rc = ensure(ctx, ctx->occ, 64))) return rc;
                 if ((rc = ensure_pinned(ctx, 1024))) return rc;
                 if ((rc = launch_sum<T>(ctx, (const T*)ctx->spacing_pp.p, r.n, (double*)ctx->occ.p))) return rc;
-                WTP_HIP(ctx, hipMemcpyAsync(ctx->host_pinned, ctx->occ.p, 16, hipMemcpyDeviceToHost, ctx->stream));
+                WTP_HIP(ctx, hipMemcpyAsync(ctx->host_pinned, ctx->occ.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
                 if ((rc = sync(ctx))) return rc;
-                const double mean = ((const double*)ctx->host_pinned)[0] / (double)r.n;
-                const double var = ((const double*)ctx->host_pinned)[1] / (double)r.n - mean * mean;
-                r.spacing_typ = mean + ctx->styp_sigma * std::sqrt(var > 0 ? var : 0.0);
+                r.spacing_typ = ((const double*)ctx->host_pinned)[0] / (double)r.n; // the mean (mean + sigma measured only slower)
                 if (!(r.spacing_typ > 0)) r.spacing_typ = r.spacing_max;
             }
         }
@@ -1442,7 +1424,7 @@ template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_ste
                 r.cs_disabled = true;
                 r.cs_sweep = false;
                 r.ksel_sweep = ksel_ok;
-                rho_cs = r.ksel_sweep ? ksel_rho_for(ctx, r.k) : 0.0;
+                rho_cs = r.ksel_sweep ? ksel_rho_for(r.k) : 0.0;
                 min_cell = 0.0;
                 r.cell_scale = 1.0;
                 rc = build_hash_tuned<T>(ctx, (const Pt<T>*)ctx->pts[r.bufP].p, (Pt<T>*)ctx->pts[t].p, r.n, r.dim, r.k, 0.0,
@@ -1460,7 +1442,7 @@ template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_ste
                 r.brick_hcap = hc < 640 ? 640 : (hc > 2560 ? 2560 : hc);
             }
             if (r.ksel_sweep) {
-                const double pick = ksel_pick_rho(ctx, (double)r.n, (double)hg.ncells, hg.n[0], rho_cs, rho_eff);
+                const double pick = ksel_pick_rho((double)r.n, (double)hg.ncells, hg.n[0], rho_cs, rho_eff);
                 if (std::fabs(pick - rho_cs) > 0.01 * rho_cs) {
                     rho_cs = pick;
                     r.cell_scale = 1.0;
@@ -1483,7 +1465,7 @@ template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_ste
             const bool head_ok = !ctx->hash_view.active ||
                                  (r.shard_grid_reuse && r.grid_fixed > 0 &&
                                   std::llabs((long long)(r.n_fixed - r.grid_fixed)) * 10 <= (long long)r.grid_fixed + 640);
-            const bool reuse = r.grid_age < ctx->grid_reuse_max && !r.moved_by_hand && head_ok && !ctx->box_active;
+            const bool reuse = r.grid_age < kGridReuseMax && !r.moved_by_hand && head_ok && !ctx->box_active;
             ctx->reuse_grid = reuse;
             r.grid_age = reuse ? r.grid_age + 1 : 0;
             if (!reuse) r.grid_fixed = r.n_fixed;
@@ -1512,7 +1494,7 @@ template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_ste
         rc = launch_spacing_session<T>(ctx, (const Pt<T>*)ctx->pts[r.bufP].p, r.n, r.n_fixed, ctx->kd_nodes.p, ctx->kd_m,
                                        r.spacing_kind, r.sp_p0, r.sp_p1, r.sp_p2, (T*)ctx->spacing_pp.p,
                                        (int32_t*)ctx->sp_hint.p - r.aux_off, r.have_tree ? (const int32_t*)ctx->cell_start.p : nullptr,
-                                       ctx->grid.p, getenv("WTP_SP_CERT_OFF") ? nullptr : (void*)((Pt<T>*)ctx->sp_cert.p - r.aux_off)); // (the switch: A/B of the certificates)
+                                       ctx->grid.p, (Pt<T>*)ctx->sp_cert.p - r.aux_off);
         span_end(ctx, sps);
         if (rc) return rc;
     }
@@ -1572,8 +1554,8 @@ template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_ste
     a.cs2_bx = r.cs_sweep ? r.cs2_bx : 0;
     a.cs2_chunked = (r.spacing_kind != WTP_SPACING_CONSTANT || r.cs2_rho > 1.6) ? 1 : 0;
     a.ksel_bx = r.ksel_sweep ? r.ksel_bx : 0;
-    if (r.ksel_sweep) a.cap_count = (float)ksel_cap_count(ctx, r.k);
-    a.tnn_frac = (T)ctx->tnn_frac;
+    if (r.ksel_sweep) a.cap_count = (float)ksel_cap_count(r.k);
+    a.tnn_frac = (T)kTnnFrac;
     a.cover_axis = r.cover_axis;
     a.cover_lo = (T)r.cover_lo;
     a.cover_hi = (T)r.cover_hi;
@@ -1626,7 +1608,7 @@ int wtp::relax_prerank(wtp_ctx* ctx, int64_t n_fixed_new) {
     RelaxState& r = ctx->relax;
     ctx->prerank.valid = false;
     if (!r.active || !r.grid_tuned || !r.have_tree || r.pending.active || r.moved_by_hand || ctx->box_active) return WTP_OK;
-    if (r.grid_age >= ctx->grid_reuse_max || !r.shard_grid_reuse || r.grid_fixed <= 0) return WTP_OK;
+    if (r.grid_age >= kGridReuseMax || !r.shard_grid_reuse || r.grid_fixed <= 0) return WTP_OK;
     if (std::llabs((long long)(n_fixed_new - r.grid_fixed)) * 10 > (long long)r.grid_fixed + 640) return WTP_OK;
     const int64_t n_new = r.n - r.n_fixed + n_fixed_new;
     if (r.cs2_bx > 0 && std::llabs((long long)(n_fixed_new - r.tuned_fixed)) * 20 > (long long)n_new) return WTP_OK;
@@ -2464,7 +2446,7 @@ WTP_API int wtp_debug_diag(wtp_ctx* ctx, unsigned long long out[16]) {
     WTP_HIP(ctx, hipMemcpyAsync(out, ctx->diag.p, 128, hipMemcpyDeviceToHost, ctx->stream));
     WTP_HIP(ctx, hipMemsetAsync(ctx->diag.p, 0, 128, ctx->stream));
     if ((rc = sync(ctx))) return rc;
-    if (getenv("WTP_DEBUG_KD")) { // diagnostic builds: node visits of the spacing law's tree walk
+    if (ctx->debug_kd) { // diagnostic builds: node visits of the spacing law's tree walk
         unsigned long long kd[2] = {0, 0};
         wtp::debug_kd_steps(kd);
         fprintf(stderr, "[wtp] kd walk: %llu node visits by %llu wave-walks (%.1f per walk)\n", kd[0], kd[1], kd[1] ? (double)kd[0] / (double)kd[1] : 0.0);

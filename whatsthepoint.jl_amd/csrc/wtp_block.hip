@@ -66,7 +66,6 @@ struct BlockState {
     std::vector<int64_t> send_cnt, mig_cnt, recv_cnt, rmig_cnt;
     // transport
     bool host_transport = false;
-    bool overlap = true; // the owned points are ranked into the cells while the ghost rows travel (WTP_BLOCK_OVERLAP=0: after them)
     wtp_transport tr{};
     std::vector<unsigned char> hbuf_a, hbuf_b;
     // last info
@@ -627,7 +626,6 @@ WTP_API int wtp_block_open(wtp_ctx* ctx, const wtp_block_desc* desc, const void*
     if (!ctx->block) ctx->block = new BlockState();
     BlockState* b = bs_of(ctx);
     if (b->active) return fail(ctx, WTP_ERR_STATE, "wtp_block_open: a block session is open already");
-    if (const char* e = getenv("WTP_BLOCK_OVERLAP")) b->overlap = atoi(e) != 0; // (A/B switch)
     if (!b->host_transport && desc->nranks > 1 && (!ctx->comm || ctx->comm_size != desc->nranks || ctx->comm_rank != desc->rank))
         return fail(ctx, WTP_ERR_STATE, "wtp_block_open: wtp_comm_init (same rank / nranks) or wtp_block_set_transport first");
     for (int r = 0; r < desc->nranks; ++r)
@@ -689,7 +687,7 @@ static int blk_exchange_and_apply(wtp_ctx* ctx, BlockState* b) {
     if ((rc = ensure(ctx, b->pool, 16 * (size_t)(n_pool + 16)))) return rc;
     if ((rc = ensure(ctx, b->recv_mig, 32 * (size_t)(n_rmig + 16)))) return rc;
     // nobody crosses in this iteration (the usual case): the owned set stays, so its part of the rebuild can start early
-    const bool early = b->overlap && np > 0 && n_mig == 0 && n_rmig == 0;
+    const bool early = ctx->block_overlap && np > 0 && n_mig == 0 && n_rmig == 0;
     // messages: per peer (ascending rank) ghosts, then migrants
     std::vector<int> peers;
     std::vector<const void*> sp;

@@ -934,7 +934,7 @@ int brick_partials() { return 1024 + 8 + 512 + 3072; } // bricks, then the follo
 // here, the rest (longer rows, queries the 27 cells cannot certify, bricks too large for LDS) is appended
 // to a.fb_list for the wave kernel.  The caller cleared a.fb_count.
 int launch_brick_radius(wtp_ctx* ctx, SearchArgs<float>& a) {
-    a.gamma_cap = (float)ctx->gamma_cap;
+    a.gamma_cap = (float)kGammaCap;
     a.k = 1;
     return brick_launch<2, 0, 0>(ctx, a);
 }
@@ -948,8 +948,8 @@ template <> int launch_topology<float>(wtp_ctx* ctx, SearchArgs<float>& a) {
         a.fb_r0 = 3;
         return launch_generic_topology<float>(ctx, a, false);
     }
-    a.gamma_cap = (float)ctx->gamma_cap;
-    a.cap_count = (float)(4.18879 * ctx->gamma_cap * ctx->gamma_cap * ctx->gamma_cap * ctx->rho * (a.k + 1) / 22.0);
+    a.gamma_cap = (float)kGammaCap;
+    a.cap_count = (float)(4.18879 * kGammaCap * kGammaCap * kGammaCap * ctx->rho * (a.k + 1) / 22.0);
     if (!a.counters_cleared) WTP_HIP(ctx, hipMemsetAsync(a.fb_count, 0, sizeof(int32_t), ctx->stream));
     int rc = a.k == 21 ? brick_launch<0, 21, 0>(ctx, a) : brick_launch<0, 0, 0>(ctx, a);
     if (rc) return rc;
@@ -992,14 +992,14 @@ template <> int launch_sweep<float>(wtp_ctx* ctx, SearchArgs<float>& a, bool fre
         span_end(ctx, spk2);
         return rk;
     }
-    a.gamma_cap = (float)ctx->gamma_cap_sweep;
-    a.cap_count = (float)(4.18879 * ctx->gamma_cap_sweep * ctx->gamma_cap_sweep * ctx->gamma_cap_sweep * ctx->rho * (a.k + 1) / 22.0);
+    a.gamma_cap = (float)kGammaCapSweep;
+    a.cap_count = (float)(4.18879 * kGammaCapSweep * kGammaCapSweep * kGammaCapSweep * ctx->rho * (a.k + 1) / 22.0);
     const int sp = span_begin(ctx, 1);
     // ClippedSpacingForce (the reference default) takes the compact-support sweep unless
     // WTP_FULL_SELECT=1 asks for the explicit k-selection on every query (both give the same output)
     // (the caller sized the grid for it and says so by passing the LDS point capacity)
     const bool cs = a.brick_hcap > 0 && a.force_kind == WTP_FORCE_CLIPPED_SPACING && a.k >= 2 && !ctx->full_select;
-    if (cs && a.cs2_bx > 0 && a.spacing_pp && a.ball_list && !getenv("WTP_CS2_DEAD_OFF")) {
+    if (cs && a.cs2_bx > 0 && a.spacing_pp && a.ball_list) {
         // variable spacing: bricks that would hand every point back are found first and passed over (wtp_cs2.hip)
         const int dead_cap = (int)(ctx->cell_start.cap / sizeof(int32_t) / 4 + 4096);
         int rd = ensure(ctx, ctx->brick_dead, (size_t)dead_cap);
@@ -1045,7 +1045,7 @@ template <> int launch_sweep<double>(wtp_ctx* ctx, SearchArgs<double>& a, bool f
         span_end(ctx, sp);
         return rc;
     }
-    a.gamma_cap = ctx->gamma_cap;
+    a.gamma_cap = kGammaCap;
     const int sp = span_begin(ctx, 1);
     int rc = launch_brick_cs<double>(ctx, a);
     // variable spacing: the hand-backs whose support ball is wider than a cell (wtp_ball64.hip), before the exact path

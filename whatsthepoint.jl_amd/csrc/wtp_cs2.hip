@@ -1056,7 +1056,6 @@ int launch_cs_all_slots(wtp_ctx* ctx, int32_t* list, int32_t n, int32_t* count) 
 int launch_cs_ball(wtp_ctx* ctx, SearchArgs<float>& a, int32_t* rest_list, int32_t* rest_count) {
     int blocks = (int)((a.n + 1023) / 1024);
     blocks = blocks < 8 ? 8 : (blocks > kBallBlocksMax ? kBallBlocksMax : blocks);
-    if (const char* e = getenv("WTP_BALL_BLOCKS")) blocks = atoi(e) > 0 && atoi(e) <= kBallBlocksMax ? atoi(e) : blocks;
     hipLaunchKernelGGL(cs_ball_kernel, dim3(blocks), dim3(kBallThreads), 0, ctx->stream, a, (const int32_t*)a.fb_list,
                        (const int32_t*)a.fb_count, rest_list, rest_count, a.used_brick);
     a.used_brick += blocks;

@@ -142,10 +142,9 @@ template <typename T> int launch_query_knn(wtp_ctx* ctx, SearchArgs<T>& a, const
     return WTP_OK;
 }
 
-// ---- RadiusTopology: count, then fill rows sorted by (d2, id) ---------------------------------
-template <typename T, bool FILL>
-__global__ __launch_bounds__(kThreads) void radius_kernel(SearchArgs<T> a, T r, int32_t* __restrict__ counts,
-                                                          const int64_t* __restrict__ offsets,
+// ---- RadiusTopology: fill rows sorted by (d2, id) -----------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(kThreads) void radius_kernel(SearchArgs<T> a, T r, const int64_t* __restrict__ offsets,
                                                           int32_t* __restrict__ idx_out, T* __restrict__ d2_tmp,
                                                           const int32_t* __restrict__ list,
                                                           const int32_t* __restrict__ list_count) {
@@ -160,8 +159,8 @@ __global__ __launch_bounds__(kThreads) void radius_kernel(SearchArgs<T> a, T r, 
         const int z0 = cz - 1 < 0 ? 0 : cz - 1, z1 = cz + 1 > g.n[2] - 1 ? g.n[2] - 1 : cz + 1;
         const int y0 = cy - 1 < 0 ? 0 : cy - 1, y1 = cy + 1 > g.n[1] - 1 ? g.n[1] - 1 : cy + 1;
         const int x0 = cx - 1 < 0 ? 0 : cx - 1, x1 = cx + 1 > g.n[0] - 1 ? g.n[0] - 1 : cx + 1;
-        int64_t base = FILL ? offsets[id] : 0;
-        int64_t cap = FILL ? offsets[id + 1] - base : 0;
+        const int64_t base = offsets[id];
+        const int64_t cap = offsets[id + 1] - base;
         int32_t m = 0;
         for (int z = z0; z <= z1; ++z)
             for (int y = y0; y <= y1; ++y) {
@@ -173,36 +172,26 @@ __global__ __launch_bounds__(kThreads) void radius_kernel(SearchArgs<T> a, T r, 
                     if (cid == id) continue; // filter(!=(i), n), src/topology.jl:96
                     const T d = dist2<T>(q.x, q.y, q.z, c.x, c.y, c.z);
                     if (!(d <= r2)) continue;
-                    if (FILL) {
-                        if (m >= cap) continue;
-                        int64_t pos = m;
-                        while (pos > 0 && lex_lt(d, cid, d2_tmp[base + pos - 1], idx_out[base + pos - 1])) {
-                            d2_tmp[base + pos] = d2_tmp[base + pos - 1];
-                            idx_out[base + pos] = idx_out[base + pos - 1];
-                            --pos;
-                        }
-                        d2_tmp[base + pos] = d;
-                        idx_out[base + pos] = cid;
+                    if (m >= cap) continue;
+                    int64_t pos = m;
+                    while (pos > 0 && lex_lt(d, cid, d2_tmp[base + pos - 1], idx_out[base + pos - 1])) {
+                        d2_tmp[base + pos] = d2_tmp[base + pos - 1];
+                        idx_out[base + pos] = idx_out[base + pos - 1];
+                        --pos;
                     }
+                    d2_tmp[base + pos] = d;
+                    idx_out[base + pos] = cid;
                     ++m;
                 }
             }
-        if (!FILL) counts[id] = m;
     }
 }
 
 
 // Exact path = wave-per-query kernel over the list (or all points), then this serial kernel over
-// whatever the wave kernel could not buffer (fb2 list).  WTP_FORCE_GENERIC=2 runs everything
-// through the serial kernel (debug).
+// whatever the wave kernel could not buffer (fb2 list).
 template <typename T> int launch_generic_topology(wtp_ctx* ctx, SearchArgs<T>& a, bool all) {
     if (!a.counters_cleared) WTP_HIP(ctx, hipMemsetAsync(a.fb2_count, 0, sizeof(int32_t), ctx->stream));
-    if (ctx->force_generic == 2) {
-        hipLaunchKernelGGL((generic_kernel<T, 0>), dim3(blocks_for(a.n, all ? 65536 : 1024)), dim3(kThreads), 0,
-                           ctx->stream, a, a.fb_list, a.fb_count, all ? 1 : 0, 0);
-        WTP_HIP(ctx, hipGetLastError());
-        return WTP_OK;
-    }
     int rc = launch_wave_topology<T>(ctx, a, all);
     if (rc) return rc;
     hipLaunchKernelGGL((generic_kernel<T, 0>), dim3(256), dim3(kThreads), 0, ctx->stream, a, a.fb2_list,
@@ -217,13 +206,6 @@ template <typename T> int launch_generic_topology(wtp_ctx* ctx, SearchArgs<T>& a
 template <typename T> int launch_generic_sweep(wtp_ctx* ctx, SearchArgs<T>& a, bool all) {
     const int part_base = a.n_partials - kGenericPartials;
     // counters were cleared by the caller (one block for fb_count / fb2_count / uncovered)
-    if (ctx->force_generic == 2) {
-        a.used_generic = blocks_for(a.n, kGenericPartials);
-        hipLaunchKernelGGL((generic_kernel<T, 1>), dim3(a.used_generic), dim3(kThreads), 0, ctx->stream, a, a.fb_list,
-                           a.fb_count, all ? 1 : 0, part_base);
-        WTP_HIP(ctx, hipGetLastError());
-        return WTP_OK;
-    }
     int rc = launch_wave_sweep<T>(ctx, a, all);
     if (rc) return rc;
     // serial last resort over what the wave kernel could not buffer: a handful of queries at most
@@ -294,16 +276,8 @@ __global__ void radius_copy_rows_kernel(int64_t n, const int32_t* __restrict__ t
 
 template <typename T>
 int launch_radius_count(wtp_ctx* ctx, SearchArgs<T>& a, T r, int32_t* d_counts) {
-    if (ctx->force_generic == 2) {
-        hipLaunchKernelGGL((radius_kernel<T, false>), dim3(blocks_for(a.n, 65536)), dim3(kThreads), 0, ctx->stream,
-                           a, r, d_counts, (const int64_t*)nullptr, (int32_t*)nullptr, (T*)nullptr,
-                           (const int32_t*)nullptr, (const int32_t*)nullptr);
-        WTP_HIP(ctx, hipGetLastError());
-        return WTP_OK;
-    }
     // the brick-staged wave-per-query kernel (wtp_radb.hip) needs somewhere to park its rows and a list to hand back to
-    const bool dense = !ctx->force_generic && a.rad_done && a.rad_arena && a.rad_arena_pos && a.rad_bricks && a.fb_list && a.fb_count &&
-                       !(getenv("WTP_RADIUS_DENSE") && atoi(getenv("WTP_RADIUS_DENSE")) == 0); // (A/B switch)
+    const bool dense = ctx->radius_dense && !ctx->force_generic && a.rad_done && a.rad_arena && a.rad_arena_pos && a.rad_bricks && a.fb_list && a.fb_count;
     a.rad_dense = dense ? radius_dense_hcap<T>() : 0;
     if (brick_radius_usable<T>(ctx, a) || dense) {
         // fp32: LDS-staged brick kernel first (lane per query, rows up to 32 entries); then the dense bricks (fp64: all bricks),
@@ -327,41 +301,21 @@ int launch_radius_count(wtp_ctx* ctx, SearchArgs<T>& a, T r, int32_t* d_counts) 
 // sorted in place by the serial kernel, which needs a d2 scratch row (ctx->scratch).
 template <typename T>
 int launch_radius_fill(wtp_ctx* ctx, SearchArgs<T>& a, T r, const int64_t* d_offsets, int32_t* d_idx) {
-    if (ctx->force_generic == 2) {
-        hipLaunchKernelGGL((radius_kernel<T, true>), dim3(blocks_for(a.n, 65536)), dim3(kThreads), 0, ctx->stream,
-                           a, r, (int32_t*)nullptr, d_offsets, d_idx, (T*)ctx->scratch.p, (const int32_t*)nullptr,
-                           (const int32_t*)nullptr);
-        WTP_HIP(ctx, hipGetLastError());
-        return WTP_OK;
-    }
     WTP_HIP(ctx, hipMemsetAsync(a.fb2_count, 0, sizeof(int32_t), ctx->stream));
+    // the count phase parked the rows it found: copy them.  What it could not park (arena full, rows beyond the wave
+    // kernel's list) is searched again: by the wave kernel over the brick kernel's hand-back list, which still stands
+    // (fp32), or over all points (it skips the parked ones), then by the serial kernel
+    hipLaunchKernelGGL(radius_copy_rows_kernel, dim3(blocks_for((int64_t)a.n * 16, 16384)), dim3(kThreads), 0, ctx->stream,
+                       (int64_t)a.n, (const int32_t*)a.rad_tmp, (const uint8_t*)a.rad_done, (const int32_t*)a.rad_arena,
+                       (const int64_t*)a.rad_arena_off, d_offsets, d_idx);
     int rc;
-    if (a.rad_done && (a.rad_arena || (brick_radius_usable<T>(ctx, a) && a.rad_tmp))) {
-        // the count phase parked the rows it found: copy them.  What it could not park (arena full, rows beyond the wave
-        // kernel's list) is searched again: by the wave kernel over the brick kernel's hand-back list, which still stands
-        // (fp32), or over all points (it skips the parked ones), then by the serial kernel
-        hipLaunchKernelGGL(radius_copy_rows_kernel, dim3(blocks_for((int64_t)a.n * 16, 16384)), dim3(kThreads), 0, ctx->stream,
-                           (int64_t)a.n, (const int32_t*)a.rad_tmp, (const uint8_t*)a.rad_done, (const int32_t*)a.rad_arena,
-                           (const int64_t*)a.rad_arena_off, d_offsets, d_idx);
-        if ((brick_radius_usable<T>(ctx, a) && a.rad_tmp) || a.rad_dense)
-            rc = launch_wave_radius_fill<T>(ctx, a, r, d_offsets, d_idx, a.fb_list, a.fb_count);
-        else
-            rc = launch_wave_radius_fill<T>(ctx, a, r, d_offsets, d_idx, nullptr, nullptr);
-    } else if (brick_radius_usable<T>(ctx, a)) {
-        WTP_HIP(ctx, hipMemsetAsync(a.fb_count, 0, sizeof(int32_t), ctx->stream));
-        a.radius2 = r * r;
-        a.rad_counts = nullptr;
-        a.rad_offsets = d_offsets;
-        a.rad_fill = 1;
-        a.idx_out = d_idx;
-        if ((rc = brick_radius<T>(ctx, a))) return rc;
+    if ((brick_radius_usable<T>(ctx, a) && a.rad_tmp) || a.rad_dense)
         rc = launch_wave_radius_fill<T>(ctx, a, r, d_offsets, d_idx, a.fb_list, a.fb_count);
-    } else {
+    else
         rc = launch_wave_radius_fill<T>(ctx, a, r, d_offsets, d_idx, nullptr, nullptr);
-    }
     if (rc) return rc;
-    hipLaunchKernelGGL((radius_kernel<T, true>), dim3(256), dim3(kThreads), 0, ctx->stream, a, r, (int32_t*)nullptr,
-                       d_offsets, d_idx, (T*)ctx->scratch.p, (const int32_t*)a.fb2_list, (const int32_t*)a.fb2_count);
+    hipLaunchKernelGGL((radius_kernel<T>), dim3(256), dim3(kThreads), 0, ctx->stream, a, r, d_offsets, d_idx,
+                       (T*)ctx->scratch.p, (const int32_t*)a.fb2_list, (const int32_t*)a.fb2_count);
     WTP_HIP(ctx, hipGetLastError());
     return WTP_OK;
 }

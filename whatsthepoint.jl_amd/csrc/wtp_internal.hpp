@@ -69,6 +69,15 @@ constexpr int kGenericPartials = 1024; // serial last-resort kernel blocks
 int brick_partials();
 constexpr int kGenericKMax = 128; // largest k the library accepts (generic kernel's list)
 
+// ---- tuned search constants (measured) ------------------------------------------------
+constexpr double kGammaCap = 1.0;       // first filter radius of the topology kernels, in cell edges (round 2: 1.08 -> 1.0, fewer ring prunes)
+constexpr double kGammaCapSweep = 0.96; // the same for the sweep with explicit k-selection (4.28 -> 3.55 ms at 10 M)
+constexpr double kTnnFrac = 0.8;        // CS sweeps: measured optimum between candidate volume and isolated-query hand-backs (0.9: 1.55 ms, 0.8: 1.44, 0.7: 1.69 per 10 M step)
+constexpr double kRhoCs2 = 1.0;         // target points per cell of the round-2 compact-support sweep (the support floor usually binds)
+constexpr double kRhoKsel = 1.2;        // points per cell of the wtp_ksel.hip grids at k + self = 22 (scales with k)
+constexpr double kCapKsel = 40.0;       // points the first filter ball of wtp_ksel.hip is expected to hold at k + self = 22
+constexpr int kGridReuseMax = 7;        // rebuilds of a relax session that may reuse a grid
+
 // ---- per-block partial reductions of one sweep -------------------------------------------------
 struct Partial {
     double max_force;
@@ -145,7 +154,7 @@ template <typename T> struct SearchArgs {
     // tunables
     T gamma_cap;               // initial filter radius cap, in cell edges
     float cap_count;           // k-selection kernels: points the first filter ball is expected to hold (0: fixed gamma_cap * c)
-    T tnn_frac;                // CS sweeps: nearest-neighbour margin of the ring, in cell edges (WTP_TNN, default 0.8)
+    T tnn_frac;                // CS sweeps: nearest-neighbour margin of the ring, in cell edges (kTnnFrac)
     int32_t brick_hcap;        // LDS point capacity for the brick kernel (0 = default)
     int32_t cs2_bx;            // > 0: brick length (own cells along x) of the round-2 compact-support sweep (wtp_cs2.hip)
     const uint8_t* brick_dead; // wtp_cs2.hip, variable spacing: bricks whose points all went to the ball kernel's list already (cs2_dead_kernel), or nullptr
@@ -241,25 +250,23 @@ struct wtp_ctx {
     hipStream_t own_stream = nullptr; // created with the context; `stream` unless wtp_set_stream lent another
     std::string err;
     int sm_count = 256;
-    // tunables (env WTP_RHO / WTP_GAMMA_CAP / WTP_FORCE_GENERIC)
-    double rho = 9.0;            // WTP_RHO: points per cell of the k = 21 selection grids (round 2: 8 -> 9, fewer hand-backs; measured)
-    double gamma_cap = 1.0;      // WTP_GAMMA_CAP: first filter radius of the topology kernels, in cell edges (round 2: 1.08 -> 1.0, fewer ring prunes)
-    double gamma_cap_sweep = 0.96; // WTP_GAMMA_CAP_SWEEP: the same for the sweep with explicit k-selection (4.28 -> 3.55 ms at 10 M)
-    double tnn_frac = 0.8;     // WTP_TNN: measured optimum between candidate volume and isolated-query hand-backs (0.9: 1.55 ms, 0.8: 1.44, 0.7: 1.69 per 10 M step)
-    int force_generic = 0;
+    // switches, read from the environment by wtp_create only
+    double rho = 9.0;          // WTP_RHO: points per cell of the k = 21 selection grids (round 2: 8 -> 9, fewer hand-backs; measured)
+    int force_generic = 0;     // WTP_FORCE_GENERIC=1: the exact wave / serial path for everything (sums in the reference's order)
     int full_select = 0;       // WTP_FULL_SELECT=1: never use the compact-support sweep
-    int cs2 = 1;               // WTP_CS2=0: the round-1 compact-support sweep (brick_kernel<1,0,1>) instead of wtp_cs2.hip
-    double rho_cs2 = 1.0;      // WTP_RHO_CS: target points per cell of the round-2 sweep (the support floor usually binds)
     int ksel = 1;              // WTP_KSEL=0: the round-1 k-selection kernels (4 x 4 x 4 bricks, wtp_brick.hip) instead of wtp_ksel.hip
-    double rho_ksel = 1.2;     // WTP_RHO_KSEL: points per cell of the wtp_ksel.hip grids at k + self = 22 (scales with k)
-    double cap_ksel = 40.0;    // WTP_CAP_KSEL: points the first filter ball of wtp_ksel.hip is expected to hold at k + self = 22
+    int ball64 = 1;            // WTP_BALL64=0: Float64 variable-spacing hand-backs straight to the wave kernel
+    int f64_ksel = 1;          // WTP_F64_KSEL=0: Float64 sweeps of the k-nearest laws on the exact wave-per-query path
+    int radius_dense = 1;      // WTP_RADIUS_DENSE=0: RadiusTopology without the brick-staged kernel for long rows (wtp_radb.hip)
+    int block_overlap = 1;     // WTP_BLOCK_OVERLAP=0: block sessions rank the owned points into the cells after the ghost rows arrive, not while they travel
+    bool debug = false;        // WTP_DEBUG: hand-back counts and brick geometry on stderr
+    bool debug_kd = false;     // WTP_DEBUG_KD: node visits of the spacing law's tree walk on stderr
     size_t cs2_smem = 0;       // launch attributes of cs2_kernel cached per context
     const void* cs2_fn = nullptr; // (and the variant they belong to)
     int cs2_occ = 0;
     // (kernel, dynamic LDS bytes) -> blocks per CU, per CONTEXT: the dynamic-LDS attribute and the occupancy are
     // properties of a kernel on one device, and several contexts (devices) may live in one process
     std::map<std::pair<const void*, size_t>, int> launch_cache;
-    double styp_sigma = 0.0;   // WTP_STYP_SIGMA: typical spacing = mean + this many standard deviations (measured: > 0 only hurts)
     // the same cache for the fp32 candidate search of fp64 topology calls (knn_dev_f64)
     int64_t knn64_tune_n = -1;
     int knn64_tune_dim = 0, knn64_tune_k = 0, knn64_tune_ksel = -1, knn64_tune_bx = 0, knn64_tune_hcap = 0;
@@ -280,7 +287,6 @@ struct wtp_ctx {
     bool topology_build = false; // set around the hash builds of KNN / radius topology calls: their rows are ordered by (d2, id) explicitly, so the
                                  // within-cell order by id (canon_kernel: 0.3 of a 1.1 ms KNN call on unsorted input) buys nothing there
     bool reuse_grid = false;   // one-shot: the next build_hash keeps the previous Grid (no bounding-box pass)
-    int grid_reuse_max = 7;    // WTP_GRID_REUSE: rebuilds of a relax session that may reuse a grid (0 = never)
     bool box_active = false;   // grid_setup clips the bounding box to box_dev (outliers piled into edge cells)
     const void* ncells_dev = nullptr; // device address of Grid::ncells of the last build_hash
     wtp::DevBuf idx_out, dist_out, counts_out;
@@ -288,8 +294,6 @@ struct wtp_ctx {
     // fp64 sweeps through fp32 candidates (wtp_sweep64.hip): the session's grid and cell table parked while the float copy's
     // are built and searched; the fp64 points and their session slots in the float copy's order; the search's own lists
     wtp::DevBuf grid_b, cell_start_b, f64k_s64, f64k_slot, f64k_lists, f64k_cnt;
-    int ball64 = 1;                           // WTP_BALL64=0: Float64 variable-spacing hand-backs straight to the wave kernel
-    int f64_ksel = 1;                         // WTP_F64_KSEL=0: the exact wave-per-query path for those sweeps
     wtp::DevBuf forces, nn_dist, nn_id, spacing_pp;
     wtp::DevBuf partials, stats, fb_list, fb_count, fb2_list, fb2_count, nn_list;
     wtp::DevBuf rad_pos;           // counter block: [0, 8) next free id of the arena (wtp_radb.hip takes pieces of it), [8, 12) bricks listed
@@ -323,7 +327,6 @@ struct wtp_ctx {
     bool mesh_cls_ready = false;
     int mesh_cls_dim[3] = {0, 0, 0};
     double mesh_cls_cell = 0;
-    int mesh_packet = 0;                // WTP_MESH_PACKET=1: standalone queries walk the tree as wave packets
     wtp::DevBuf sp_hint;       // variable spacings: nearest tree node of each snapshot point at the last sweep
     wtp::DevBuf kd_nodes;      // variable spacings: kd-tree over the boundary points (heap order)
     int64_t kd_m = 0;          // nodes in it; the key below identifies the boundary it was built from
@@ -343,7 +346,6 @@ struct wtp_ctx {
     double rad_r = 0;
     int64_t rad_nnz = 0;
     bool rad_valid = false;
-    bool rad_rows_cached = false; // the count phase parked the brick kernel's rows (rad_tmp / rad_done): the fill phase copies them
     bool rad_offsets_dev = false; // wtp_radius_offsets left the CSR offsets in dist_out (device): fill may take them from there
     wtp::RelaxState relax;
     // timers

@@ -294,16 +294,6 @@ __device__ inline int tri_closest(const T* p, const T* a, const T* b, const T* c
     return 0;
 }
 
-#ifdef WTP_MESH_COUNT
-__device__ unsigned long long g_mesh_count[4];
-extern "C" int wtp_mesh_count(unsigned long long out[4]) {
-    unsigned long long z[4] = {0, 0, 0, 0};
-    hipMemcpyFromSymbol(out, HIP_SYMBOL(g_mesh_count), sizeof(z));
-    hipMemcpyToSymbol(HIP_SYMBOL(g_mesh_count), z, sizeof(z));
-    return 0;
-}
-#endif
-
 template <typename T> struct Nearest {
     T d2;
     T cp[3];
@@ -375,7 +365,7 @@ __device__ inline int32_t mesh_greedy_guess(const MeshNode<T>* __restrict__ node
 }
 
 // Per-lane walk for a query that brings a good first guess (the tree node of its nearest triangle at the
-// last sweep).  The packet walk below visits the UNION of what 64 lanes want — measured 98 node steps
+// last sweep).  A packet walk (the wave's 64 lanes together) visits the UNION of what they want — measured 98 node steps
 // per wave on the box surface although a lane with a tight bound wants ~30 — so with a guess every lane
 // walks alone: stackless (pre-order with arithmetic skips in the heap-ordered tree), own triangle of a
 // node evaluated only if its bbox is within the bound.  Same candidates, same (d2, index) minimum.
@@ -484,114 +474,6 @@ __device__ inline Nearest<T> mesh_nearest_guess(const MeshNode<T>* __restrict__ 
     return r;
 }
 
-// Packet traversal (all 64 lanes of the wave call this together; inactive lanes never ask for a subtree).
-template <typename T>
-__device__ inline Nearest<T> mesh_nearest(const MeshNode<T>* __restrict__ nodes, int32_t m, const T* q, bool active,
-                                          T scale, int32_t* __restrict__ stack /* LDS row of this wave */,
-                                          int32_t hint = -1, int32_t* best_node = nullptr) {
-    Nearest<T> r;
-    r.d2 = Lim<T>::inf();
-    r.cp[0] = q[0], r.cp[1] = q[1], r.cp[2] = q[2];
-    r.tri = -1;
-    r.feat = 0;
-    int32_t bn = -1;
-    T aq = q[0] < 0 ? -q[0] : q[0];
-    const T ay = q[1] < 0 ? -q[1] : q[1], az = q[2] < 0 ? -q[2] : q[2];
-    aq = aq > ay ? aq : ay;
-    aq = aq > az ? aq : az;
-    const T delta = (T)64 * EpsOf<T>::v * (aq > scale ? aq : scale);
-    T limit = active ? Lim<T>::inf() : (T)-1; // box distance >= 0 > -1
-    if (active && hint >= 0 && hint < m) { // the nearest triangle of the last sweep: a point moves a fraction of a
-        const MeshNode<T>& hn = nodes[hint]; // spacing per sweep, so this already prunes nearly every subtree
-        T v[9];
-#pragma unroll
-        for (int a = 0; a < 9; ++a) v[a] = hn.v[a];
-        T cp[3], dv[3];
-        r.feat = tri_closest<T>(q, v, v + 3, v + 6, cp);
-#pragma unroll
-        for (int a = 0; a < 3; ++a) dv[a] = q[a] - cp[a];
-        r.d2 = ddot(dv, dv);
-        r.tri = hn.tri_axis & 0x3fffffff;
-        r.cp[0] = cp[0], r.cp[1] = cp[1], r.cp[2] = cp[2];
-        bn = hint;
-        if (!(r.d2 == r.d2)) { // degenerate triangle: no candidate
-            r.d2 = Lim<T>::inf();
-            r.tri = -1;
-            bn = -1;
-        }
-        limit = prune_limit<T>(r.d2, delta);
-    }
-    int sp = 0;
-    int32_t node = 0;
-#ifdef WTP_MESH_COUNT
-    int steps = 0, evals = 0;
-#endif
-    for (;;) {
-        node = __builtin_amdgcn_readfirstlane(node);
-        const MeshNode<T> nd = nodes[node];
-#ifdef WTP_MESH_COUNT
-        ++steps;
-#endif
-        T t[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const T below = nd.lo[a] - q[a], above = q[a] - nd.hi[a];
-            const T mm = below > above ? below : above;
-            t[a] = mm > (T)0 ? mm : (T)0;
-        }
-        const bool want = ((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]) <= limit;
-        bool descended = false;
-        if (__any(want)) {
-#ifdef WTP_MESH_COUNT
-            ++evals;
-#endif
-            const int32_t tri = nd.tri_axis & 0x3fffffff, sd = (nd.tri_axis >> 30) & 3;
-            if (want && tri_box_d2<T>(nd.v, q) <= limit) { // the node's own triangle may be far although its subtree is near
-                T cp[3], dv[3];
-                const int f = tri_closest<T>(q, nd.v, nd.v + 3, nd.v + 6, cp);
-#pragma unroll
-                for (int a = 0; a < 3; ++a) dv[a] = q[a] - cp[a];
-                const T d2 = ddot(dv, dv);
-                if (d2 < r.d2 || (d2 == r.d2 && tri < r.tri)) {
-                    r.d2 = d2;
-                    r.tri = tri;
-                    r.feat = f;
-                    r.cp[0] = cp[0], r.cp[1] = cp[1], r.cp[2] = cp[2];
-                    bn = node;
-                    limit = prune_limit<T>(d2, delta);
-                }
-            }
-            const T cen = ((nd.v[sd] + nd.v[3 + sd]) + nd.v[6 + sd]) / (T)3;
-            const bool lft = q[sd] < cen;
-            const int32_t left = 2 * node + 1;
-            const int nl = __popcll(__ballot(want && lft)), nr = __popcll(__ballot(want && !lft));
-            const int32_t first = left + (nl >= nr ? 0 : 1), second = left + (nl >= nr ? 1 : 0);
-            if (second < m && sp < 64) {
-                if ((threadIdx.x & 63) == 0) stack[sp] = second;
-                ++sp;
-            }
-            if (first < m) {
-                node = first;
-                descended = true;
-            }
-        }
-        if (!descended) {
-            if (sp == 0) break;
-            node = stack[--sp];
-        }
-    }
-#ifdef WTP_MESH_COUNT
-    if (best_node && (threadIdx.x & 63) == 0) {
-        atomicAdd(g_mesh_count, (unsigned long long)steps);
-        atomicAdd(g_mesh_count + 1, (unsigned long long)evals);
-        atomicAdd(g_mesh_count + 2, 1ull);
-        atomicMax(g_mesh_count + 3, (unsigned long long)steps);
-    }
-#endif
-    if (best_node) *best_node = bn;
-    return r;
-}
-
 template <typename T> struct MeshView {
     const MeshNode<T>* nodes;
     const T* pn; // nt x 7 x 3
@@ -670,21 +552,16 @@ template <typename TM, typename TP>
 __global__ void __launch_bounds__(kMeshThreads)
 mesh_query_kernel(const TP* __restrict__ xyz, int64_t n, MeshView<TM> mv, TM offset, TP* __restrict__ sd_out,
                   int32_t* __restrict__ tri_out, TP* __restrict__ cp_out, uint8_t* __restrict__ inside_out,
-                  TP* __restrict__ proj_out, int packet) {
-    __shared__ int32_t stk[kMeshThreads / 64][64];
+                  TP* __restrict__ proj_out) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t span = (n + 63) / 64 * 64;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < span; i += stride) {
         const bool active = i < n;
         const int64_t ii = active ? i : n - 1;
         const TM q[3] = {(TM)xyz[3 * ii], (TM)xyz[3 * ii + 1], (TM)xyz[3 * ii + 2]}; // seam: convert once at entry
-        Nearest<TM> r;
-        if (packet) {
-            r = mesh_nearest<TM>(mv.nodes, mv.m, q, active, mv.scale, stk[threadIdx.x >> 6]);
-        } else {
-            int32_t bn;
-            r = mesh_nearest_guess<TM>(mv.nodes, mv.m, q, active, mv.scale, mesh_greedy_guess<TM>(mv.nodes, mv.m, q), &bn);
-        }
+        int32_t bn;
+        const Nearest<TM> r =
+            mesh_nearest_guess<TM>(mv.nodes, mv.m, q, active, mv.scale, mesh_greedy_guess<TM>(mv.nodes, mv.m, q), &bn);
         if (!active) continue;
         if (r.tri < 0) { // every triangle degenerate: no nearest element (closest_idx == 0 in the reference)
             if (sd_out) sd_out[i] = Lim<TP>::inf();
@@ -796,7 +673,7 @@ template <typename TM, typename TP>
 static int launch_mesh_query(wtp_ctx* ctx, const TP* d_xyz, int64_t n, double offset, TP* sd, int32_t* tri, TP* cp,
                              uint8_t* inside, TP* proj) {
     hipLaunchKernelGGL((mesh_query_kernel<TM, TP>), dim3(mesh_grid(n)), dim3(kMeshThreads), 0, ctx->stream, d_xyz, n,
-                       make_view<TM>(ctx), (TM)offset, sd, tri, cp, inside, proj, ctx->mesh_packet);
+                       make_view<TM>(ctx), (TM)offset, sd, tri, cp, inside, proj);
     WTP_HIP(ctx, hipGetLastError());
     return WTP_OK;
 }

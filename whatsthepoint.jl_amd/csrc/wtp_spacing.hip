@@ -309,7 +309,7 @@ __global__ void spacing_session_kernel(const Pt<T>* __restrict__ pts, int64_t n,
                                        const KdNode<T>* __restrict__ nodes, int32_t m, SpacingLaw<T> law,
                                        T* __restrict__ spacing_pp, int32_t* __restrict__ hint,
                                        const int32_t* __restrict__ stop, const int32_t* __restrict__ cell_start,
-                                       const Grid<T>* __restrict__ gp, Pt<T>* __restrict__ cert, int queue_on) {
+                                       const Grid<T>* __restrict__ gp, Pt<T>* __restrict__ cert) {
     __shared__ int32_t kd_stack[kSpThreads / 64][64];
     __shared__ int32_t kd_queue[kSpThreads / 64][128];
     if (stop && *stop) return;
@@ -333,14 +333,12 @@ __global__ void spacing_session_kernel(const Pt<T>* __restrict__ pts, int64_t n,
         if (need) {
             spacing_pp[id] = spacing_law<T>(law, wsqrt(d2));
             hint[id] = bn; // points move a fraction of a spacing per sweep: next time this is (nearly) the answer
-            if (cert) {
-                Pt<T> c;
-                c.x = p.x;
-                c.y = p.y;
-                c.z = p.z;
-                c.w = lb;
-                cert[id] = c;
-            }
+            Pt<T> c;
+            c.x = p.x;
+            c.y = p.y;
+            c.z = p.z;
+            c.w = lb;
+            cert[id] = c;
         }
     };
     auto one = [&](int64_t slot, bool on) {
@@ -351,7 +349,7 @@ __global__ void spacing_session_kernel(const Pt<T>* __restrict__ pts, int64_t n,
         int32_t h = -1;
         if (active) {
             h = hint[id];
-            if (cert && h >= 0 && h < m) {
+            if (h >= 0 && h < m) {
                 const Pt<T> c = cert[id];
                 if (c.w > (T)0) { // (never walked: the bits of -1)
                     const Pt<T> b = nodes[h].p;
@@ -389,7 +387,7 @@ __global__ void spacing_session_kernel(const Pt<T>* __restrict__ pts, int64_t n,
         for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < span; i += stride) one(i, i < n);
         return;
     }
-    queue = queue_on ? kd_queue[threadIdx.x >> 6] : nullptr;
+    queue = kd_queue[threadIdx.x >> 6];
     const Grid<T> g = *gp;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // tile = W x H x Hz cells, as cubic as the occupancy allows and ~56 points: up to 64 row segments, one per lane
@@ -444,7 +442,7 @@ __global__ void spacing_session_kernel(const Pt<T>* __restrict__ pts, int64_t n,
         }
         __builtin_amdgcn_wave_barrier();
     }
-    if (queue && qn > 0) { // what is left in the queue (fewer than 64)
+    if (qn > 0) { // what is left in the queue (fewer than 64)
         const int lane_ = threadIdx.x & 63;
         search(queue[lane_ < qn ? lane_ : 0], lane_ < qn);
     }
@@ -472,7 +470,7 @@ int launch_spacing_session(wtp_ctx* ctx, const Pt<T>* pts, int64_t n, int64_t fi
     SpacingLaw<T> law{kind, (T)p0, (T)p1, (T)p2};
     hipLaunchKernelGGL(spacing_session_kernel<T>, dim3(sp_grid(n)), dim3(kSpThreads), 0, ctx->stream, pts, n,
                        (int32_t)first_id, (const KdNode<T>*)d_nodes, (int32_t)m, law, d_spacing_pp, d_hint, ctx->stop_dev,
-                       d_cell_start, (const Grid<T>*)d_grid, (Pt<T>*)d_cert, getenv("WTP_SP_QUEUE") ? atoi(getenv("WTP_SP_QUEUE")) : 1);
+                       d_cell_start, (const Grid<T>*)d_grid, (Pt<T>*)d_cert);
     WTP_HIP(ctx, hipGetLastError());
     return WTP_OK;
 }
