@@ -157,8 +157,7 @@ static int check_cloud(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dt
 // first build of a session / call measures the occupancy the POINTS see (sum cnt^2 / sum cnt, = rho + 1
 // for a Poisson cloud) and shrinks the cell edge until that matches the target; at most 3 builds,
 // one small read-back each.  Floors (radius, the force law's support) stay in force.
-static double hash_target_rho(const wtp_ctx* ctx, int dim, int k, double radius, double rho_direct) {
-    if (radius > 0) return 2.0;
+static double hash_target_rho(const wtp_ctx* ctx, int dim, int k, double rho_direct) {
     if (rho_direct > 0) return rho_direct < 1.0 ? 1.0 : rho_direct;
     const double r = (dim == 3 ? 0.381 : 0.436) * (double)(k > 0 ? k : 21) * (ctx->rho / 8.0);
     return r < 1.0 ? 1.0 : r;
@@ -219,11 +218,13 @@ static int find_robust_box(wtp_ctx* ctx, const Pt<T>* in, int64_t n, int dim, co
     return WTP_OK;
 }
 
+// Measured build: the cell scale into t.scale (from 1) and the occupancy asked for into t.rho; the grid of the last build and
+// the occupancy its points see into *hg_out / *rho_eff_out.
 template <typename T>
-static int build_hash_tuned(wtp_ctx* ctx, const Pt<T>* in, Pt<T>* out, int64_t n, int dim, int k, double radius,
-                            double rho_direct, double min_cell, double* scale_io, double* rho_eff_out, Grid<T>* hg_out) {
-    const double target = hash_target_rho(ctx, dim, k, radius, rho_direct);
-    double scale = *scale_io > 0 ? *scale_io : 1.0;
+static int build_hash_tuned(wtp_ctx* ctx, GridTune& t, const Pt<T>* in, Pt<T>* out, int64_t n, int dim, int k,
+                            double rho_direct, double min_cell, Grid<T>* hg_out, double* rho_eff_out) {
+    const double target = hash_target_rho(ctx, dim, k, rho_direct);
+    double scale = 1.0;
     double prev_c = -1;
     int rc;
     if ((rc = ensure(ctx, ctx->occ, 64))) return rc;
@@ -231,7 +232,7 @@ static int build_hash_tuned(wtp_ctx* ctx, const Pt<T>* in, Pt<T>* out, int64_t n
     ctx->box_active = false; // every tuned build starts from the true bounding box
     bool boxed = false;
     for (int round = 0; round < 3; ++round) {
-        if ((rc = build_hash<T>(ctx, in, out, n, dim, k, radius, rho_direct, min_cell, scale))) return rc;
+        if ((rc = build_hash<T>(ctx, in, out, n, dim, k, 0.0, rho_direct, min_cell, scale))) return rc;
         if ((rc = launch_occupancy(ctx, (unsigned long long*)ctx->occ.p))) return rc;
         char* hp = (char*)ctx->host_pinned;
         WTP_HIP(ctx, hipMemcpyAsync(hp, ctx->occ.p, 24, hipMemcpyDeviceToHost, ctx->stream));
@@ -248,7 +249,7 @@ static int build_hash_tuned(wtp_ctx* ctx, const Pt<T>* in, Pt<T>* out, int64_t n
         // the box is stretched by outliers — lay the grid over the bulk and start over, once
         const bool capped = hg.n[0] >= kMaxAxisCells || hg.n[1] >= kMaxAxisCells || hg.n[2] >= kMaxAxisCells ||
                             (double)hg.ncells > 6.0 * (double)n;
-        if (excess > 4.0 && capped && !boxed && radius <= 0) {
+        if (excess > 4.0 && capped && !boxed) {
             if ((rc = find_robust_box<T>(ctx, in, n, dim, hg))) return rc;
             boxed = true;
             scale = 1.0;
@@ -264,24 +265,20 @@ static int build_hash_tuned(wtp_ctx* ctx, const Pt<T>* in, Pt<T>* out, int64_t n
         scale *= f;
         if (scale < 0.02) scale = 0.02;
     }
-    *scale_io = scale;
+    t.scale = scale;
+    t.rho = rho_direct;
     return WTP_OK;
 }
 
 // ---- topology -----------------------------------------------------------------------------------
-// Brick geometry of wtp_ksel.hip from the measured grid: the brick length along x that puts ~224 queries on the 256
-// lanes (four own cells per column; the denser of the box average and the occupancy the points see), and the LDS
-// point area for its halo of 36 cells per column plus five standard deviations.
-static void ksel_geometry(wtp_ctx* ctx, double n, double ncells, int n0, double rho_eff, int* bx_out, int* hcap_out) {
-    double rho_cell = ncells > 0 ? n / ncells : 1.0;
-    if (rho_eff - 1.0 > rho_cell) rho_cell = rho_eff - 1.0;
-    if (rho_cell < 0.05) rho_cell = 0.05;
-    // Bricks of equal length along x: among the splits of the n0 columns, the one with the lowest expected cost per
-    // query — a brick costs one round of the 256 lanes, two when its Q own points (Poisson) exceed them
+// Expected cost per query of the bricks of wtp_ksel.hip over `cols` columns of rho_cell points per cell, for the cheapest
+// split of the columns into bricks of equal length along x (its length in *bx_out): a brick costs one round of the 256
+// lanes, two when its Q own points (Poisson) exceed them
+static double ksel_brick_cost(int cols, double rho_cell, int* bx_out = nullptr) {
     int bx = ksel_max_bx();
     double best = 1e300;
-    for (int nbx = 1; nbx <= n0; ++nbx) {
-        const int b = (n0 + nbx - 1) / nbx;
+    for (int nbx = 1; nbx <= cols; ++nbx) {
+        const int b = (cols + nbx - 1) / nbx;
         if (b > ksel_max_bx()) continue;
         const double q = 4.0 * rho_cell * b;
         const double p2 = 0.5 * std::erfc((256.0 - q) / std::sqrt(2.0 * (q > 1 ? q : 1)));
@@ -292,6 +289,19 @@ static void ksel_geometry(wtp_ctx* ctx, double n, double ncells, int n0, double 
         }
         if (b < 8) break;
     }
+    if (bx_out) *bx_out = bx;
+    return best;
+}
+
+// Brick geometry of wtp_ksel.hip from the measured grid: the brick length along x that puts ~224 queries on the 256
+// lanes (four own cells per column; the denser of the box average and the occupancy the points see), and the LDS
+// point area for its halo of 36 cells per column plus five standard deviations.
+static void ksel_geometry(wtp_ctx* ctx, double n, double ncells, int n0, double rho_eff, int* bx_out, int* hcap_out) {
+    double rho_cell = ncells > 0 ? n / ncells : 1.0;
+    if (rho_eff - 1.0 > rho_cell) rho_cell = rho_eff - 1.0;
+    if (rho_cell < 0.05) rho_cell = 0.05;
+    int bx;
+    ksel_brick_cost(n0, rho_cell, &bx);
     bx = bx < 8 ? (n0 < 8 ? (n0 > 0 ? n0 : 1) : 8) : bx;
     const double halo = 36.0 * (bx + 4) * rho_cell;
     int hc = (int)(halo + 5.0 * std::sqrt(halo)) + 32;
@@ -315,17 +325,7 @@ static double ksel_pick_rho(double n, double ncells, int n0, double rho_cur, dou
         if (rho_cur * f > 1.27) continue;                 // (a run of 173 cells must fit the 256 slots of the hit masks)
         const double edge = std::cbrt(f);                 // cell edge relative to the current one
         const int cols = (int)(((double)n0 - 0.5) / edge) + 1;
-        const double rho_cell = fill_cur * f;
-        double cost_b = 1e300;
-        for (int nbx = 1; nbx <= cols; ++nbx) {
-            const int b = (cols + nbx - 1) / nbx;
-            if (b > ksel_max_bx()) continue;
-            const double q = 4.0 * rho_cell * b;
-            const double p2 = 0.5 * std::erfc((256.0 - q) / std::sqrt(2.0 * (q > 1 ? q : 1)));
-            const double cst = (1.0 + p2 + (q > 512.0 ? 100.0 : 0.0)) / q;
-            cost_b = cst < cost_b ? cst : cost_b;
-            if (b < 8) break;
-        }
+        const double cost_b = ksel_brick_cost(cols, fill_cur * f);
         const double round = 0.63 + 0.37 * f;                       // per-round work: fixed part + scan
         const double handback = 1.0 + 0.20 * (1.0 - f) / 0.1 * 0.1;   // ~2 % more total time per 10 % less occupancy
         const double cost = cost_b * round * handback;
@@ -349,6 +349,60 @@ static double ksel_cap_count(int kq) {
     return (double)kq + (kCapKsel - 22.0) / std::sqrt(22.0) * std::sqrt((double)kq);
 }
 
+// The k-selection layout on the grid just measured (hg, with rho_eff the occupancy its points see): the occupancy whose grid
+// fills the bricks' lanes best — one more measured build when the pick moves t.rho by more than 1 % — and the brick
+// geometry of the final grid, into t.
+template <typename T>
+static int ksel_tune(wtp_ctx* ctx, GridTune& t, const Pt<T>* in, Pt<T>* out, int64_t n, int dim, int k, Grid<T>& hg,
+                     double& rho_eff) {
+    const double pick = ksel_pick_rho((double)n, (double)hg.ncells, hg.n[0], t.rho, rho_eff);
+    int rc;
+    if (std::fabs(pick - t.rho) > 0.01 * t.rho && (rc = build_hash_tuned<T>(ctx, t, in, out, n, dim, k, pick, 0.0, &hg, &rho_eff)))
+        return rc;
+    ksel_geometry(ctx, (double)n, (double)hg.ncells, hg.n[0], rho_eff, &t.bx, &t.hcap);
+    return WTP_OK;
+}
+
+// The grid of a cloud with the tuning cached in t.  When t was measured for this cloud size, dim, kq and layout (the usual
+// case: rebuild_topology! on the same points) it is one build_hash: no occupancy passes, no host synchronisation.  The
+// tuning only affects speed, never the result.  Otherwise the grid is measured (build_hash_tuned, then ksel_tune on the k-selection layout) and stored with its key.
+template <typename T>
+static int build_grid_cached(wtp_ctx* ctx, GridTune& t, const Pt<T>* in, Pt<T>* out, int64_t n, int dim, int kq, bool ksel) {
+    // (loose: a Float64 session's cloud changes size with every swapped head; an exact match would measure again each sweep)
+    const int64_t slack = t.loose ? n / 20 : 0;
+    if (t.valid && t.dim == dim && t.kq == kq && t.ksel == ksel && std::llabs((long long)(n - t.n)) <= slack) {
+        ctx->box_active = false;
+        return build_hash<T>(ctx, in, out, n, dim, kq, 0.0, t.rho, 0.0, t.scale);
+    }
+    t.valid = false;
+    double rho_eff = 0;
+    Grid<T> hg;
+    int rc = build_hash_tuned<T>(ctx, t, in, out, n, dim, kq, ksel ? ksel_rho_for(kq) : 0.0, 0.0, &hg, &rho_eff);
+    if (!rc && ksel) rc = ksel_tune<T>(ctx, t, in, out, n, dim, kq, hg, rho_eff);
+    if (rc) return rc;
+    t.n = n;
+    t.dim = dim;
+    t.kq = kq;
+    t.ksel = ksel;
+    // A clipped box belongs to this very cloud: a topology call never reuses its scale on the full box a hit builds.  (loose:
+    // kept, as a Float64 session has always kept it — measuring again would cost three builds and host reads per sweep.)
+    t.valid = t.loose || !ctx->box_active;
+    return WTP_OK;
+}
+
+// the seven leading fields of a search; the rest stays as the caller has it
+template <typename T>
+static void init_search(SearchArgs<T>& a, const wtp_ctx* ctx, const Pt<T>* snap, const Pt<T>* query, int64_t n, int k,
+                        int include_self) {
+    a.grid = (const Grid<T>*)ctx->grid.p;
+    a.snap = snap;
+    a.query = query;
+    a.cell_start = (const int32_t*)ctx->cell_start.p;
+    a.n = (int32_t)n;
+    a.k = k;
+    a.include_self = include_self;
+}
+
 template <typename T>
 static int knn_dev_t(wtp_ctx* ctx, const T* d_xyz, int64_t n, int dim, int k, int include_self,
                      int32_t* d_idx, T* d_dist) {
@@ -365,58 +419,17 @@ static int knn_dev_t(wtp_ctx* ctx, const T* d_xyz, int64_t n, int dim, int k, in
     int sp = span_begin(ctx, 0);
     if ((rc = load_points<T>(ctx, d_xyz, raw, n, dim))) return rc;
     // neighbours sought per query inside the structure: k others + self
-    // The measured cell scale of the last topology call is reused for a cloud of the same size (the
-    // usual case: rebuild_topology! on the same points); it only affects speed, never the result.
     const int kq = include_self ? k : k + 1;
     // fp32 3-D clouds with k + self <= 24 (the reference's k = 21 among them): the x-slowest layout of wtp_ksel.hip —
     // cells of ~1.2 points, the k nearest inside the 5 x 5 x 5 block around the query's cell
     const bool ksel = sizeof(T) == 4 && dim == 3 && ctx->ksel && !ctx->force_generic && kq <= ksel_kmax() && n >= 4096;
-    const double rho_direct = ksel ? ksel_rho_for(kq) : 0.0;
     ctx->topology_build = true;
-    if (ctx->knn_tune_n == n && ctx->knn_tune_dim == dim && ctx->knn_tune_k == kq && !ctx->knn_tune_boxed &&
-        ctx->knn_tune_ksel == (int)ksel) {
-        ctx->box_active = false;
-        if ((rc = build_hash<T>(ctx, raw, sorted, n, dim, kq, 0.0, ksel ? ctx->knn_tune_rho : 0.0, 0.0, ctx->knn_tune_scale))) {
-            ctx->topology_build = false;
-            return rc;
-        }
-    } else {
-        double scale = 1.0, rho_eff = 0;
-        Grid<T> hg;
-        if ((rc = build_hash_tuned<T>(ctx, raw, sorted, n, dim, kq, 0.0, rho_direct, 0.0, &scale, &rho_eff, &hg))) {
-            ctx->topology_build = false;
-            return rc;
-        }
-        ctx->knn_tune_rho = rho_direct;
-        if (ksel) { // the occupancy whose grid fills the bricks' lanes best: one more measured build, this call only
-            const double pick = ksel_pick_rho((double)n, (double)hg.ncells, hg.n[0], rho_direct, rho_eff);
-            if (std::fabs(pick - rho_direct) > 0.01 * rho_direct) {
-                scale = 1.0;
-                if ((rc = build_hash_tuned<T>(ctx, raw, sorted, n, dim, kq, 0.0, pick, 0.0, &scale, &rho_eff, &hg))) {
-                    ctx->topology_build = false;
-                    return rc;
-                }
-                ctx->knn_tune_rho = pick;
-            }
-        }
-        ctx->knn_tune_n = n;
-        ctx->knn_tune_dim = dim;
-        ctx->knn_tune_k = kq;
-        ctx->knn_tune_scale = scale;
-        ctx->knn_tune_boxed = ctx->box_active; // a clipped box belongs to this very cloud: never reuse it
-        ctx->knn_tune_ksel = (int)ksel;
-        if (ksel) ksel_geometry(ctx, (double)n, (double)hg.ncells, hg.n[0], rho_eff, &ctx->knn_tune_bx, &ctx->knn_tune_hcap);
-    }
+    rc = build_grid_cached<T>(ctx, ctx->knn_tune, raw, sorted, n, dim, kq, ksel);
     ctx->topology_build = false;
+    if (rc) return rc;
     span_end(ctx, sp);
     SearchArgs<T> a{};
-    a.grid = (const Grid<T>*)ctx->grid.p;
-    a.snap = sorted;
-    a.query = sorted;
-    a.cell_start = (const int32_t*)ctx->cell_start.p;
-    a.n = (int32_t)n;
-    a.k = k;
-    a.include_self = include_self;
+    init_search(a, ctx, sorted, sorted, n, k, include_self);
     a.idx_out = d_idx;
     a.dist_out = d_dist;
     a.fb_list = (int32_t*)ctx->fb_list.p;
@@ -429,8 +442,8 @@ static int knn_dev_t(wtp_ctx* ctx, const T* d_xyz, int64_t n, int dim, int k, in
     if ((rc = ensure(ctx, ctx->diag, 128))) return rc;
     a.diag = (unsigned long long*)ctx->diag.p; // (written by -DWTP_DIAG builds only)
     if (ksel) {
-        a.ksel_bx = ctx->knn_tune_bx;
-        a.brick_hcap = ctx->knn_tune_hcap;
+        a.ksel_bx = ctx->knn_tune.bx;
+        a.brick_hcap = ctx->knn_tune.hcap;
         a.cap_count = (float)ksel_cap_count(kq);
     }
     sp = span_begin(ctx, 1);
@@ -447,6 +460,44 @@ static int knn_dev_t(wtp_ctx* ctx, const T* d_xyz, int64_t n, int dim, int k, in
     ctx->relax.have_tree = false; // pts[] reused
     ctx->rad_valid = false;
     return rc;
+}
+
+// fp32 k-nearest candidates of a double4 cloud (knn_dev_f64, relax_f64_ksel_sweep): the cloud moved to its own origin
+// (*org4_out) and rounded to float by to_local(org4, raw32), hashed with the tuning cached in t, relabel(sorted32) run on
+// the sorted float copy, then the kc nearest per query (self included) into cand_idx / cand_dist, on the x-slowest layout
+// of wtp_ksel.hip where that applies (3-D, kc <= 24).  `b` comes with the caller's counter block; `sp`, the caller's
+// hash span, is closed and the search span left open.
+template <typename ToLocal, typename Relabel>
+static int f64_candidates(wtp_ctx* ctx, const double4* pts, int64_t n, int dim, int kc, GridTune& t, SearchArgs<float>& b,
+                          int& sp, const double** org4_out, ToLocal to_local, Relabel relabel) {
+    int rc;
+    if ((rc = ensure(ctx, ctx->f32_pts, 2 * sizeof(float4) * (size_t)n))) return rc;
+    if ((rc = ensure(ctx, ctx->cand_idx, sizeof(int32_t) * (size_t)n * kc))) return rc;
+    if ((rc = ensure(ctx, ctx->cand_dist, sizeof(float) * (size_t)n * kc))) return rc;
+    if ((rc = ensure(ctx, ctx->occ, 64))) return rc;
+    float4* raw32 = (float4*)ctx->f32_pts.p;
+    float4* sorted32 = raw32 + n;
+    double* org4 = (double*)ctx->occ.p + 4; // behind the occupancy counters
+    *org4_out = org4;
+    if ((rc = launch_origin(ctx, pts, n, org4))) return rc;
+    if ((rc = to_local(org4, raw32))) return rc;
+    const bool ksel = dim == 3 && ctx->ksel && kc <= ksel_kmax() && n >= 4096;
+    ctx->topology_build = true; // rows are ordered by (d2, id) explicitly: no canonical-order pass
+    rc = build_grid_cached<float>(ctx, t, raw32, sorted32, n, dim, kc, ksel);
+    ctx->topology_build = false;
+    if (!rc) rc = relabel(sorted32);
+    if (rc) return rc;
+    span_end(ctx, sp);
+    sp = span_begin(ctx, 1);
+    init_search(b, ctx, sorted32, sorted32, n, kc, 1);
+    b.idx_out = (int32_t*)ctx->cand_idx.p;
+    b.dist_out = (float*)ctx->cand_dist.p;
+    if (ksel) {
+        b.ksel_bx = t.bx;
+        b.brick_hcap = t.hcap;
+        b.cap_count = (float)ksel_cap_count(kc);
+    }
+    return launch_topology<float>(ctx, b);
 }
 
 // fp64 clouds, KNNTopology: Float64 is the reference's default type, and the exact wave-per-query
@@ -469,90 +520,30 @@ static int knn_dev_f64(wtp_ctx* ctx, const double* d_xyz, int64_t n, int dim, in
     int rc;
     if ((rc = ensure(ctx, ctx->pts[0], sizeof(double4) * (size_t)n))) return rc;
     if ((rc = ensure(ctx, ctx->pts[1], sizeof(double4) * (size_t)n))) return rc;
-    if ((rc = ensure(ctx, ctx->f32_pts, 2 * sizeof(float4) * (size_t)n))) return rc;
-    if ((rc = ensure(ctx, ctx->cand_idx, sizeof(int32_t) * (size_t)n * kc))) return rc;
-    if ((rc = ensure(ctx, ctx->cand_dist, sizeof(float) * (size_t)n * kc))) return rc;
     if ((rc = ensure(ctx, ctx->fb_list, sizeof(int32_t) * (size_t)n))) return rc;
     if ((rc = ensure(ctx, ctx->fb_count, 64))) return rc;
     ctx->counters_clean = false; // (this call counts in the block; the next sweep clears it itself)
     if ((rc = ensure(ctx, ctx->fb2_list, sizeof(int32_t) * (size_t)n))) return rc;
     if ((rc = ensure(ctx, ctx->fb2_count, 64))) return rc;
-    if ((rc = ensure(ctx, ctx->occ, 64))) return rc;
     double4* raw64 = (double4*)ctx->pts[0].p;
-    float4* raw32 = (float4*)ctx->f32_pts.p;
-    float4* sorted32 = raw32 + n;
-    double* org4 = (double*)ctx->occ.p + 4; // behind the occupancy counters
     int sp = span_begin(ctx, 0);
     if ((rc = load_points<double>(ctx, d_xyz, raw64, n, dim))) return rc;
-    if ((rc = launch_origin(ctx, raw64, n, org4))) return rc;
-    if ((rc = launch_to_local_f32(ctx, raw64, n, org4, raw32))) return rc;
-    double scale = 1.0, rho_eff = 0;
-    Grid<float> hg;
-    // the fp32 candidate search takes the x-slowest layout of wtp_ksel.hip where that applies (3-D, k + self + 2 <= 24)
-    const bool ksel = dim == 3 && ctx->ksel && kc <= ksel_kmax() && n >= 4096;
-    double rho_direct = ksel ? ksel_rho_for(kc) : 0.0;
-    ctx->topology_build = true;
-    // the measured cell scale (and the brick geometry that goes with it) of the last fp64 call is reused for a cloud of the
-    // same size, as in the fp32 calls: it only affects speed, and saves two occupancy passes and a host synchronisation
-    const bool cached = ctx->knn64_tune_n == n && ctx->knn64_tune_dim == dim && ctx->knn64_tune_k == kc &&
-                        ctx->knn64_tune_ksel == (int)ksel;
-    if (cached) {
-        ctx->box_active = false;
-        rc = build_hash<float>(ctx, raw32, sorted32, n, dim, kc, 0.0, ksel ? ctx->knn64_tune_rho : 0.0, 0.0, ctx->knn64_tune_scale);
-    } else {
-        rc = build_hash_tuned<float>(ctx, raw32, sorted32, n, dim, kc, 0.0, rho_direct, 0.0, &scale, &rho_eff, &hg);
-        if (!rc && ksel) {
-            const double pick = ksel_pick_rho((double)n, (double)hg.ncells, hg.n[0], rho_direct, rho_eff);
-            if (std::fabs(pick - rho_direct) > 0.01 * rho_direct) {
-                rho_direct = pick;
-                scale = 1.0;
-                rc = build_hash_tuned<float>(ctx, raw32, sorted32, n, dim, kc, 0.0, rho_direct, 0.0, &scale, &rho_eff, &hg);
-            }
-        }
-        if (!rc && !ctx->box_active) { // (a clipped box belongs to this very cloud: never reused)
-            ctx->knn64_tune_n = n;
-            ctx->knn64_tune_dim = dim;
-            ctx->knn64_tune_k = kc;
-            ctx->knn64_tune_ksel = (int)ksel;
-            ctx->knn64_tune_scale = scale;
-            ctx->knn64_tune_rho = rho_direct;
-            if (ksel) ksel_geometry(ctx, (double)n, (double)hg.ncells, hg.n[0], rho_eff, &ctx->knn64_tune_bx, &ctx->knn64_tune_hcap);
-        } else {
-            ctx->knn64_tune_n = -1;
-        }
-    }
-    ctx->topology_build = false;
-    if (rc) return rc;
-    span_end(ctx, sp);
-    ctx->knn_tune_n = -1; // the cached scale belongs to fp32 calls
+    // k = 21 without self (kc = 24): search and re-ranking in slot order (see refine_f64_slots_kernel)
+    const bool slots = kc == 24;
+    double4* slot64 = (double4*)ctx->pts[1].p;
     SearchArgs<float> a{};
-    a.grid = (const Grid<float>*)ctx->grid.p;
-    a.snap = sorted32;
-    a.query = sorted32;
-    a.cell_start = (const int32_t*)ctx->cell_start.p;
-    a.n = (int32_t)n;
-    a.k = kc;
-    a.include_self = 1;
-    a.idx_out = (int32_t*)ctx->cand_idx.p;
-    a.dist_out = (float*)ctx->cand_dist.p;
     a.fb_list = (int32_t*)ctx->fb_list.p;
     a.fb_count = (int32_t*)ctx->fb_count.p;
     a.fb2_list = (int32_t*)ctx->fb2_list.p;
     a.fb2_count = (int32_t*)ctx->fb2_count.p;
-    if (ksel) {
-        if (ctx->knn64_tune_n != n) // (a clipped box: geometry of this very build)
-            ksel_geometry(ctx, (double)n, (double)hg.ncells, hg.n[0], rho_eff, &ctx->knn64_tune_bx, &ctx->knn64_tune_hcap);
-        a.ksel_bx = ctx->knn64_tune_bx;
-        a.brick_hcap = ctx->knn64_tune_hcap;
-        a.cap_count = (float)ksel_cap_count(kc);
-    }
-    sp = span_begin(ctx, 1);
-    // k = 21 without self (kc = 24): search and re-ranking in slot order (see refine_f64_slots_kernel)
-    const bool slots = kc == 24;
-    double4* slot64 = (double4*)ctx->pts[1].p;
-    if (slots && (rc = launch_relabel_slots(ctx, raw64, sorted32, slot64, n))) return rc;
-    rc = launch_topology<float>(ctx, a);
+    const double* org4 = nullptr;
+    rc = f64_candidates(
+        ctx, raw64, n, dim, kc, ctx->knn64_tune, a, sp, &org4,
+        [&](const double* o, float4* raw32) { return launch_to_local_f32(ctx, raw64, n, o, raw32); },
+        [&](float4* sorted32) { return slots ? launch_relabel_slots(ctx, raw64, sorted32, slot64, n) : WTP_OK; });
     if (rc) return rc;
+    // kept: the next fp32 call measures its cloud afresh, not with a scale measured before this call on a cloud of that size
+    ctx->knn_tune.valid = false;
     if (slots)
         rc = launch_refine_f64_slots(ctx, slot64, a.idx_out, a.dist_out, n, kc, k, include_self, org4, d_idx, d_dist,
                                      (int32_t*)ctx->fb_list.p, (int32_t*)ctx->fb_count.p);
@@ -576,13 +567,7 @@ static int knn_dev_f64(wtp_ctx* ctx, const double* d_xyz, int64_t n, int dim, in
         ctx->topology_build = false;
         if (rc) return rc;
         SearchArgs<double> b{};
-        b.grid = (const Grid<double>*)ctx->grid.p;
-        b.snap = sorted64;
-        b.query = raw64; // list entries are ids: raw64[id] is the query, its w the id
-        b.cell_start = (const int32_t*)ctx->cell_start.p;
-        b.n = (int32_t)n;
-        b.k = k;
-        b.include_self = include_self;
+        init_search(b, ctx, sorted64, raw64, n, k, include_self); // list entries are ids: raw64[id] is the query, its w the id
         b.idx_out = d_idx;
         b.dist_out = d_dist;
         b.fb_list = (int32_t*)ctx->fb_list.p;
@@ -841,11 +826,7 @@ template <typename T> static int radius_count_t(wtp_ctx* ctx, int64_t n, int dim
     if (rc) return rc;
     span_end(ctx, sp);
     SearchArgs<T> a{};
-    a.grid = (const Grid<T>*)ctx->grid.p;
-    a.snap = sorted;
-    a.query = sorted;
-    a.cell_start = (const int32_t*)ctx->cell_start.p;
-    a.n = (int32_t)n;
+    init_search(a, ctx, sorted, sorted, n, 0, 0);
     if ((rc = ensure(ctx, ctx->fb_list, sizeof(int32_t) * (size_t)n))) return rc;
     if ((rc = ensure(ctx, ctx->fb_count, 64))) return rc;
     ctx->counters_clean = false; // (this call counts in the block; the next sweep clears it itself)
@@ -892,11 +873,7 @@ template <typename T> static int radius_count_t(wtp_ctx* ctx, int64_t n, int dim
 
 template <typename T> static int radius_fill_t(wtp_ctx* ctx, const int64_t* d_off, int32_t* d_idx) {
     SearchArgs<T> a{};
-    a.grid = (const Grid<T>*)ctx->grid.p;
-    a.snap = (const Pt<T>*)ctx->pts[1].p;
-    a.query = a.snap;
-    a.cell_start = (const int32_t*)ctx->cell_start.p;
-    a.n = (int32_t)ctx->rad_n;
+    init_search(a, ctx, (const Pt<T>*)ctx->pts[1].p, (const Pt<T>*)ctx->pts[1].p, ctx->rad_n, 0, 0);
     a.fb2_list = (int32_t*)ctx->fb2_list.p;
     a.fb2_count = (int32_t*)ctx->fb2_count.p;
     a.fb_list = (int32_t*)ctx->fb_list.p; // ensured by the count phase
@@ -1267,77 +1244,32 @@ static int relax_f64_ksel_sweep(wtp_ctx* ctx, SearchArgs<double>& a) {
     const int64_t n = r.n;
     const int kc = 24;
     int rc;
-    if ((rc = ensure(ctx, ctx->f32_pts, 2 * sizeof(float4) * (size_t)n))) return rc;
-    if ((rc = ensure(ctx, ctx->cand_idx, sizeof(int32_t) * (size_t)n * kc))) return rc;
-    if ((rc = ensure(ctx, ctx->cand_dist, sizeof(float) * (size_t)n * kc))) return rc;
     if ((rc = ensure(ctx, ctx->f64k_s64, sizeof(double4) * (size_t)n))) return rc;
     if ((rc = ensure(ctx, ctx->f64k_slot, sizeof(int32_t) * (size_t)n))) return rc;
     if ((rc = ensure(ctx, ctx->f64k_lists, sizeof(int32_t) * 2 * (size_t)n))) return rc;
     if ((rc = ensure(ctx, ctx->f64k_cnt, 64))) return rc;
-    if ((rc = ensure(ctx, ctx->occ, 64))) return rc;
     const double4* snap = (const double4*)a.snap; // the sorted snapshot (fresh: the queries are its points)
-    float4* raw32 = (float4*)ctx->f32_pts.p;
-    float4* sorted32 = raw32 + n;
-    double* org4 = (double*)ctx->occ.p + 4; // behind the occupancy counters
+    SearchArgs<float> b{};
+    b.fb_list = (int32_t*)ctx->f64k_lists.p;
+    b.fb_count = (int32_t*)ctx->f64k_cnt.p;
+    b.fb2_list = (int32_t*)ctx->f64k_lists.p + n;
+    b.fb2_count = (int32_t*)ctx->f64k_cnt.p + 4;
+    b.stop = ctx->stop_dev;
+    b.diag = a.diag;
     int sp = span_begin(ctx, 0);
-    if ((rc = launch_origin(ctx, snap, n, org4))) return rc;
-    if ((rc = launch_f64k_local(ctx, snap, n, org4, raw32))) return rc;
+    WTP_HIP(ctx, hipMemsetAsync(ctx->f64k_cnt.p, 0, 64, ctx->stream));
+    b.counters_cleared = 1;
     std::swap(ctx->grid, ctx->grid_b);
     std::swap(ctx->cell_start, ctx->cell_start_b);
     const void* ncells_session = ctx->ncells_dev;
-    const bool box_session = ctx->box_active;
-    ctx->box_active = false; // (a clipped box is in the session's coordinates)
-    ctx->topology_build = true; // rows are ordered explicitly: no canonical-order pass
-    const bool tuned = r.f64k_n > 0 && std::llabs((long long)(n - r.f64k_n)) * 20 <= (long long)n;
-    if (tuned) {
-        rc = build_hash<float>(ctx, raw32, sorted32, n, 3, kc, 0.0, r.f64k_rho, 0.0, r.f64k_scale);
-    } else { // once per session: cell scale and occupancy measured on the float copy (host reads)
-        double scale = 1.0, rho_eff = 0, rho_direct = ksel_rho_for(kc);
-        Grid<float> hg;
-        rc = build_hash_tuned<float>(ctx, raw32, sorted32, n, 3, kc, 0.0, rho_direct, 0.0, &scale, &rho_eff, &hg);
-        if (!rc) {
-            const double pick = ksel_pick_rho((double)n, (double)hg.ncells, hg.n[0], rho_direct, rho_eff);
-            if (std::fabs(pick - rho_direct) > 0.01 * rho_direct) {
-                rho_direct = pick;
-                scale = 1.0;
-                rc = build_hash_tuned<float>(ctx, raw32, sorted32, n, 3, kc, 0.0, rho_direct, 0.0, &scale, &rho_eff, &hg);
-            }
-        }
-        if (!rc) {
-            r.f64k_n = n;
-            r.f64k_scale = scale;
-            r.f64k_rho = rho_direct;
-            ksel_geometry(ctx, (double)n, (double)hg.ncells, hg.n[0], rho_eff, &r.f64k_bx, &r.f64k_hcap);
-        }
-    }
-    ctx->topology_build = false;
-    if (!rc) rc = launch_f64k_relabel(ctx, snap, sorted32, (int32_t*)ctx->f64k_slot.p, (double4*)ctx->f64k_s64.p, n);
-    span_end(ctx, sp);
-    sp = span_begin(ctx, 1);
-    if (!rc) {
-        SearchArgs<float> b{};
-        b.grid = (const Grid<float>*)ctx->grid.p;
-        b.snap = sorted32;
-        b.query = sorted32;
-        b.cell_start = (const int32_t*)ctx->cell_start.p;
-        b.n = (int32_t)n;
-        b.k = kc;
-        b.include_self = 1;
-        b.idx_out = (int32_t*)ctx->cand_idx.p;
-        b.dist_out = (float*)ctx->cand_dist.p;
-        b.fb_list = (int32_t*)ctx->f64k_lists.p;
-        b.fb_count = (int32_t*)ctx->f64k_cnt.p;
-        b.fb2_list = (int32_t*)ctx->f64k_lists.p + n;
-        b.fb2_count = (int32_t*)ctx->f64k_cnt.p + 4;
-        b.stop = ctx->stop_dev;
-        b.diag = a.diag;
-        b.ksel_bx = r.f64k_bx;
-        b.brick_hcap = r.f64k_hcap;
-        b.cap_count = (float)ksel_cap_count(kc);
-        WTP_HIP(ctx, hipMemsetAsync(ctx->f64k_cnt.p, 0, 64, ctx->stream));
-        b.counters_cleared = 1;
-        rc = launch_topology<float>(ctx, b);
-    }
+    const bool box_session = ctx->box_active; // (a clipped box is in the session's coordinates)
+    const double* org4 = nullptr;
+    rc = f64_candidates(
+        ctx, snap, n, 3, kc, r.f64k_tune, b, sp, &org4,
+        [&](const double* o, float4* raw32) { return launch_f64k_local(ctx, snap, n, o, raw32); },
+        [&](float4* sorted32) {
+            return launch_f64k_relabel(ctx, snap, sorted32, (int32_t*)ctx->f64k_slot.p, (double4*)ctx->f64k_s64.p, n);
+        });
     // the session's structures again (the float copy's stay where they are until the next sweep overwrites them)
     std::swap(ctx->grid, ctx->grid_b);
     std::swap(ctx->cell_start, ctx->cell_start_b);
@@ -1353,6 +1285,23 @@ static int relax_f64_ksel_sweep(wtp_ctx* ctx, SearchArgs<double>& a) {
     rc = launch_generic_sweep<double>(ctx, a, false); // the exact path for what the certificate turned down
     span_end(ctx, sp);
     return rc;
+}
+
+// Will the next rebuild keep its grid (no bounding-box pass) for a head of n_fixed_next points?  head_swapped: it reads a
+// replaced fixed head (HashView).  relax_step_t decides by it, relax_prerank guesses by it ahead of the ghost rows.
+static bool grid_reusable(const wtp_ctx* ctx, int64_t n_fixed_next, bool head_swapped) {
+    const RelaxState& r = ctx->relax;
+    const bool head_ok = !head_swapped || (r.shard_grid_reuse && r.grid_fixed > 0 &&
+                                           std::llabs((long long)(n_fixed_next - r.grid_fixed)) * 10 <= (long long)r.grid_fixed + 640);
+    return r.grid_age < kGridReuseMax && !r.moved_by_hand && head_ok && !ctx->box_active;
+}
+
+// The brick geometry of the round-2 sweep (and which queries its bricks hand to the exact path, whose sums round
+// differently) was measured on the cloud of the first rebuild: a head that changes the cloud by more than 5 % has it
+// measured again, so that a resident session keeps equalling a fresh one bit for bit.
+static bool head_remeasures(const RelaxState& r, int64_t n_fixed_new) {
+    const int64_t n_new = r.n - r.n_fixed + n_fixed_new;
+    return r.cs2_bx > 0 && std::llabs((long long)(n_fixed_new - r.tuned_fixed)) * 20 > (long long)n_new;
 }
 
 template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_step_stats* d_slot) {
@@ -1386,7 +1335,7 @@ template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_ste
         const bool ksel_ok = sizeof(T) == 4 && r.dim == 3 && ctx->ksel && !ctx->force_generic && r.k >= 2 &&
                              r.k <= ksel_kmax() && r.n >= 4096;
         r.ksel_sweep = !r.cs_sweep && ksel_ok;
-        if (r.ksel_sweep) rho_cs = r.grid_tuned && r.ksel_rho > 0 ? r.ksel_rho : ksel_rho_for(r.k);
+        if (r.ksel_sweep) rho_cs = r.tune.valid && r.tune.bx > 0 ? r.tune.rho : ksel_rho_for(r.k);
         if (r.spacing_typ <= 0) { // once per session: the spacing a typical point asks for
             r.spacing_typ = r.spacing_const;
             if (r.spacing_kind != WTP_SPACING_CONSTANT) {
@@ -1407,12 +1356,12 @@ template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_ste
         const double cell_f = (cs2 && r.spacing_kind == WTP_SPACING_CONSTANT) ? 1.01 : 1.1;
         double min_cell = r.cs_sweep ? cell_f * r.force.u0 * (r.spacing_typ < r.spacing_max ? r.spacing_typ : r.spacing_max)
                                      : 0.0;
-        if (!r.grid_tuned) { // once per session: measured cell edge, LDS point area sized from the real grid
+        const Pt<T>* in = (const Pt<T>*)ctx->pts[r.bufP].p;
+        Pt<T>* out = (Pt<T>*)ctx->pts[t].p;
+        if (!r.tune.valid) { // once per session: measured cell edge, LDS point area sized from the real grid
             double rho_eff = 0;
             Grid<T> hg;
-            rc = build_hash_tuned<T>(ctx, (const Pt<T>*)ctx->pts[r.bufP].p, (Pt<T>*)ctx->pts[t].p, r.n, r.dim, r.k, 0.0,
-                                     rho_cs, min_cell, &r.cell_scale, &rho_eff, &hg);
-            if (rc) return rc;
+            if ((rc = build_hash_tuned<T>(ctx, r.tune, in, out, r.n, r.dim, r.k, rho_cs, min_cell, &hg, &rho_eff))) return rc;
             // A spacing far coarser than the cloud (the reference's own tests repel 46 786 face centres 0.22 apart
             // with a spacing of 3): cells that cover the law's support then hold hundreds of points, every support
             // ball holds more than k of them and each query would go to the exact path one by one.  Such a session
@@ -1426,10 +1375,7 @@ template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_ste
                 r.ksel_sweep = ksel_ok;
                 rho_cs = r.ksel_sweep ? ksel_rho_for(r.k) : 0.0;
                 min_cell = 0.0;
-                r.cell_scale = 1.0;
-                rc = build_hash_tuned<T>(ctx, (const Pt<T>*)ctx->pts[r.bufP].p, (Pt<T>*)ctx->pts[t].p, r.n, r.dim, r.k, 0.0,
-                                         rho_cs, min_cell, &r.cell_scale, &rho_eff, &hg);
-                if (rc) return rc;
+                if ((rc = build_hash_tuned<T>(ctx, r.tune, in, out, r.n, r.dim, r.k, rho_cs, min_cell, &hg, &rho_eff))) return rc;
             }
             r.cs2_bx = 0;
             if (r.cs_sweep && cs2) {
@@ -1442,18 +1388,10 @@ template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_ste
                 r.brick_hcap = hc < 640 ? 640 : (hc > 2560 ? 2560 : hc);
             }
             if (r.ksel_sweep) {
-                const double pick = ksel_pick_rho((double)r.n, (double)hg.ncells, hg.n[0], rho_cs, rho_eff);
-                if (std::fabs(pick - rho_cs) > 0.01 * rho_cs) {
-                    rho_cs = pick;
-                    r.cell_scale = 1.0;
-                    rc = build_hash_tuned<T>(ctx, (const Pt<T>*)ctx->pts[r.bufP].p, (Pt<T>*)ctx->pts[t].p, r.n, r.dim, r.k, 0.0,
-                                             rho_cs, min_cell, &r.cell_scale, &rho_eff, &hg);
-                    if (rc) return rc;
-                }
-                r.ksel_rho = rho_cs;
-                ksel_geometry(ctx, (double)r.n, (double)hg.ncells, hg.n[0], rho_eff, &r.ksel_bx, &r.ksel_hcap);
+                if ((rc = ksel_tune<T>(ctx, r.tune, in, out, r.n, r.dim, r.k, hg, rho_eff))) return rc;
+                rho_cs = r.tune.rho;
             }
-            r.grid_tuned = true;
+            r.tune.valid = true;
             r.tuned_fixed = r.n_fixed;
             r.grid_fixed = r.n_fixed;
             r.grid_age = 0;
@@ -1462,16 +1400,12 @@ template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_ste
             // (and always after a point was placed by hand, a fixed head was swapped, or with a clipped box).
             // A block session swaps its ghost head every iteration; the layer keeps its place and, nearly, its size, so the
             // box of the last full pass still fits (what sticks out is clamped into edge cells: exact, as for a moved point).
-            const bool head_ok = !ctx->hash_view.active ||
-                                 (r.shard_grid_reuse && r.grid_fixed > 0 &&
-                                  std::llabs((long long)(r.n_fixed - r.grid_fixed)) * 10 <= (long long)r.grid_fixed + 640);
-            const bool reuse = r.grid_age < kGridReuseMax && !r.moved_by_hand && head_ok && !ctx->box_active;
+            const bool reuse = grid_reusable(ctx, r.n_fixed, ctx->hash_view.active);
             ctx->reuse_grid = reuse;
             r.grid_age = reuse ? r.grid_age + 1 : 0;
             if (!reuse) r.grid_fixed = r.n_fixed;
             ctx->topology_build = f64k_ok; // (no canonical-order pass: 0.37 ms per 10 M Float64 points)
-            rc = build_hash<T>(ctx, (const Pt<T>*)ctx->pts[r.bufP].p, (Pt<T>*)ctx->pts[t].p, r.n, r.dim, r.k, 0.0, rho_cs,
-                               min_cell, r.cell_scale);
+            rc = build_hash<T>(ctx, in, out, r.n, r.dim, r.k, 0.0, rho_cs, min_cell, r.tune.scale);
             ctx->topology_build = false;
             ctx->reuse_grid = false;
         }
@@ -1502,13 +1436,7 @@ template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_ste
     const int o = pick_free(r, r.bufS, r.bufP);
     if ((rc = ensure(ctx, ctx->pts[o], sizeof(Pt<T>) * (size_t)(r.n + r.shard_extra)))) return rc;
     SearchArgs<T> a{};
-    a.grid = (const Grid<T>*)ctx->grid.p;
-    a.snap = (const Pt<T>*)ctx->pts[r.bufS].p;
-    a.query = (const Pt<T>*)ctx->pts[r.bufP].p;
-    a.cell_start = (const int32_t*)ctx->cell_start.p;
-    a.n = (int32_t)r.n;
-    a.k = r.k;
-    a.include_self = 1;
+    init_search(a, ctx, (const Pt<T>*)ctx->pts[r.bufS].p, (const Pt<T>*)ctx->pts[r.bufP].p, r.n, r.k, 1);
     a.out = (Pt<T>*)ctx->pts[o].p;
     a.forces = (T*)ctx->forces.p;
     a.nn_dist = (T*)ctx->nn_dist.p;
@@ -1550,10 +1478,10 @@ template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_ste
     }
     if ((rc = ensure(ctx, ctx->diag, 128))) return rc;
     a.diag = (unsigned long long*)ctx->diag.p;
-    a.brick_hcap = r.cs_sweep ? r.brick_hcap : (r.ksel_sweep ? r.ksel_hcap : 0);
+    a.brick_hcap = r.cs_sweep ? r.brick_hcap : (r.ksel_sweep ? r.tune.hcap : 0);
     a.cs2_bx = r.cs_sweep ? r.cs2_bx : 0;
     a.cs2_chunked = (r.spacing_kind != WTP_SPACING_CONSTANT || r.cs2_rho > 1.6) ? 1 : 0;
-    a.ksel_bx = r.ksel_sweep ? r.ksel_bx : 0;
+    a.ksel_bx = r.ksel_sweep ? r.tune.bx : 0;
     if (r.ksel_sweep) a.cap_count = (float)ksel_cap_count(r.k);
     a.tnn_frac = (T)kTnnFrac;
     a.cover_axis = r.cover_axis;
@@ -1601,25 +1529,23 @@ static int relax_step_any(wtp_ctx* ctx, int rebuild, wtp_step_stats* d_slot) {
 int wtp::relax_step_enqueue(wtp_ctx* ctx, int rebuild, wtp_step_stats* d_slot) { return relax_step_any(ctx, rebuild, d_slot); }
 
 // The block driver knows, before the ghost rows of an iteration have arrived, how many there will be.  When the rebuild that
-// follows is going to keep its grid (the same rule as in relax_step_t), the snapshot's own entries are ranked into the
+// follows is going to keep its grid (grid_reusable, as in relax_step_t), the snapshot's own entries are ranked into the
 // cells right away, on the context's stream, while the rows travel on another; build_hash then ranks the appended head
 // only.  A wrong guess costs one wasted pass, never a wrong result (build_hash checks what it finds).
 int wtp::relax_prerank(wtp_ctx* ctx, int64_t n_fixed_new) {
     RelaxState& r = ctx->relax;
     ctx->prerank.valid = false;
-    if (!r.active || !r.grid_tuned || !r.have_tree || r.pending.active || r.moved_by_hand || ctx->box_active) return WTP_OK;
-    if (r.grid_age >= kGridReuseMax || !r.shard_grid_reuse || r.grid_fixed <= 0) return WTP_OK;
-    if (std::llabs((long long)(n_fixed_new - r.grid_fixed)) * 10 > (long long)r.grid_fixed + 640) return WTP_OK;
+    if (!r.active || !r.tune.valid || !r.have_tree || r.pending.active) return WTP_OK;
+    if (!grid_reusable(ctx, n_fixed_new, true) || head_remeasures(r, n_fixed_new)) return WTP_OK;
     const int64_t n_new = r.n - r.n_fixed + n_fixed_new;
-    if (r.cs2_bx > 0 && std::llabs((long long)(n_fixed_new - r.tuned_fixed)) * 20 > (long long)n_new) return WTP_OK;
     const size_t ptsz = r.dtype == WTP_F32 ? sizeof(float4) : sizeof(double4);
     if (ctx->pts[r.bufP].cap < ptsz * (size_t)(r.n + n_fixed_new)) return WTP_OK; // (the head would be rewritten, not appended)
     const int k = (int64_t)r.k_req < n_new ? r.k_req : (int)n_new;
     if (r.dtype == WTP_F32)
         return prerank_old_snapshot<float>(ctx, (const Pt<float>*)ctx->pts[r.bufP].p, r.n, (int32_t)r.n_fixed, n_new, r.n + n_fixed_new,
-                                           k, r.last_rho_cs, r.cell_scale);
+                                           k, r.last_rho_cs, r.tune.scale);
     return prerank_old_snapshot<double>(ctx, (const Pt<double>*)ctx->pts[r.bufP].p, r.n, (int32_t)r.n_fixed, n_new, r.n + n_fixed_new,
-                                        k, r.last_rho_cs, r.cell_scale);
+                                        k, r.last_rho_cs, r.tune.scale);
 }
 
 // The movable set of a session is replaced as a whole (block decomposition: points migrated in and out).  The caller
@@ -2018,11 +1944,7 @@ static int relax_query_knn_t(wtp_ctx* ctx, const void* xyz, int64_t nq, int k, i
     if (dist_out && (rc = ensure(ctx, ctx->dist_out, sizeof(T) * (size_t)nq * k))) return rc;
     WTP_HIP(ctx, hipMemcpyAsync(ctx->scratch.p, xyz, sizeof(T) * (size_t)nq * r.dim, hipMemcpyHostToDevice, ctx->stream));
     SearchArgs<T> a{};
-    a.grid = (const Grid<T>*)ctx->grid.p;
-    a.snap = (const Pt<T>*)ctx->pts[r.bufS].p;
-    a.cell_start = (const int32_t*)ctx->cell_start.p;
-    a.n = (int32_t)nq;
-    a.k = k;
+    init_search(a, ctx, (const Pt<T>*)ctx->pts[r.bufS].p, nullptr, nq, k, 0);
     a.idx_out = (int32_t*)ctx->idx_out.p;
     a.dist_out = dist_out ? (T*)ctx->dist_out.p : nullptr;
     int sp = span_begin(ctx, 2);
@@ -2332,13 +2254,7 @@ int wtp::relax_set_fixed_dev_impl(wtp_ctx* ctx, const void* d_fixed4, int64_t n_
         if (rc) return rc;
         r.bufP = t;
     }
-    // The brick geometry of the round-2 sweep (and which queries its bricks hand to the exact path, whose sums
-    // round differently) was measured on the cloud of the first rebuild: a head that changes the cloud by more
-    // than 5 % has it measured again, so that a resident session keeps equalling a fresh one bit for bit.
-    if (r.cs2_bx > 0 && std::llabs((long long)(n_fixed_new - r.tuned_fixed)) * 20 > (long long)n_new) {
-        r.grid_tuned = false;
-        r.cell_scale = 1.0;
-    }
+    if (head_remeasures(r, n_fixed_new)) r.tune.valid = false; // the next rebuild measures the grid again
     r.n = n_new;
     r.n_fixed = n_fixed_new;
     r.k = (int64_t)r.k_req < n_new ? r.k_req : (int)n_new;

@@ -194,6 +194,20 @@ struct Prerank {
     const void *cnt = nullptr, *cr = nullptr, *dirty = nullptr;
 };
 
+// Measured tuning of a grid (build_hash_tuned, ksel_tune in wtp_api.hip): the key it was measured for and what was measured.
+// The topology calls keep one per context; a relax session keeps one for its own grid (only `valid` of the key: measured
+// once per session) and one for the float copy of its Float64 sweeps.
+struct GridTune {
+    bool loose = false;      // Float64 sweeps: a cloud within 5 % of n fits, and a scale measured on a clipped box is kept (build_grid_cached)
+    bool valid = false;
+    int64_t n = 0;
+    int dim = 0, kq = 0;     // kq: neighbours sought per query (self included)
+    bool ksel = false;       // the grid was built for the k-selection kernels of wtp_ksel.hip
+    double scale = 1.0;      // cell scale: < 1 when the occupied cells hold more than the box average
+    double rho = 0;          // occupancy the grid was built with (the k-selection pick, ksel_pick_rho)
+    int bx = 0, hcap = 0;    // wtp_ksel.hip: brick length along x and LDS point area (0: not measured)
+};
+
 struct RelaxState {
     bool active = false;
     int64_t n = 0, n_fixed = 0;
@@ -208,17 +222,14 @@ struct RelaxState {
     bool have_point_data = false;
     double spacing_max = 0;  // largest spacing value (host-side max of the per-point array)
     int brick_hcap = 0;      // LDS point capacity of the sweep's brick kernel (0 = not chosen yet)
-    bool grid_tuned = false; // cell_scale / spacing_typ measured on the first rebuild
+    GridTune tune;           // cell scale (and, for the k-selection sweep, occupancy and brick geometry) measured on the first rebuild
     int grid_age = 0;             // rebuilds since the grid (bounding box, cell edge) was last computed
     int sweeps_since_rebuild = 0; // every sweep moves a point by at most its spacing (src/repel.jl:286-289)
     bool moved_by_hand = false;   // wtp_relax_set since the last rebuild: that bound is gone
-    double cell_scale = 1.0; // < 1: cells shrunk because the occupied ones hold more than the box average
     double spacing_typ = 0;  // mean spacing over the snapshot (floor of the compact-support cell edge)
     bool cs_sweep = false;   // compact-support sweep in use (ClippedSpacingForce)
     bool cs_disabled = false; // measured on the first rebuild: support cells would be over-full, use the k-selection sweep
     bool ksel_sweep = false; // k-selection sweep on the x-slowest layout (wtp_ksel.hip)
-    int ksel_bx = 0, ksel_hcap = 0; // its brick length along x and LDS point area, measured with the grid
-    double ksel_rho = 0;     // the occupancy picked for this cloud (ksel_pick_rho)
     double cs2_rho = 0;      // points per cell the sweep's bricks were sized for (cs2_tune)
     int cs2_bx = 0;          // > 0: the round-2 compact-support sweep (wtp_cs2.hip) with bricks of this many cells along x
     int64_t tuned_fixed = 0; // fixed points the grid / brick geometry was measured with (a swapped head re-measures when it differs by > 5 % of n)
@@ -229,10 +240,7 @@ struct RelaxState {
     int swap_target = -1;    // relax_swap_begin .. relax_swap_commit (wtp_block.hip: migration)
     bool shard_grid_reuse = false; // block sessions: the grid is kept across a swapped ghost head (points outside it pile into edge cells, which every search treats as unbounded outward)
     int64_t grid_fixed = -1;       // fixed points the current grid's bounding box was computed with
-    // fp64 sweeps through fp32 candidates: what the float copy's grid was measured with (cloud size, cell scale, occupancy, brick geometry)
-    int64_t f64k_n = 0;
-    double f64k_scale = 1.0, f64k_rho = 0.0;
-    int f64k_bx = 0, f64k_hcap = 0;
+    GridTune f64k_tune{/*loose=*/true}; // fp64 sweeps through fp32 candidates: the float copy's grid
     double last_rho_cs = 0.0;      // occupancy argument of the session's last hash build (relax_prerank sizes its scratch alike)
     bool wall_active = false; // octree method: _constrain_octree runs after every sweep (wtp_relax_set_wall)
     double wall_offset = 0;   // inward nudge of a projected boundary point (src/repel.jl:143)
@@ -267,16 +275,9 @@ struct wtp_ctx {
     // (kernel, dynamic LDS bytes) -> blocks per CU, per CONTEXT: the dynamic-LDS attribute and the occupancy are
     // properties of a kernel on one device, and several contexts (devices) may live in one process
     std::map<std::pair<const void*, size_t>, int> launch_cache;
-    // the same cache for the fp32 candidate search of fp64 topology calls (knn_dev_f64)
-    int64_t knn64_tune_n = -1;
-    int knn64_tune_dim = 0, knn64_tune_k = 0, knn64_tune_ksel = -1, knn64_tune_bx = 0, knn64_tune_hcap = 0;
-    double knn64_tune_scale = 1.0, knn64_tune_rho = 0;
-    double knn_tune_rho = 0;   // occupancy the wtp_ksel.hip grid of that cloud was built with
-    int knn_tune_ksel = -1, knn_tune_bx = 0, knn_tune_hcap = 0; // wtp_ksel.hip layout in use for that cloud, its brick geometry
-    int64_t knn_tune_n = -1;   // topology calls: cloud size / dim / k the cached cell scale was measured for
-    int knn_tune_dim = 0, knn_tune_k = 0;
-    double knn_tune_scale = 1.0;
-    bool knn_tune_boxed = false;
+    // topology calls: the grid tuning of the last call, reused for a cloud of the same size (knn_dev_t; knn_dev_f64 for the
+    // fp32 candidate search of fp64 calls)
+    wtp::GridTune knn_tune, knn64_tune;
     // pooled device buffers
     wtp::DevBuf pts[3];        // Pt arrays
     wtp::DevBuf raw_in;        // AoS staging of host input
