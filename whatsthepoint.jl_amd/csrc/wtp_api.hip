@@ -1238,8 +1238,9 @@ static int cs2_tune(wtp_ctx* ctx, RelaxState& r, const Grid<float>& hg, double r
 
 // Float64 sweep of a k-nearest law on a fresh snapshot (wtp_sweep64.hip): candidates from the fp32 k-selection kernels on a
 // float copy of the snapshot with its own grid — the session's grid and cell table are parked meanwhile and come back
-// untouched for the exact path —, exact re-ranking + force sum + step per query, the wave kernel for what is not certified.
-static int relax_f64_ksel_sweep(wtp_ctx* ctx, SearchArgs<double>& a) {
+// untouched for the exact path —, exact re-ranking + force sum + step per query; what is not certified is left in a.fb_list.
+// *sp: the hash span it opens is closed and the search span left open.
+static int relax_f64_ksel_sweep(wtp_ctx* ctx, SearchArgs<double>& a, int* sp) {
     RelaxState& r = ctx->relax;
     const int64_t n = r.n;
     const int kc = 24;
@@ -1256,7 +1257,7 @@ static int relax_f64_ksel_sweep(wtp_ctx* ctx, SearchArgs<double>& a) {
     b.fb2_count = (int32_t*)ctx->f64k_cnt.p + 4;
     b.stop = ctx->stop_dev;
     b.diag = a.diag;
-    int sp = span_begin(ctx, 0);
+    *sp = span_begin(ctx, 0);
     WTP_HIP(ctx, hipMemsetAsync(ctx->f64k_cnt.p, 0, 64, ctx->stream));
     b.counters_cleared = 1;
     std::swap(ctx->grid, ctx->grid_b);
@@ -1265,7 +1266,7 @@ static int relax_f64_ksel_sweep(wtp_ctx* ctx, SearchArgs<double>& a) {
     const bool box_session = ctx->box_active; // (a clipped box is in the session's coordinates)
     const double* org4 = nullptr;
     rc = f64_candidates(
-        ctx, snap, n, 3, kc, r.f64k_tune, b, sp, &org4,
+        ctx, snap, n, 3, kc, r.f64k_tune, b, *sp, &org4,
         [&](const double* o, float4* raw32) { return launch_f64k_local(ctx, snap, n, o, raw32); },
         [&](float4* sorted32) {
             return launch_f64k_relabel(ctx, snap, sorted32, (int32_t*)ctx->f64k_slot.p, (double4*)ctx->f64k_s64.p, n);
@@ -1276,15 +1277,8 @@ static int relax_f64_ksel_sweep(wtp_ctx* ctx, SearchArgs<double>& a) {
     ctx->ncells_dev = ncells_session;
     ctx->box_active = box_session;
     if (rc) return rc;
-    ctx->n_sweep_launches += 1;
-    rc = launch_refine_sweep_f64(ctx, a, (const double4*)ctx->f64k_s64.p, (const int32_t*)ctx->f64k_slot.p,
-                                 (const int32_t*)ctx->cand_idx.p, (const float*)ctx->cand_dist.p, org4);
-    span_end(ctx, sp);
-    if (rc) return rc;
-    sp = span_begin(ctx, 2);
-    rc = launch_generic_sweep<double>(ctx, a, false); // the exact path for what the certificate turned down
-    span_end(ctx, sp);
-    return rc;
+    return launch_refine_sweep_f64(ctx, a, (const double4*)ctx->f64k_s64.p, (const int32_t*)ctx->f64k_slot.p,
+                                   (const int32_t*)ctx->cand_idx.p, (const float*)ctx->cand_dist.p, org4);
 }
 
 // Will the next rebuild keep its grid (no bounding-box pass) for a head of n_fixed_next points?  head_swapped: it reads a
@@ -1304,38 +1298,147 @@ static bool head_remeasures(const RelaxState& r, int64_t n_fixed_new) {
     return r.cs2_bx > 0 && std::llabs((long long)(n_fixed_new - r.tuned_fixed)) * 20 > (long long)n_new;
 }
 
+// The route of a session's sweeps, from the session and the switches; relax_step_t decides at every rebuild (a swapped head
+// changes n and k), and once more with cs_disabled set when the first rebuild finds the support cells over-full.
+template <typename T> static SweepRoute sweep_route(const wtp_ctx* ctx, const RelaxState& r) {
+    if (ctx->force_generic) return SweepRoute::Exact;
+    // ClippedSpacingForce (the reference default): cells only have to cover the law's support u0*s and the nearest-neighbour
+    // radius, so they can be smaller than the k-NN cells — unless WTP_FULL_SELECT=1 asks for the explicit k-selection on
+    // every query (both give the same output)
+    const bool clipped = r.force.kind == WTP_FORCE_CLIPPED_SPACING;
+    if (clipped && r.k >= 2 && r.k < 32 && !ctx->full_select && !r.cs_disabled) {
+        if (sizeof(T) == 8) return ctx->ball64 ? SweepRoute::Cs64 : SweepRoute::Cs64Wave;
+        return r.dim == 3 ? SweepRoute::Cs2 : SweepRoute::Cs;
+    }
+    if (sizeof(T) == 8) {
+        // Float64, a k-nearest law, 3-D: candidates from the fp32 k-selection kernels.  (ClippedSpacingForce keeps its
+        // compact-support kernels: measured through this route on the graded 10 M-point cloud, 39 ms per iteration against
+        // 20 — the k-selection grid hands a quarter of a graded cloud's queries back)
+        const bool f64k = r.dim == 3 && ctx->ksel && ctx->f64_ksel && !clipped && r.k >= 2 && r.k <= 22 && r.n >= 4096;
+        return f64k ? SweepRoute::F64Ksel : SweepRoute::Exact;
+    }
+    if (r.k >= 32) return SweepRoute::Exact; // beyond the brick kernels' lists
+    // every other law, WTP_FULL_SELECT=1 and over-full support cells: the explicit k-selection — on the x-slowest layout of
+    // wtp_ksel.hip where that applies
+    const bool ksel = r.dim == 3 && ctx->ksel && r.k >= 2 && r.k <= ksel_kmax() && r.n >= 4096;
+    return ksel ? SweepRoute::Ksel : SweepRoute::Select;
+}
+
+static bool route_cs(SweepRoute s) {
+    return s == SweepRoute::Cs || s == SweepRoute::Cs2 || s == SweepRoute::Cs64 || s == SweepRoute::Cs64Wave;
+}
+// the ball kernel takes the route's supports wider than a cell and every query of a stale snapshot
+static bool route_ball(SweepRoute s) { return s == SweepRoute::Cs || s == SweepRoute::Cs2 || s == SweepRoute::Cs64; }
+
+// The session's hash builds for its route: occupancy (points per cell, 0: the k-NN default) and smallest cell edge
+struct RouteGrid { double rho, min_cell; };
+static RouteGrid route_grid(const wtp_ctx* ctx, const RelaxState& r) {
+    if (r.route == SweepRoute::Ksel) return {r.tune.valid && r.tune.bx > 0 ? r.tune.rho : ksel_rho_for(r.k), 0.0};
+    if (!route_cs(r.route)) return {0.0, 0.0};
+    // round-2 sweep (wtp_cs2.hip): the nearest neighbour comes from the support or from a per-wave follow-up, so the cells
+    // only cover the support: rho ~ 1.  The other compact-support kernels: rho ~ 3.5 instead of ~8, 2.3x fewer candidates.
+    const bool cs2 = r.route == SweepRoute::Cs2;
+    // The cells cover the law's support u0*s.  With a variable spacing the cell edge follows the spacing a typical point
+    // asks for (the mean over points, which the dense regions dominate), not the largest one: the few points whose support
+    // is wider than that are handed to the exact path, instead of everybody's cells being 64x over-full.
+    // (constant spacing: c - margin = c (1 - 1/256) must reach u0 s, 1.01 does; variable: 10 % headroom over the mean)
+    const double cell_f = (cs2 && r.spacing_kind == WTP_SPACING_CONSTANT) ? 1.01 : 1.1;
+    return {cs2 ? kRhoCs2 : 3.5 * (ctx->rho / 9.0),
+            cell_f * r.force.u0 * (r.spacing_typ < r.spacing_max ? r.spacing_typ : r.spacing_max)};
+}
+
+// What this step's sweep runs: the session's route on a fresh snapshot; on a stale one the ball kernel for every query where
+// the route has one, else the exact path.
+static SweepRoute step_route(const RelaxState& r, bool fresh) {
+    if (!fresh) return route_ball(r.route) ? SweepRoute::Ball : SweepRoute::Exact;
+    // a grid measured for another route (a head swap took n past 4096, or k below 32) left this one without its brick
+    // geometry: the explicit k-selection on 4 x 4 x 4 bricks, in Float64 the exact path
+    const bool measured = r.route == SweepRoute::Ksel ? r.tune.bx > 0 : !route_cs(r.route) || r.brick_hcap > 0;
+    if (measured) return r.route;
+    return r.route == SweepRoute::Cs64 || r.route == SweepRoute::Cs64Wave ? SweepRoute::Exact : SweepRoute::Select;
+}
+
+static int ball_pass(wtp_ctx* ctx, SearchArgs<float>& a) { return launch_cs_ball(ctx, a, a.ball_list, a.ball_count); }
+static int ball_pass(wtp_ctx* ctx, SearchArgs<double>& a) { return launch_cs_ball64(ctx, a, a.ball_list, a.ball_count); }
+
+// One relax sweep along the step's route (ball: with the ball kernel for supports wider than a cell): span 1 around the
+// route's own kernels, span 2 around the exact path for what they hand back.  The caller cleared the counter block; partial
+// slots need no clearing: the reduction reads only the slots this step's launches write (a.used_*).
+template <typename T> static int launch_sweep(wtp_ctx* ctx, SearchArgs<T>& a, SweepRoute route, bool ball) {
+    constexpr bool f32 = sizeof(T) == 4;
+    ctx->n_sweep_launches += 1;
+    int rc = WTP_OK, sp = -1;
+    switch (route) {
+    case SweepRoute::Exact:
+    case SweepRoute::Ball:
+        sp = span_begin(ctx, 1);
+        if (route == SweepRoute::Ball) {
+            // A stale snapshot (rebuild_every > 1, src/repel.jl:245) and the default law: the query has moved away from its
+            // snapshot entry, so the brick kernels (queries = the staged points) do not apply, but the ball kernel's argument
+            // does — the support ball around the point where it is NOW, searched in the block that provably holds it, at
+            // most k points in it — with eight lanes per query instead of the wave kernel's 64 (10.5 -> see DESIGN.md).
+            rc = launch_cs_all_slots(ctx, a.fb_list, a.n, a.fb_count);
+            if (!rc) rc = ball_pass(ctx, a);
+        }
+        if (!rc) rc = launch_generic_sweep<T>(ctx, a, route == SweepRoute::Exact);
+        span_end(ctx, sp);
+        return rc;
+    case SweepRoute::F64Ksel:
+        if constexpr (!f32) rc = relax_f64_ksel_sweep(ctx, a, &sp);
+        break;
+    case SweepRoute::Ksel:
+        sp = span_begin(ctx, 1);
+        if constexpr (f32) rc = launch_ksel_sweep(ctx, a);
+        a.fb_r0 = 3; // its hand-backs failed at the 5^3 cells around the query
+        break;
+    case SweepRoute::Select:
+    case SweepRoute::Cs:
+    case SweepRoute::Cs2:
+        sp = span_begin(ctx, 1);
+        if constexpr (f32) {
+            if (route == SweepRoute::Cs2 && ball) {
+                // variable spacing: bricks that would hand every point back are found first and passed over (wtp_cs2.hip)
+                const int dead_cap = (int)(ctx->cell_start.cap / sizeof(int32_t) / 4 + 4096);
+                rc = ensure(ctx, ctx->brick_dead, (size_t)dead_cap);
+                if (!rc) rc = launch_cs2_dead(ctx, a, (uint8_t*)ctx->brick_dead.p, dead_cap);
+                a.brick_dead = (const uint8_t*)ctx->brick_dead.p;
+                a.brick_dead_cap = dead_cap;
+            }
+            if (!rc) rc = route == SweepRoute::Cs2 ? launch_cs2(ctx, a) : launch_brick_sweep(ctx, a, route == SweepRoute::Cs);
+        }
+        break;
+    case SweepRoute::Cs64:
+    case SweepRoute::Cs64Wave:
+        sp = span_begin(ctx, 1);
+        if constexpr (!f32) {
+            rc = launch_brick_cs<double>(ctx, a);
+            if (!rc && ball) rc = ball_pass(ctx, a); // supports wider than a cell (wtp_ball64.hip), before the exact path
+        }
+        break;
+    }
+    span_end(ctx, sp);
+    if (rc) return rc;
+    sp = span_begin(ctx, 2);
+    if constexpr (f32) {
+        if (route == SweepRoute::Cs2) rc = launch_cs2_followup(ctx, a); // nearest neighbour of the queries the bricks left open
+        if (!rc && ball) rc = ball_pass(ctx, a); // hand-backs whose support outgrew their cell, ball by ball (wtp_cs2.hip)
+    }
+    if (!rc) rc = launch_generic_sweep<T>(ctx, a, false);
+    span_end(ctx, sp);
+    return rc;
+}
+
 template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_step_stats* d_slot) {
     RelaxState& r = ctx->relax;
     int rc;
     if (!r.have_tree || r.pending.active) rebuild = 1; // the reference builds its first tree in the setup (src/repel.jl:218)
-    // Float64, a k-nearest law, 3-D: on a fresh snapshot the sweep takes its candidates from the fp32 k-selection kernels
-    // (wtp_sweep64.hip).  Every sum on that route and on the exact path behind it is ordered by (d2, index) explicitly, so
-    // the snapshot's cells need no canonical order.
-    const bool f64k_ok = sizeof(T) == 8 && r.dim == 3 && ctx->ksel && ctx->f64_ksel && !ctx->force_generic &&
-                         r.force.kind != WTP_FORCE_CLIPPED_SPACING && r.k >= 2 && r.k <= 22 && r.n >= 4096;
-    // (ClippedSpacingForce keeps its compact-support kernels: measured through this route on the graded 10 M-point cloud,
-    // 39 ms per iteration against 20 — the k-selection grid hands a quarter of a graded cloud's queries back)
     if (rebuild) {
         // snapshot tail <- p, tree rebuilt (src/repel.jl:245-253): scatter P into a free buffer
         const int t = pick_free(r, r.bufP, -1);
         if ((rc = ensure(ctx, ctx->pts[t], sizeof(Pt<T>) * (size_t)(r.n + r.shard_extra)))) return rc;
         ctx->hash_view = r.pending; // a replaced fixed head waiting in P (wtp_relax_set_fixed_dev)
         int sp = span_begin(ctx, 0);
-        // Compact-support sweep (fp32, ClippedSpacingForce, k >= 2): cells only have to cover the
-        // law's support u0*s and the nearest-neighbour radius, so they can be smaller than the k-NN
-        // cells (rho ~ 3.5 instead of ~8): 2.3x fewer candidates per query.
-        r.cs_sweep = r.force.kind == WTP_FORCE_CLIPPED_SPACING && r.k >= 2 && r.k < 32 && !ctx->full_select &&
-                     !ctx->force_generic && !r.cs_disabled;
-        // round-2 sweep (wtp_cs2.hip, fp32 3-D): the nearest neighbour comes from the support or from a
-        // per-wave follow-up, so the cells only cover the support: rho ~ 1
-        const bool cs2 = r.cs_sweep && sizeof(T) == 4 && r.dim == 3;
-        double rho_cs = r.cs_sweep ? (cs2 ? kRhoCs2 : 3.5 * (ctx->rho / 9.0)) : 0.0;
-        // every other law (and ClippedSpacingForce with WTP_FULL_SELECT=1 or over-full support cells): the sweep with the
-        // explicit k-selection — on the x-slowest layout of wtp_ksel.hip where that applies (fp32, 3-D, k <= 22)
-        const bool ksel_ok = sizeof(T) == 4 && r.dim == 3 && ctx->ksel && !ctx->force_generic && r.k >= 2 &&
-                             r.k <= ksel_kmax() && r.n >= 4096;
-        r.ksel_sweep = !r.cs_sweep && ksel_ok;
-        if (r.ksel_sweep) rho_cs = r.tune.valid && r.tune.bx > 0 ? r.tune.rho : ksel_rho_for(r.k);
+        r.route = sweep_route<T>(ctx, r);
         if (r.spacing_typ <= 0) { // once per session: the spacing a typical point asks for
             r.spacing_typ = r.spacing_const;
             if (r.spacing_kind != WTP_SPACING_CONSTANT) {
@@ -1348,20 +1451,13 @@ template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_ste
                 if (!(r.spacing_typ > 0)) r.spacing_typ = r.spacing_max;
             }
         }
-        // The compact-support sweep needs cells that cover the law's support u0*s.  With a variable
-        // spacing the cell edge follows the spacing a typical point asks for (the mean over points, which
-        // the dense regions dominate), not the largest one: the few points whose support is wider than
-        // that are handed to the exact path, instead of everybody's cells being 64x over-full.
-        // (constant spacing: c - margin = c (1 - 1/256) must reach u0 s, 1.01 does; variable: 10 % headroom over the mean)
-        const double cell_f = (cs2 && r.spacing_kind == WTP_SPACING_CONSTANT) ? 1.01 : 1.1;
-        double min_cell = r.cs_sweep ? cell_f * r.force.u0 * (r.spacing_typ < r.spacing_max ? r.spacing_typ : r.spacing_max)
-                                     : 0.0;
+        RouteGrid g = route_grid(ctx, r);
         const Pt<T>* in = (const Pt<T>*)ctx->pts[r.bufP].p;
         Pt<T>* out = (Pt<T>*)ctx->pts[t].p;
         if (!r.tune.valid) { // once per session: measured cell edge, LDS point area sized from the real grid
             double rho_eff = 0;
             Grid<T> hg;
-            if ((rc = build_hash_tuned<T>(ctx, r.tune, in, out, r.n, r.dim, r.k, rho_cs, min_cell, &hg, &rho_eff))) return rc;
+            if ((rc = build_hash_tuned<T>(ctx, r.tune, in, out, r.n, r.dim, r.k, g.rho, g.min_cell, &hg, &rho_eff))) return rc;
             // A spacing far coarser than the cloud (the reference's own tests repel 46 786 face centres 0.22 apart
             // with a spacing of 3): cells that cover the law's support then hold hundreds of points, every support
             // ball holds more than k of them and each query would go to the exact path one by one.  Such a session
@@ -1369,27 +1465,25 @@ template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_ste
             // the crowded points are themselves queries: a dense FIXED wall around a few movable points is served
             // well by the support cells (their balls hold few points), and badly by small cells (the movable
             // points' k-th neighbour is many cells away).
-            if (r.cs_sweep && rho_eff > (cs2 ? 5.0 : 4.0 * rho_cs) && 2 * r.n_fixed < r.n) {
+            if (route_cs(r.route) && rho_eff > (r.route == SweepRoute::Cs2 ? 5.0 : 4.0 * g.rho) && 2 * r.n_fixed < r.n) {
                 r.cs_disabled = true;
-                r.cs_sweep = false;
-                r.ksel_sweep = ksel_ok;
-                rho_cs = r.ksel_sweep ? ksel_rho_for(r.k) : 0.0;
-                min_cell = 0.0;
-                if ((rc = build_hash_tuned<T>(ctx, r.tune, in, out, r.n, r.dim, r.k, rho_cs, min_cell, &hg, &rho_eff))) return rc;
+                r.route = sweep_route<T>(ctx, r);
+                g = route_grid(ctx, r);
+                if ((rc = build_hash_tuned<T>(ctx, r.tune, in, out, r.n, r.dim, r.k, g.rho, g.min_cell, &hg, &rho_eff))) return rc;
             }
             r.cs2_bx = 0;
-            if (r.cs_sweep && cs2) {
+            if (r.route == SweepRoute::Cs2) {
                 Grid<float> hgf;
                 memcpy(&hgf, &hg, sizeof(hgf)); // T == float here
                 if ((rc = cs2_tune(ctx, r, hgf, rho_eff))) return rc;
-            } else if (r.cs_sweep) {
+            } else if (route_cs(r.route)) {
                 int hc = (int)(HCELLS * rho_eff * 1.15) + 128;
                 hc = (hc + 63) / 64 * 64;
                 r.brick_hcap = hc < 640 ? 640 : (hc > 2560 ? 2560 : hc);
             }
-            if (r.ksel_sweep) {
+            if (r.route == SweepRoute::Ksel) {
                 if ((rc = ksel_tune<T>(ctx, r.tune, in, out, r.n, r.dim, r.k, hg, rho_eff))) return rc;
-                rho_cs = r.tune.rho;
+                g.rho = r.tune.rho;
             }
             r.tune.valid = true;
             r.tuned_fixed = r.n_fixed;
@@ -1404,12 +1498,14 @@ template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_ste
             ctx->reuse_grid = reuse;
             r.grid_age = reuse ? r.grid_age + 1 : 0;
             if (!reuse) r.grid_fixed = r.n_fixed;
-            ctx->topology_build = f64k_ok; // (no canonical-order pass: 0.37 ms per 10 M Float64 points)
-            rc = build_hash<T>(ctx, in, out, r.n, r.dim, r.k, 0.0, rho_cs, min_cell, r.tune.scale);
+            // the Float64 candidate route orders every sum by (d2, index) explicitly, on the exact path behind it too: no
+            // canonical-order pass (0.37 ms per 10 M Float64 points)
+            ctx->topology_build = r.route == SweepRoute::F64Ksel;
+            rc = build_hash<T>(ctx, in, out, r.n, r.dim, r.k, 0.0, g.rho, g.min_cell, r.tune.scale);
             ctx->topology_build = false;
             ctx->reuse_grid = false;
         }
-        r.last_rho_cs = rho_cs;
+        r.last_rho_cs = g.rho;
         span_end(ctx, sp);
         ctx->hash_view.active = false;
         if (rc) return rc;
@@ -1459,30 +1555,31 @@ template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_ste
     // [4] of the wave kernel, [8] uncovered queries
     a.fb2_count = (int32_t*)ctx->fb_count.p + 4;
     a.stop = ctx->stop_dev;
-    a.nn_list = nullptr;
     a.nn_count = (int32_t*)ctx->fb_count.p + 2;
-    // wtp_cs2.hip: cs_ball_kernel — variable spacing (supports wider than a cell), and every query of a sweep against a stale snapshot
-    const bool ball = r.cs_sweep && sizeof(T) == 4 && (r.spacing_kind != WTP_SPACING_CONSTANT || r.bufS != r.bufP);
-    if (r.cs_sweep && (r.cs2_bx > 0 || ball)) {
+    const SweepRoute route = step_route(r, fresh);
+    // the session's route keeps the ball kernel's list: supports wider than a cell, and every query of a stale snapshot
+    const bool ball = route_ball(r.route) && (!fresh || r.spacing_kind != WTP_SPACING_CONSTANT);
+    if (ball || route == SweepRoute::Cs2) {
         if ((rc = ensure(ctx, ctx->nn_list, sizeof(int32_t) * (size_t)r.n))) return rc;
-        a.nn_list = (int32_t*)ctx->nn_list.p;
-    }
-    if (ball) { // the follow-up kernel has consumed the list by the time the ball kernel refills it
-        a.ball_list = (int32_t*)ctx->nn_list.p;
-        a.ball_count = (int32_t*)ctx->fb_count.p + 6;
-    }
-    if (r.cs_sweep && sizeof(T) == 8 && (r.spacing_kind != WTP_SPACING_CONSTANT || r.bufS != r.bufP) && ctx->ball64) { // wtp_ball64.hip: its Float64 twin
-        if ((rc = ensure(ctx, ctx->nn_list, sizeof(int32_t) * (size_t)r.n))) return rc;
-        a.ball_list = (int32_t*)ctx->nn_list.p;
-        a.ball_count = (int32_t*)ctx->fb_count.p + 6;
+        if (sizeof(T) == 4) a.nn_list = (int32_t*)ctx->nn_list.p; // wtp_cs2.hip: the follow-up kernel's list
+        if (ball) { // the follow-up kernel has consumed the list by the time the ball kernel refills it
+            a.ball_list = (int32_t*)ctx->nn_list.p;
+            a.ball_count = (int32_t*)ctx->fb_count.p + 6;
+        }
     }
     if ((rc = ensure(ctx, ctx->diag, 128))) return rc;
     a.diag = (unsigned long long*)ctx->diag.p;
-    a.brick_hcap = r.cs_sweep ? r.brick_hcap : (r.ksel_sweep ? r.tune.hcap : 0);
-    a.cs2_bx = r.cs_sweep ? r.cs2_bx : 0;
+    // the grid the session's route was built for (the exact path's kernels receive it too), and the first filter radius
+    a.brick_hcap = route_cs(r.route) ? r.brick_hcap : (r.route == SweepRoute::Ksel ? r.tune.hcap : 0);
+    a.cs2_bx = route_cs(r.route) ? r.cs2_bx : 0;
     a.cs2_chunked = (r.spacing_kind != WTP_SPACING_CONSTANT || r.cs2_rho > 1.6) ? 1 : 0;
-    a.ksel_bx = r.ksel_sweep ? r.tune.bx : 0;
-    if (r.ksel_sweep) a.cap_count = (float)ksel_cap_count(r.k);
+    a.ksel_bx = r.route == SweepRoute::Ksel ? r.tune.bx : 0;
+    if (r.route == SweepRoute::Ksel) a.cap_count = (float)ksel_cap_count(r.k);
+    if (route == SweepRoute::Select || route == SweepRoute::Cs || route == SweepRoute::Cs2) {
+        a.gamma_cap = (T)kGammaCapSweep;
+        a.cap_count = (float)(4.18879 * kGammaCapSweep * kGammaCapSweep * kGammaCapSweep * ctx->rho * (a.k + 1) / 22.0);
+    }
+    if (route == SweepRoute::Cs64 || route == SweepRoute::Cs64Wave) a.gamma_cap = (T)kGammaCap;
     a.tnn_frac = (T)kTnnFrac;
     a.cover_axis = r.cover_axis;
     a.cover_lo = (T)r.cover_lo;
@@ -1495,13 +1592,7 @@ template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_ste
     if (!ctx->counters_clean) WTP_HIP(ctx, hipMemsetAsync(ctx->fb_count.p, 0, 64, ctx->stream));
     ctx->counters_clean = false; // (set again by the step's final reduction, which zeroes the block after reading it)
     a.used_brick = a.used_wave = a.used_generic = 0;
-    bool by_candidates = false;
-    if constexpr (sizeof(T) == 8) {
-        // the k-nearest laws in Float64 on a fresh snapshot: fp32 candidates, exact re-ranking (wtp_sweep64.hip)
-        by_candidates = fresh && f64k_ok;
-        if (by_candidates && (rc = relax_f64_ksel_sweep(ctx, a))) return rc;
-    }
-    if (!by_candidates && (rc = launch_sweep<T>(ctx, a, fresh))) return rc;
+    if ((rc = launch_sweep<T>(ctx, a, route, ball && route_ball(route)))) return rc;
     int sp = span_begin(ctx, 2);
     if (r.wall_active) { // p[id] = constrain(id, x_i, x_i + disp) (src/repel.jl:290): the octree wall rule
         char* wf = (char*)ctx->wall_flags.p;

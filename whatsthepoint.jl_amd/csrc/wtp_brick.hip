@@ -960,102 +960,9 @@ template <> int launch_topology<double>(wtp_ctx* ctx, SearchArgs<double>& a) {
     return launch_generic_topology<double>(ctx, a, true); // fp64: exact wave-per-query path
 }
 
-template <> int launch_sweep<float>(wtp_ctx* ctx, SearchArgs<float>& a, bool fresh) {
-    // the caller cleared the counter block; partial slots need no clearing: the reduction reads only
-    // the slots this step's launches write (a.used_*)
-    ctx->n_sweep_launches += 1;
-    if (!fresh || a.k > kFastKMax - 1 || ctx->force_generic) {
-        const int sp = span_begin(ctx, 1);
-        int rc;
-        if (!fresh && !ctx->force_generic && a.ball_list && a.force_kind == WTP_FORCE_CLIPPED_SPACING && a.k >= 2 && !ctx->full_select) {
-            // A stale snapshot (rebuild_every > 1, src/repel.jl:245) and the default law: the query has moved away from its
-            // snapshot entry, so the brick kernels (queries = the staged points) do not apply, but the ball kernel's argument
-            // does — the support ball around the point where it is NOW, searched in the block that provably holds it, at
-            // most k points in it — with eight lanes per query instead of the wave kernel's 64 (10.5 -> see DESIGN.md).
-            rc = launch_cs_all_slots(ctx, a.fb_list, a.n, a.fb_count);
-            if (!rc) rc = launch_cs_ball(ctx, a, a.ball_list, a.ball_count);
-            if (!rc) rc = launch_generic_sweep<float>(ctx, a, false);
-        } else {
-            rc = launch_generic_sweep<float>(ctx, a, true);
-        }
-        span_end(ctx, sp);
-        return rc;
-    }
-    if (a.ksel_bx > 0) { // the session built the grid for the x-slowest layout (wtp_ksel.hip); a.cap_count is the caller's
-        const int spk = span_begin(ctx, 1);
-        int rk = launch_ksel_sweep(ctx, a);
-        span_end(ctx, spk);
-        if (rk) return rk;
-        const int spk2 = span_begin(ctx, 2);
-        a.fb_r0 = 3;
-        rk = launch_generic_sweep<float>(ctx, a, false);
-        span_end(ctx, spk2);
-        return rk;
-    }
-    a.gamma_cap = (float)kGammaCapSweep;
-    a.cap_count = (float)(4.18879 * kGammaCapSweep * kGammaCapSweep * kGammaCapSweep * ctx->rho * (a.k + 1) / 22.0);
-    const int sp = span_begin(ctx, 1);
-    // ClippedSpacingForce (the reference default) takes the compact-support sweep unless
-    // WTP_FULL_SELECT=1 asks for the explicit k-selection on every query (both give the same output)
-    // (the caller sized the grid for it and says so by passing the LDS point capacity)
-    const bool cs = a.brick_hcap > 0 && a.force_kind == WTP_FORCE_CLIPPED_SPACING && a.k >= 2 && !ctx->full_select;
-    if (cs && a.cs2_bx > 0 && a.spacing_pp && a.ball_list) {
-        // variable spacing: bricks that would hand every point back are found first and passed over (wtp_cs2.hip)
-        const int dead_cap = (int)(ctx->cell_start.cap / sizeof(int32_t) / 4 + 4096);
-        int rd = ensure(ctx, ctx->brick_dead, (size_t)dead_cap);
-        if (!rd) rd = launch_cs2_dead(ctx, a, (uint8_t*)ctx->brick_dead.p, dead_cap);
-        if (rd) {
-            span_end(ctx, sp);
-            return rd;
-        }
-        a.brick_dead = (const uint8_t*)ctx->brick_dead.p;
-        a.brick_dead_cap = dead_cap;
-    }
-    int rc = cs ? (a.cs2_bx > 0 ? launch_cs2(ctx, a) : brick_launch<1, 0, 1>(ctx, a))
-                : (a.k == 21 ? brick_launch<1, 21, 0>(ctx, a) : brick_launch<1, 0, 0>(ctx, a));
-    span_end(ctx, sp);
-    if (rc) return rc;
-    const int sp2 = span_begin(ctx, 2);
-    if (cs && a.cs2_bx > 0) rc = launch_cs2_followup(ctx, a); // nearest neighbour of the queries the bricks left open
-    // variable spacing: hand-backs whose support outgrew their cell are finished ball by ball (wtp_cs2.hip)
-    if (!rc && cs && a.spacing_pp && a.ball_list) rc = launch_cs_ball(ctx, a, a.ball_list, a.ball_count);
-    if (!rc) rc = launch_generic_sweep<float>(ctx, a, false);
-    span_end(ctx, sp2);
-    return rc;
-}
-
-template <> int launch_sweep<double>(wtp_ctx* ctx, SearchArgs<double>& a, bool fresh) {
-    ctx->n_sweep_launches += 1;
-    // ClippedSpacingForce on a fresh snapshot: compact-support brick sweep (wtp_brick64.hip), the wave
-    // kernel takes what it hands back.  Everything else in fp64: the exact wave-per-query path.
-    const bool cs = fresh && a.brick_hcap > 0 && a.force_kind == WTP_FORCE_CLIPPED_SPACING && a.k >= 2 &&
-                    a.k <= kFastKMax - 1 && !ctx->full_select && !ctx->force_generic;
-    if (!cs) {
-        const int sp = span_begin(ctx, 1);
-        int rc;
-        if (!fresh && a.ball_list && a.force_kind == WTP_FORCE_CLIPPED_SPACING && a.k >= 2 && a.k <= kFastKMax - 1 &&
-            !ctx->full_select && !ctx->force_generic) {
-            // a stale snapshot and the default law: every query through the Float64 ball kernel (as in fp32, launch_sweep<float>)
-            rc = launch_cs_all_slots(ctx, a.fb_list, a.n, a.fb_count);
-            if (!rc) rc = launch_cs_ball64(ctx, a, a.ball_list, a.ball_count);
-            if (!rc) rc = launch_generic_sweep<double>(ctx, a, false);
-        } else {
-            rc = launch_generic_sweep<double>(ctx, a, true);
-        }
-        span_end(ctx, sp);
-        return rc;
-    }
-    a.gamma_cap = kGammaCap;
-    const int sp = span_begin(ctx, 1);
-    int rc = launch_brick_cs<double>(ctx, a);
-    // variable spacing: the hand-backs whose support ball is wider than a cell (wtp_ball64.hip), before the exact path
-    if (!rc && a.spacing_pp && a.ball_list) rc = launch_cs_ball64(ctx, a, a.ball_list, a.ball_count);
-    span_end(ctx, sp);
-    if (rc) return rc;
-    const int sp2 = span_begin(ctx, 2);
-    rc = launch_generic_sweep<double>(ctx, a, false);
-    span_end(ctx, sp2);
-    return rc;
+int launch_brick_sweep(wtp_ctx* ctx, SearchArgs<float>& a, bool cs) {
+    if (cs) return brick_launch<1, 0, 1>(ctx, a);
+    return a.k == 21 ? brick_launch<1, 21, 0>(ctx, a) : brick_launch<1, 0, 0>(ctx, a);
 }
 
 } // namespace wtp

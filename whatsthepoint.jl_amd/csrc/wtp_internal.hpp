@@ -208,6 +208,20 @@ struct GridTune {
     int bx = 0, hcap = 0;    // wtp_ksel.hip: brick length along x and LDS point area (0: not measured)
 };
 
+// The kernels of a relax sweep on a fresh snapshot, chosen at every rebuild (sweep_route in wtp_api.hip).  A stale snapshot
+// (rebuild_every > 1) sends every query through the ball kernel on the routes that have one, else to the exact path.
+enum class SweepRoute {
+    Exact,    // wave-per-query and serial kernels for every query
+    Select,   // fp32: brick_kernel<1,21|0,0>, explicit k-selection on 4 x 4 x 4 bricks (wtp_brick.hip)
+    Ksel,     // fp32 3-D: ksel_kernel on the x-slowest layout (wtp_ksel.hip); Select until its geometry is measured
+    Cs,       // fp32 2-D ClippedSpacingForce: brick_kernel<1,0,1> over cells that cover the law's support
+    Cs2,      // fp32 3-D ClippedSpacingForce: cs2_kernel (wtp_cs2.hip)
+    Cs64,     // fp64 ClippedSpacingForce: brick_cs_kernel<double> (wtp_brick64.hip), the ball kernel for wide supports
+    Cs64Wave, // the same with WTP_BALL64=0: wide supports and stale snapshots go to the exact path
+    Ball,     // a stale snapshot on Cs, Cs2 or Cs64: every query through the ball kernel (per step, never a session's route)
+    F64Ksel,  // fp64 3-D k-nearest laws: fp32 candidates, exact re-ranking (wtp_sweep64.hip)
+};
+
 struct RelaxState {
     bool active = false;
     int64_t n = 0, n_fixed = 0;
@@ -227,9 +241,8 @@ struct RelaxState {
     int sweeps_since_rebuild = 0; // every sweep moves a point by at most its spacing (src/repel.jl:286-289)
     bool moved_by_hand = false;   // wtp_relax_set since the last rebuild: that bound is gone
     double spacing_typ = 0;  // mean spacing over the snapshot (floor of the compact-support cell edge)
-    bool cs_sweep = false;   // compact-support sweep in use (ClippedSpacingForce)
+    SweepRoute route = SweepRoute::Exact; // the sweep's kernels, chosen at the last rebuild
     bool cs_disabled = false; // measured on the first rebuild: support cells would be over-full, use the k-selection sweep
-    bool ksel_sweep = false; // k-selection sweep on the x-slowest layout (wtp_ksel.hip)
     double cs2_rho = 0;      // points per cell the sweep's bricks were sized for (cs2_tune)
     int cs2_bx = 0;          // > 0: the round-2 compact-support sweep (wtp_cs2.hip) with bricks of this many cells along x
     int64_t tuned_fixed = 0; // fixed points the grid / brick geometry was measured with (a swapped head re-measures when it differs by > 5 % of n)
@@ -405,7 +418,8 @@ template <typename T>
 int load_points(wtp_ctx* ctx, const T* d_xyz, Pt<T>* out, int64_t n, int dim);
 
 template <typename T> int launch_topology(wtp_ctx* ctx, SearchArgs<T>& a);
-template <typename T> int launch_sweep(wtp_ctx* ctx, SearchArgs<T>& a, bool fresh);
+// fp32 sweep on 4 x 4 x 4 bricks (wtp_brick.hip), compact-support (cs) or explicit k-selection; hand-backs land in a.fb_list
+int launch_brick_sweep(wtp_ctx* ctx, SearchArgs<float>& a, bool cs);
 // fp64 compact-support brick sweep (wtp_brick64.hip); hand-backs land in a.fb_list
 template <typename T> int launch_brick_cs(wtp_ctx* ctx, SearchArgs<T>& a);
 // exact paths: wave-per-query (list = fb_list or all points), then the serial kernel on fb2_list
