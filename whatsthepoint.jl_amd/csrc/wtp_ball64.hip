@@ -7,8 +7,8 @@
 // must not.  This is its Float64 twin: eight lanes per query walk the (2R+1)^3 block that provably holds the ball, the
 // ball's points (at most k, self included: more than k is the k-selection's case) are collected in the group's LDS list,
 // ranked by (d2, index), their force terms evaluated by the lanes and added by one lane in that order — what the wave
-// kernel's compact-support shortcut does with the same points (wtp_wave.hip: cs_done), so the same bits.  A query alone
-// in its ball needs only its nearest neighbour, which must lie inside the radius the block certifies.  Anything else
+// kernel's compact-support shortcut does with the same points (wtp_wave.hip: cs_done), so the same bits.  A query whose
+// ball holds only its own entry needs its nearest neighbour, which must lie inside the radius the block certifies.  Anything else
 // (more than k points in the ball, a ball beyond four cells, a lonely query whose neighbour is not certified) is left
 // for the wave kernel.
 #include "wtp_device.hpp"
@@ -120,10 +120,12 @@ __global__ __launch_bounds__(kB64Threads) void cs_ball64_kernel(SearchArgs<doubl
             }
         }
         __builtin_amdgcn_wave_barrier();
-        const int m_lim = sg->count; // population of the ball, self included
-        // what this kernel finishes: the ball holds 2 .. k points, or the query is alone in it and its nearest neighbour is certified
-        const bool alone = m_lim == 1;
-        const bool mine = ok && ((m_lim >= 2 && m_lim <= K && m_lim <= kB64Cap) || (alone && nid != 0x7FFFFFFF));
+        const int m_lim = sg->count; // population of the ball (self among them, unless the query has moved off a stale entry)
+        // what this kernel finishes: the ball holds 1 .. k points, or the query's own entry alone and its nearest neighbour is
+        // certified.  On a stale snapshot the one member of a ball may be another point (src/repel.jl:263-265): a ball of one,
+        // whose member is the nearest other point and the only nonzero term.
+        const bool alone = m_lim == 1 && sg->id[0] == qid;
+        const bool mine = ok && ((!alone && m_lim >= 1 && m_lim <= K && m_lim <= kB64Cap) || (alone && nid != 0x7FFFFFFF));
         if (!mine) {
             if (l8 == 0 && on) out_list[atomicAdd(out_count, 1)] = gslot;
             continue; // (group-uniform)
@@ -174,7 +176,7 @@ __global__ __launch_bounds__(kB64Threads) void cs_ball64_kernel(SearchArgs<doubl
             a.nn_dist[gslot] = nd;
             a.nn_id[gslot] = nn;
             acc_point<double>(acc, f, nd, s, qid, nn);
-            // sharded sessions: the answer rests on the support ball, or — alone in it — on the neighbour's distance too
+            // sharded sessions: the answer rests on the support ball, or — self alone in it — on the neighbour's distance too
             const double last = sg->d2[sg->order[m - 1]];
             const double need = alone ? (last > lim ? last : lim) : lim;
             if (reaches_past_cover<double>(a, qp.x, qp.y, qp.z, need)) atomicAdd(a.uncovered, 1);

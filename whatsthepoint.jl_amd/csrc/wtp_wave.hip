@@ -214,10 +214,12 @@ __global__ __launch_bounds__(kThreads) void wave_kernel(SearchArgs<T> a, const i
                     cs_done = true; // the answer is everything within the ball: the cut is its radius
                     break;
                 }
-                // Alone in its support ball: every term of the sum is exactly 0 and only the nearest
-                // neighbour (nn_dist / nn_id) is still unknown — a 2-nearest search (self + one) gives
-                // the same step as the k-list would.  The list already holds everything the block
-                // certifies, so usually it is right there.
+                // One point in the support ball.  If it is self, every term of the sum is exactly 0 and only
+                // the nearest neighbour (nn_dist / nn_id) is still unknown.  On a stale snapshot it may be
+                // another point (self has moved off its entry): that point is the nearest neighbour and its
+                // term the only nonzero one.  Either way a 2-nearest search gives the same step as the
+                // k-list would.  The list already holds everything the block certifies, so usually the
+                // second point is right there.
                 if (!overflow && m_lim == 1) {
                     Kq = 2;
                     if (m >= 2) break; // the 2nd smallest lies inside the certified radius: done
