@@ -125,6 +125,13 @@ static int sync(wtp_ctx* ctx) {
 }
 
 static size_t tsize(int dtype) { return dtype == WTP_F64 ? 8 : 4; }
+static size_t pt_size(int dtype) { return by_dtype(dtype, [](auto t) { return sizeof(Pt<decltype(t)>); }); }
+
+int need_session(wtp_ctx* ctx, const char* entry) {
+    if (!ctx) return WTP_ERR_ARG;
+    if (!ctx->relax.active) return fail(ctx, WTP_ERR_STATE, std::string(entry) + " before wtp_relax_init");
+    return WTP_OK;
+}
 
 static double host_max(const void* v, int64_t n, int dtype) {
     double m = 0;
@@ -656,24 +663,41 @@ WTP_API int wtp_destroy(wtp_ctx* ctx) {
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
     wtp_comm_finalize(ctx);
-    DevBuf* bufs[] = {&ctx->pts[0], &ctx->pts[1], &ctx->pts[2], &ctx->raw_in, &ctx->cell_of, &ctx->rank_of,
-                      &ctx->cell_cnt, &ctx->cell_start, &ctx->scan_tmp, &ctx->grid, &ctx->bbox_part,
-                      &ctx->idx_out, &ctx->dist_out, &ctx->counts_out, &ctx->forces, &ctx->nn_dist,
-                      &ctx->nn_id, &ctx->spacing_pp, &ctx->partials, &ctx->stats, &ctx->fb_list,
-                      &ctx->fb_count, &ctx->fb2_list, &ctx->fb2_count, &ctx->nn_list, &ctx->brick_dead, &ctx->rad_tmp, &ctx->rad_done, &ctx->rad_arena, &ctx->rad_arena_off, &ctx->rad_pos, &ctx->rad_bricks, &ctx->grid_b, &ctx->cell_start_b, &ctx->f64k_s64, &ctx->f64k_slot, &ctx->f64k_lists, &ctx->f64k_cnt, &ctx->scratch, &ctx->diag,
-                      &ctx->ins_in, &ctx->ins_elems, &ctx->ins_partial, &ctx->ins_out, &ctx->mesh_nodes, &ctx->mesh_pn, &ctx->mesh_io,
-                      &ctx->wall_flags, &ctx->wall_tri, &ctx->wall_hint, &ctx->mesh_cls, &ctx->kd_nodes, &ctx->sp_hint, &ctx->occ, &ctx->box_dev,
-                      &ctx->cand_idx, &ctx->cand_dist, &ctx->f32_pts, &ctx->comm_scratch, &ctx->sp_cert};
-    for (DevBuf* b : bufs)
-        if (b->p) hipFree(b->p);
     if (ctx->host_pinned) hipHostFree(ctx->host_pinned);
     for (auto e : ctx->ev_pool) hipEventDestroy(e);
     if (ctx->ev_comm_a) hipEventDestroy(ctx->ev_comm_a);
     if (ctx->ev_comm_b) hipEventDestroy(ctx->ev_comm_b);
     if (ctx->comm_stream) hipStreamDestroy(ctx->comm_stream);
     hipStreamDestroy(ctx->own_stream);
-    delete ctx;
+    delete ctx; // (frees the device buffers)
     return WTP_OK;
+}
+
+// The k-NN dispatch of a device cloud: fp32 through knn_dev_t; fp64 through fp32 candidates and exact re-ranking
+// (knn_dev_f64), else the exact fp64 path.
+static int knn_on_device(wtp_ctx* ctx, const void* d_xyz, int64_t n, int dim, int dtype, int k, int include_self,
+                         int32_t* d_idx, void* d_dist) {
+    bool done = false;
+    int rc = dtype == WTP_F64 ? knn_dev_f64(ctx, (const double*)d_xyz, n, dim, k, include_self, d_idx, (double*)d_dist, &done)
+                              : WTP_OK;
+    if (rc || done) return rc;
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return knn_dev_t<T>(ctx, (const T*)d_xyz, n, dim, k, include_self, d_idx, (T*)d_dist);
+    });
+}
+
+// rows and, if wanted, distances of a host cloud, left in ctx->idx_out / dist_out (the cloud in ctx->raw_in)
+static int knn_rows_on_device(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype, int k, int include_self,
+                              bool want_dist) {
+    const size_t ts = tsize(dtype);
+    int rc;
+    if ((rc = ensure(ctx, ctx->raw_in, ts * (size_t)n * dim))) return rc;
+    if ((rc = ensure(ctx, ctx->idx_out, sizeof(int32_t) * (size_t)n * k))) return rc;
+    if (want_dist && (rc = ensure(ctx, ctx->dist_out, ts * (size_t)n * k))) return rc;
+    WTP_HIP(ctx, hipMemcpyAsync(ctx->raw_in.p, xyz, ts * (size_t)n * dim, hipMemcpyHostToDevice, ctx->stream));
+    return knn_on_device(ctx, ctx->raw_in.p, n, dim, dtype, k, include_self, (int32_t*)ctx->idx_out.p,
+                         want_dist ? ctx->dist_out.p : nullptr);
 }
 
 WTP_API int wtp_knn_dev(wtp_ctx* ctx, const void* d_xyz, int64_t n, int dim, int dtype, int k, int include_self,
@@ -684,15 +708,7 @@ WTP_API int wtp_knn_dev(wtp_ctx* ctx, const void* d_xyz, int64_t n, int dim, int
     if ((rc = check_idle(ctx))) return rc;
     if (!d_idx_out) return fail(ctx, WTP_ERR_ARG, "idx_out is NULL");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    if (dtype == WTP_F32) {
-        rc = knn_dev_t<float>(ctx, (const float*)d_xyz, n, dim, k, include_self, d_idx_out, (float*)d_dist_out);
-    } else {
-        bool done = false;
-        rc = knn_dev_f64(ctx, (const double*)d_xyz, n, dim, k, include_self, d_idx_out, (double*)d_dist_out, &done);
-        if (!rc && !done)
-            rc = knn_dev_t<double>(ctx, (const double*)d_xyz, n, dim, k, include_self, d_idx_out, (double*)d_dist_out);
-    }
-    if (rc) return rc;
+    if ((rc = knn_on_device(ctx, d_xyz, n, dim, dtype, k, include_self, d_idx_out, d_dist_out))) return rc;
     return sync(ctx);
 }
 
@@ -705,23 +721,7 @@ WTP_API int wtp_knn(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype
     if (!idx_out) return fail(ctx, WTP_ERR_ARG, "idx_out is NULL");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t ts = tsize(dtype);
-    if ((rc = ensure(ctx, ctx->raw_in, ts * (size_t)n * dim))) return rc;
-    if ((rc = ensure(ctx, ctx->idx_out, sizeof(int32_t) * (size_t)n * k))) return rc;
-    if (dist_out && (rc = ensure(ctx, ctx->dist_out, ts * (size_t)n * k))) return rc;
-    WTP_HIP(ctx, hipMemcpyAsync(ctx->raw_in.p, xyz, ts * (size_t)n * dim, hipMemcpyHostToDevice, ctx->stream));
-    void* ddist = dist_out ? ctx->dist_out.p : nullptr;
-    if (dtype == WTP_F32)
-        rc = knn_dev_t<float>(ctx, (const float*)ctx->raw_in.p, n, dim, k, include_self, (int32_t*)ctx->idx_out.p,
-                              (float*)ddist);
-    else {
-        bool done = false;
-        rc = knn_dev_f64(ctx, (const double*)ctx->raw_in.p, n, dim, k, include_self, (int32_t*)ctx->idx_out.p,
-                         (double*)ddist, &done);
-        if (!rc && !done)
-            rc = knn_dev_t<double>(ctx, (const double*)ctx->raw_in.p, n, dim, k, include_self,
-                                   (int32_t*)ctx->idx_out.p, (double*)ddist);
-    }
-    if (rc) return rc;
+    if ((rc = knn_rows_on_device(ctx, xyz, n, dim, dtype, k, include_self, dist_out != nullptr))) return rc;
     WTP_HIP(ctx, hipMemcpyAsync(idx_out, ctx->idx_out.p, sizeof(int32_t) * (size_t)n * k, hipMemcpyDeviceToHost,
                                 ctx->stream));
     if (dist_out)
@@ -730,24 +730,6 @@ WTP_API int wtp_knn(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype
 }
 
 // ---- consumers of the rows ------------------------------------------------------
-// rows (self included) and, if wanted, distances of a host cloud, left in ctx->idx_out / dist_out
-static int knn_rows_on_device(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype, int k, bool want_dist) {
-    const size_t ts = tsize(dtype);
-    int rc;
-    if ((rc = ensure(ctx, ctx->raw_in, ts * (size_t)n * dim))) return rc;
-    if ((rc = ensure(ctx, ctx->idx_out, sizeof(int32_t) * (size_t)n * k))) return rc;
-    if (want_dist && (rc = ensure(ctx, ctx->dist_out, ts * (size_t)n * k))) return rc;
-    WTP_HIP(ctx, hipMemcpyAsync(ctx->raw_in.p, xyz, ts * (size_t)n * dim, hipMemcpyHostToDevice, ctx->stream));
-    void* ddist = want_dist ? ctx->dist_out.p : nullptr;
-    if (dtype == WTP_F32)
-        return knn_dev_t<float>(ctx, (const float*)ctx->raw_in.p, n, dim, k, 1, (int32_t*)ctx->idx_out.p, (float*)ddist);
-    bool done = false;
-    rc = knn_dev_f64(ctx, (const double*)ctx->raw_in.p, n, dim, k, 1, (int32_t*)ctx->idx_out.p, (double*)ddist, &done);
-    if (!rc && !done)
-        rc = knn_dev_t<double>(ctx, (const double*)ctx->raw_in.p, n, dim, k, 1, (int32_t*)ctx->idx_out.p, (double*)ddist);
-    return rc;
-}
-
 WTP_API int wtp_pca_normals(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype, int k, void* normals_out) {
     int rc = check_cloud(ctx, xyz, n, dim, dtype);
     if (rc) return rc;
@@ -757,13 +739,13 @@ WTP_API int wtp_pca_normals(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, i
     if (!normals_out) return fail(ctx, WTP_ERR_ARG, "normals_out is NULL");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t ts = tsize(dtype);
-    if ((rc = knn_rows_on_device(ctx, xyz, n, dim, dtype, k, false))) return rc;
+    if ((rc = knn_rows_on_device(ctx, xyz, n, dim, dtype, k, 1, false))) return rc;
     if ((rc = ensure(ctx, ctx->scratch, ts * (size_t)n * dim))) return rc;
     int sp = span_begin(ctx, 2);
-    rc = dtype == WTP_F32 ? launch_pca_normals<float>(ctx, (const float*)ctx->raw_in.p, n, dim, (const int32_t*)ctx->idx_out.p,
-                                                      k, (float*)ctx->scratch.p)
-                          : launch_pca_normals<double>(ctx, (const double*)ctx->raw_in.p, n, dim,
-                                                       (const int32_t*)ctx->idx_out.p, k, (double*)ctx->scratch.p);
+    rc = by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_pca_normals<T>(ctx, (const T*)ctx->raw_in.p, n, dim, (const int32_t*)ctx->idx_out.p, k, (T*)ctx->scratch.p);
+    });
     span_end(ctx, sp);
     if (rc) return rc;
     WTP_HIP(ctx, hipMemcpyAsync(normals_out, ctx->scratch.p, ts * (size_t)n * dim, hipMemcpyDeviceToHost, ctx->stream));
@@ -780,7 +762,7 @@ WTP_API int wtp_gradient_limit(wtp_ctx* ctx, const void* centers, int64_t n, int
     if (max_sweeps < 0) return fail(ctx, WTP_ERR_ARG, "max_sweeps must be >= 0");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t ts = tsize(dtype);
-    if ((rc = knn_rows_on_device(ctx, centers, n, dim, dtype, k, true))) return rc;
+    if ((rc = knn_rows_on_device(ctx, centers, n, dim, dtype, k, 1, true))) return rc;
     const size_t o1 = (ts * (size_t)n + 255) / 256 * 256;
     if ((rc = ensure(ctx, ctx->scratch, 2 * o1 + 64))) return rc;
     char* b = (char*)ctx->scratch.p;
@@ -793,11 +775,11 @@ WTP_API int wtp_gradient_limit(wtp_ctx* ctx, const void* centers, int64_t n, int
     int sp = span_begin(ctx, 2);
     for (int first = 0; first < max_sweeps && !hst[0];) { // batches: one read-back per 16 sweeps
         const int batch = max_sweeps - first < 16 ? max_sweeps - first : 16;
-        rc = dtype == WTP_F32
-                 ? launch_minplus_batch<float>(ctx, (const int32_t*)ctx->idx_out.p, (const float*)ctx->dist_out.p, n, k, g,
-                                               tol, (float*)b, (float*)(b + o1), first, batch, st)
-                 : launch_minplus_batch<double>(ctx, (const int32_t*)ctx->idx_out.p, (const double*)ctx->dist_out.p, n, k,
-                                                g, tol, (double*)b, (double*)(b + o1), first, batch, st);
+        rc = by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            return launch_minplus_batch<T>(ctx, (const int32_t*)ctx->idx_out.p, (const T*)ctx->dist_out.p, n, k, g, tol, (T*)b,
+                                           (T*)(b + o1), first, batch, st);
+        });
         if (rc) return rc;
         WTP_HIP(ctx, hipMemcpyAsync(hst, st, 16, hipMemcpyDeviceToHost, ctx->stream));
         if ((rc = sync(ctx))) return rc;
@@ -891,11 +873,14 @@ template <typename T> static int radius_fill_t(wtp_ctx* ctx, const int64_t* d_of
     return rc;
 }
 
-WTP_API int wtp_radius_count(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype, double r, int32_t* counts_out) {
+// wtp_radius_count and wtp_radius_offsets: counts of a host cloud on the device, handed back as they are or, with
+// `offsets`, as CSR offsets (exclusive scan on the device: the counts never cross the bus and the offsets stay resident
+// for the fill)
+static int radius_count_call(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype, double r, bool offsets, void* out) {
     int rc = check_cloud(ctx, xyz, n, dim, dtype);
     if (rc) return rc;
     if (!(r >= 0) || !std::isfinite(r)) return fail(ctx, WTP_ERR_ARG, "radius must be finite and >= 0");
-    if (!counts_out) return fail(ctx, WTP_ERR_ARG, "counts_out is NULL");
+    if (!out) return fail(ctx, WTP_ERR_ARG, offsets ? "offsets_out is NULL" : "counts_out is NULL");
     if ((rc = check_idle(ctx))) return rc;
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t ts = tsize(dtype);
@@ -904,59 +889,40 @@ WTP_API int wtp_radius_count(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, 
     ctx->relax.have_tree = false;
     if ((rc = ensure(ctx, ctx->raw_in, ts * (size_t)n * dim))) return rc;
     if ((rc = ensure(ctx, ctx->counts_out, sizeof(int32_t) * (size_t)n))) return rc;
+    if (offsets && (rc = ensure(ctx, ctx->dist_out, sizeof(int64_t) * (size_t)(n + 1)))) return rc; // offsets live here until the fill
     WTP_HIP(ctx, hipMemcpyAsync(ctx->raw_in.p, xyz, ts * (size_t)n * dim, hipMemcpyHostToDevice, ctx->stream));
-    rc = dtype == WTP_F32 ? radius_count_t<float>(ctx, n, dim, r, (int32_t*)ctx->counts_out.p)
-                          : radius_count_t<double>(ctx, n, dim, r, (int32_t*)ctx->counts_out.p);
+    rc = by_dtype(dtype, [&](auto t) { return radius_count_t<decltype(t)>(ctx, n, dim, r, (int32_t*)ctx->counts_out.p); });
     if (rc) return rc;
-    WTP_HIP(ctx, hipMemcpyAsync(counts_out, ctx->counts_out.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost,
-                                ctx->stream));
+    if (offsets) {
+        // (radius_count_t uses scratch for nothing; the scan's tile sums go there)
+        if ((rc = ensure(ctx, ctx->scratch, offsets_scan_tmp_bytes(n)))) return rc;
+        int sp = span_begin(ctx, 2);
+        rc = launch_offsets_scan(ctx, (const int32_t*)ctx->counts_out.p, n, (int64_t*)ctx->scratch.p, (int64_t*)ctx->dist_out.p);
+        span_end(ctx, sp);
+        if (rc) return rc;
+        WTP_HIP(ctx, hipMemcpyAsync(out, ctx->dist_out.p, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    } else {
+        WTP_HIP(ctx, hipMemcpyAsync(out, ctx->counts_out.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    }
     if ((rc = sync(ctx))) return rc;
     ctx->rad_n = n;
     ctx->rad_dim = dim;
     ctx->rad_dtype = dtype;
     ctx->rad_r = r;
     ctx->rad_valid = true;
+    ctx->rad_offsets_dev = offsets;
+    if (offsets) ctx->rad_nnz = ((const int64_t*)out)[n];
     return WTP_OK;
 }
 
-// count + exclusive scan on the device: the caller gets the offsets it needs to allocate, the counts never
-// cross the bus and the offsets stay resident for the fill
+WTP_API int wtp_radius_count(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype, double r, int32_t* counts_out) {
+    return radius_count_call(ctx, xyz, n, dim, dtype, r, false, counts_out);
+}
+
 WTP_API int wtp_radius_offsets(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype, double r,
                                int64_t* offsets_out) {
-    int rc = check_cloud(ctx, xyz, n, dim, dtype);
-    if (rc) return rc;
-    if (!(r >= 0) || !std::isfinite(r)) return fail(ctx, WTP_ERR_ARG, "radius must be finite and >= 0");
-    if (!offsets_out) return fail(ctx, WTP_ERR_ARG, "offsets_out is NULL");
-    if ((rc = check_idle(ctx))) return rc;
-    WTP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t ts = tsize(dtype);
-    ctx->rad_valid = false;
-    ctx->rad_offsets_dev = false;
-    ctx->relax.have_tree = false;
-    if ((rc = ensure(ctx, ctx->raw_in, ts * (size_t)n * dim))) return rc;
-    if ((rc = ensure(ctx, ctx->counts_out, sizeof(int32_t) * (size_t)n))) return rc;
-    if ((rc = ensure(ctx, ctx->dist_out, sizeof(int64_t) * (size_t)(n + 1)))) return rc; // offsets live here until the fill
-    WTP_HIP(ctx, hipMemcpyAsync(ctx->raw_in.p, xyz, ts * (size_t)n * dim, hipMemcpyHostToDevice, ctx->stream));
-    rc = dtype == WTP_F32 ? radius_count_t<float>(ctx, n, dim, r, (int32_t*)ctx->counts_out.p)
-                          : radius_count_t<double>(ctx, n, dim, r, (int32_t*)ctx->counts_out.p);
-    if (rc) return rc;
-    // (radius_count_t uses scratch for nothing; the scan's tile sums go there)
-    if ((rc = ensure(ctx, ctx->scratch, offsets_scan_tmp_bytes(n)))) return rc;
-    int sp = span_begin(ctx, 2);
-    rc = launch_offsets_scan(ctx, (const int32_t*)ctx->counts_out.p, n, (int64_t*)ctx->scratch.p, (int64_t*)ctx->dist_out.p);
-    span_end(ctx, sp);
-    if (rc) return rc;
-    WTP_HIP(ctx, hipMemcpyAsync(offsets_out, ctx->dist_out.p, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost,
-                                ctx->stream));
-    if ((rc = sync(ctx))) return rc;
-    ctx->rad_n = n;
-    ctx->rad_dim = dim;
-    ctx->rad_dtype = dtype;
-    ctx->rad_r = r;
-    ctx->rad_valid = true;
-    ctx->rad_offsets_dev = true;
-    ctx->rad_nnz = offsets_out[n];
-    return WTP_OK;
+    return radius_count_call(ctx, xyz, n, dim, dtype, r, true, offsets_out);
 }
 
 WTP_API int wtp_radius_fill(wtp_ctx* ctx, const int64_t* offsets, int32_t* idx_out) {
@@ -983,8 +949,8 @@ WTP_API int wtp_radius_fill(wtp_ctx* ctx, const int64_t* offsets, int32_t* idx_o
     if (offsets)
         WTP_HIP(ctx, hipMemcpyAsync(ctx->dist_out.p, offsets, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice,
                                     ctx->stream));
-    rc = ctx->rad_dtype == WTP_F32 ? radius_fill_t<float>(ctx, (const int64_t*)ctx->dist_out.p, (int32_t*)ctx->idx_out.p)
-                                   : radius_fill_t<double>(ctx, (const int64_t*)ctx->dist_out.p, (int32_t*)ctx->idx_out.p);
+    rc = by_dtype(ctx->rad_dtype,
+                  [&](auto t) { return radius_fill_t<decltype(t)>(ctx, (const int64_t*)ctx->dist_out.p, (int32_t*)ctx->idx_out.p); });
     if (rc) return rc;
     if (nnz > 0)
         WTP_HIP(ctx, hipMemcpyAsync(idx_out, ctx->idx_out.p, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost,
@@ -1011,14 +977,14 @@ static int ensure_kd(wtp_ctx* ctx, const wtp_spacing_desc* s, int dim, int dtype
     const unsigned char* b = (const unsigned char*)s->boundary_xyz;
     for (size_t i = 0; i < bytes; ++i) h = (h ^ b[i]) * 1099511628211ull;
     if (ctx->kd_m == s->n_boundary && ctx->kd_key == h && ctx->kd_dim == dim && ctx->kd_dtype == dtype) return WTP_OK;
-    const size_t kdsz = dtype == WTP_F32 ? kd_bytes<float>(s->n_boundary) : kd_bytes<double>(s->n_boundary);
+    const size_t kdsz = by_dtype(dtype, [&](auto t) { return kd_bytes<decltype(t)>(s->n_boundary); });
     int rc;
     if ((rc = ensure(ctx, ctx->kd_nodes, kdsz))) return rc;
     std::vector<char> host(kdsz);
-    if (dtype == WTP_F32)
-        kd_build_host<float>((const float*)s->boundary_xyz, s->n_boundary, dim, host.data());
-    else
-        kd_build_host<double>((const double*)s->boundary_xyz, s->n_boundary, dim, host.data());
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        kd_build_host<T>((const T*)s->boundary_xyz, s->n_boundary, dim, host.data());
+    });
     WTP_HIP(ctx, hipMemcpyAsync(ctx->kd_nodes.p, host.data(), host.size(), hipMemcpyHostToDevice, ctx->stream));
     if ((rc = sync(ctx))) return rc; // `host` dies with this scope
     ctx->kd_m = s->n_boundary;
@@ -1068,12 +1034,11 @@ static int relax_init_impl(wtp_ctx* ctx, const void* snap_xyz, bool on_device, i
     if (kk > kGenericKMax) return fail(ctx, WTP_ERR_ARG, "k > 128 is not supported");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t ts = tsize(dtype);
-    const size_t ptsz = dtype == WTP_F32 ? sizeof(float4) : sizeof(double4);
     RelaxState& r = ctx->relax;
     r = RelaxState{};
     ctx->rad_valid = false;
     for (int i = 0; i < 2; ++i)
-        if ((rc = ensure(ctx, ctx->pts[i], ptsz * (size_t)n))) return rc;
+        if ((rc = ensure(ctx, ctx->pts[i], pt_size(dtype) * (size_t)n))) return rc;
     if ((rc = ensure(ctx, ctx->raw_in, ts * (size_t)n * dim))) return rc;
     if ((rc = ensure(ctx, ctx->forces, ts * (size_t)n))) return rc;
     if ((rc = ensure(ctx, ctx->nn_dist, ts * (size_t)n))) return rc;
@@ -1087,10 +1052,10 @@ static int relax_init_impl(wtp_ctx* ctx, const void* snap_xyz, bool on_device, i
     if ((rc = ensure(ctx, ctx->partials, sizeof(Partial) * (size_t)n_partials))) return rc;
     WTP_HIP(ctx, hipMemcpyAsync(ctx->raw_in.p, snap_xyz, ts * (size_t)n * dim,
                                 on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-    if (dtype == WTP_F32)
-        rc = load_points<float>(ctx, (const float*)ctx->raw_in.p, (float4*)ctx->pts[0].p, n, dim);
-    else
-        rc = load_points<double>(ctx, (const double*)ctx->raw_in.p, (double4*)ctx->pts[0].p, n, dim);
+    rc = by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return load_points<T>(ctx, (const T*)ctx->raw_in.p, pts_of<T>(ctx, 0), n, dim);
+    });
     if (rc) return rc;
     if (spacing->kind == WTP_SPACING_PER_POINT) {
         if ((rc = ensure(ctx, ctx->spacing_pp, ts * (size_t)n))) return rc;
@@ -1105,16 +1070,12 @@ static int relax_init_impl(wtp_ctx* ctx, const void* snap_xyz, bool on_device, i
         WTP_HIP(ctx, hipMemsetAsync(ctx->sp_hint.p, 0xFF, sizeof(int32_t) * (size_t)n, ctx->stream)); // -1: no hint
         if ((rc = ensure(ctx, ctx->sp_cert, 4 * ts * (size_t)n))) return rc;
         WTP_HIP(ctx, hipMemsetAsync(ctx->sp_cert.p, 0xFF, 4 * ts * (size_t)n, ctx->stream)); // no certificate yet
-        if (dtype == WTP_F32)
-            rc = launch_spacing_session<float>(ctx, (const float4*)ctx->pts[0].p, n, 0, ctx->kd_nodes.p, ctx->kd_m,
-                                               spacing->kind, spacing->p0, spacing->p1, spacing->p2,
-                                               (float*)ctx->spacing_pp.p, (int32_t*)ctx->sp_hint.p, nullptr, nullptr,
-                                               ctx->sp_cert.p);
-        else
-            rc = launch_spacing_session<double>(ctx, (const double4*)ctx->pts[0].p, n, 0, ctx->kd_nodes.p, ctx->kd_m,
-                                                spacing->kind, spacing->p0, spacing->p1, spacing->p2,
-                                                (double*)ctx->spacing_pp.p, (int32_t*)ctx->sp_hint.p, nullptr, nullptr,
-                                                ctx->sp_cert.p);
+        rc = by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            return launch_spacing_session<T>(ctx, pts_of<T>(ctx, 0), n, 0, ctx->kd_nodes.p, ctx->kd_m, spacing->kind,
+                                             spacing->p0, spacing->p1, spacing->p2, (T*)ctx->spacing_pp.p,
+                                             (int32_t*)ctx->sp_hint.p, nullptr, nullptr, ctx->sp_cert.p);
+        });
         if (rc) return rc;
     }
     if ((rc = sync(ctx))) return rc;
@@ -1614,8 +1575,7 @@ template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_ste
 }
 
 static int relax_step_any(wtp_ctx* ctx, int rebuild, wtp_step_stats* d_slot) {
-    return ctx->relax.dtype == WTP_F32 ? relax_step_t<float>(ctx, rebuild, d_slot)
-                                       : relax_step_t<double>(ctx, rebuild, d_slot);
+    return by_dtype(ctx->relax.dtype, [&](auto t) { return relax_step_t<decltype(t)>(ctx, rebuild, d_slot); });
 }
 int wtp::relax_step_enqueue(wtp_ctx* ctx, int rebuild, wtp_step_stats* d_slot) { return relax_step_any(ctx, rebuild, d_slot); }
 
@@ -1629,14 +1589,12 @@ int wtp::relax_prerank(wtp_ctx* ctx, int64_t n_fixed_new) {
     if (!r.active || !r.tune.valid || !r.have_tree || r.pending.active) return WTP_OK;
     if (!grid_reusable(ctx, n_fixed_new, true) || head_remeasures(r, n_fixed_new)) return WTP_OK;
     const int64_t n_new = r.n - r.n_fixed + n_fixed_new;
-    const size_t ptsz = r.dtype == WTP_F32 ? sizeof(float4) : sizeof(double4);
-    if (ctx->pts[r.bufP].cap < ptsz * (size_t)(r.n + n_fixed_new)) return WTP_OK; // (the head would be rewritten, not appended)
+    if (ctx->pts[r.bufP].cap < pt_size(r.dtype) * (size_t)(r.n + n_fixed_new)) return WTP_OK; // (the head would be rewritten, not appended)
     const int k = (int64_t)r.k_req < n_new ? r.k_req : (int)n_new;
-    if (r.dtype == WTP_F32)
-        return prerank_old_snapshot<float>(ctx, (const Pt<float>*)ctx->pts[r.bufP].p, r.n, (int32_t)r.n_fixed, n_new, r.n + n_fixed_new,
-                                           k, r.last_rho_cs, r.tune.scale);
-    return prerank_old_snapshot<double>(ctx, (const Pt<double>*)ctx->pts[r.bufP].p, r.n, (int32_t)r.n_fixed, n_new, r.n + n_fixed_new,
-                                        k, r.last_rho_cs, r.tune.scale);
+    return by_dtype(r.dtype, [&](auto t) {
+        return prerank_old_snapshot<decltype(t)>(ctx, pts_of<decltype(t)>(ctx, r.bufP), r.n, (int32_t)r.n_fixed, n_new,
+                                                 r.n + n_fixed_new, k, r.last_rho_cs, r.tune.scale);
+    });
 }
 
 // The movable set of a session is replaced as a whole (block decomposition: points migrated in and out).  The caller
@@ -1647,10 +1605,9 @@ int wtp::relax_swap_begin(wtp_ctx* ctx, int64_t n_move_new, void** d_buf_out) {
     RelaxState& r = ctx->relax;
     if (!r.active || r.pending.active) return fail(ctx, WTP_ERR_STATE, "relax_swap_begin: no session, or a pending fixed head");
     if (n_move_new < 1 || n_move_new > 2000000000LL) return fail(ctx, WTP_ERR_ARG, "relax_swap_begin: bad point count");
-    const size_t ptsz = r.dtype == WTP_F32 ? sizeof(float4) : sizeof(double4);
     const int t = pick_free(r, r.bufP, -1);
     int rc;
-    if ((rc = ensure(ctx, ctx->pts[t], ptsz * (size_t)(n_move_new + r.shard_extra)))) return rc;
+    if ((rc = ensure(ctx, ctx->pts[t], pt_size(r.dtype) * (size_t)(n_move_new + r.shard_extra)))) return rc;
     r.swap_target = t;
     *d_buf_out = ctx->pts[t].p;
     return WTP_OK;
@@ -1683,32 +1640,42 @@ int wtp::relax_swap_commit(wtp_ctx* ctx, int64_t n_move_new) {
     return WTP_OK;
 }
 
-WTP_API int wtp_relax_step(wtp_ctx* ctx, int rebuild, wtp_step_stats* stats) {
-    if (!ctx) return WTP_ERR_ARG;
-    if (!ctx->relax.active) return fail(ctx, WTP_ERR_STATE, "wtp_relax_step before wtp_relax_init");
-    WTP_HIP(ctx, hipSetDevice(ctx->device));
+// After a sweep into ctx->stats: its statistics (none wanted: just the synchronisation) and the four layer totals of every
+// axis a < n_axes that enqueue_layers was asked for (d_tot[a] != NULL; counts 0 otherwise), one read-back for all.
+static int read_step(wtp_ctx* ctx, wtp_step_stats* stats, int n_axes = 0, int32_t* const* d_tot = nullptr,
+                     int64_t* counts = nullptr) {
+    if (!stats) return sync(ctx);
+    const size_t off = (sizeof(wtp_step_stats) + 63) / 64 * 64;
     int rc;
+    if ((rc = ensure_pinned(ctx, n_axes ? off + 64 * n_axes : sizeof(wtp_step_stats)))) return rc;
+    char* h = (char*)ctx->host_pinned;
+    WTP_HIP(ctx, hipMemcpyAsync(h, ctx->stats.p, sizeof(wtp_step_stats), hipMemcpyDeviceToHost, ctx->stream));
+    for (int ax = 0; ax < n_axes; ++ax)
+        if (d_tot[ax])
+            WTP_HIP(ctx, hipMemcpyAsync(h + off + 64 * ax, d_tot[ax], 4 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = sync(ctx))) return rc;
+    memcpy(stats, h, sizeof(wtp_step_stats));
+    for (int ax = 0; ax < n_axes; ++ax)
+        for (int j = 0; j < 4; ++j) counts[4 * ax + j] = d_tot[ax] ? ((const int32_t*)(h + off + 64 * ax))[j] : 0;
+    return WTP_OK;
+}
+
+WTP_API int wtp_relax_step(wtp_ctx* ctx, int rebuild, wtp_step_stats* stats) {
+    int rc = need_session(ctx, __func__);
+    if (rc) return rc;
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
     if ((rc = ensure(ctx, ctx->stats, sizeof(wtp_step_stats)))) return rc;
     if ((rc = relax_step_any(ctx, rebuild, (wtp_step_stats*)ctx->stats.p))) return rc;
-    if (stats) {
-        if ((rc = ensure_pinned(ctx, sizeof(wtp_step_stats)))) return rc;
-        WTP_HIP(ctx, hipMemcpyAsync(ctx->host_pinned, ctx->stats.p, sizeof(wtp_step_stats), hipMemcpyDeviceToHost,
-                                    ctx->stream));
-        if ((rc = sync(ctx))) return rc;
-        memcpy(stats, ctx->host_pinned, sizeof(wtp_step_stats));
-        return WTP_OK;
-    }
-    return sync(ctx);
+    return read_step(ctx, stats);
 }
 
 WTP_API int wtp_relax_run(wtp_ctx* ctx, int n_iters, int rebuild_every, double* conv_out, wtp_step_stats* last) {
-    if (!ctx) return WTP_ERR_ARG;
-    if (!ctx->relax.active) return fail(ctx, WTP_ERR_STATE, "wtp_relax_run before wtp_relax_init");
+    int rc = need_session(ctx, __func__);
+    if (rc) return rc;
     if (rebuild_every < 1) return fail(ctx, WTP_ERR_ARG, "rebuild_every must be >= 1"); // src/repel.jl:74
     if (n_iters < 0) return fail(ctx, WTP_ERR_ARG, "n_iters must be >= 0");
     if (n_iters == 0) return WTP_OK;
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
     if ((rc = ensure(ctx, ctx->stats, sizeof(wtp_step_stats) * (size_t)n_iters))) return rc;
     wtp_step_stats* d = (wtp_step_stats*)ctx->stats.p;
     for (int i = 0; i < n_iters; ++i)
@@ -1770,9 +1737,9 @@ __global__ void stop_rules_kernel(const wtp_step_stats* __restrict__ st, StopSta
 WTP_API int wtp_relax_run_until(wtp_ctx* ctx, int max_iters, int rebuild_every, double tol, int stall_after,
                                 double cv_target, double* conv_out, int* n_done_out, int* reason_out,
                                 wtp_step_stats* last) {
-    if (!ctx) return WTP_ERR_ARG;
+    int rc = need_session(ctx, __func__);
+    if (rc) return rc;
     RelaxState& r = ctx->relax;
-    if (!r.active) return fail(ctx, WTP_ERR_STATE, "wtp_relax_run_until before wtp_relax_init");
     if (rebuild_every < 1) return fail(ctx, WTP_ERR_ARG, "rebuild_every must be >= 1"); // src/repel.jl:74
     if (max_iters < 0) return fail(ctx, WTP_ERR_ARG, "max_iters must be >= 0");
     if (r.wall_active) return fail(ctx, WTP_ERR_STATE, "wtp_relax_run_until: the octree wall rule steps through wtp_relax_step");
@@ -1780,7 +1747,6 @@ WTP_API int wtp_relax_run_until(wtp_ctx* ctx, int max_iters, int rebuild_every, 
     if (reason_out) *reason_out = 0;
     if (max_iters == 0) return WTP_OK;
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
     if ((rc = ensure(ctx, ctx->stats, sizeof(wtp_step_stats) * (size_t)max_iters))) return rc;
     if ((rc = ensure(ctx, ctx->stop_state, 64))) return rc;
     if ((rc = ensure_pinned(ctx, 64 + sizeof(wtp_step_stats) * (size_t)max_iters))) return rc;
@@ -1838,41 +1804,40 @@ WTP_API int wtp_relax_run_until(wtp_ctx* ctx, int max_iters, int rebuild_every, 
     return WTP_OK;
 }
 
+// the movable points of P in index order into d_out (device)
+static int unpermute_p(wtp_ctx* ctx, void* d_out) {
+    const RelaxState& r = ctx->relax;
+    return by_dtype(r.dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_unpermute<T>(ctx, pts_of<T>(ctx, r.bufP), r.n, r.n_fixed, r.dim, (T*)d_out);
+    });
+}
+
 WTP_API int wtp_relax_get(wtp_ctx* ctx, void* xyz_out) {
-    if (!ctx) return WTP_ERR_ARG;
+    int rc = need_session(ctx, __func__);
+    if (rc) return rc;
     RelaxState& r = ctx->relax;
-    if (!r.active) return fail(ctx, WTP_ERR_STATE, "wtp_relax_get before wtp_relax_init");
     if (!xyz_out) return fail(ctx, WTP_ERR_ARG, "xyz_out is NULL");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rcf = flush_pending(ctx)) return rcf;
+    if ((rc = flush_pending(ctx))) return rc;
     const int64_t n_move = r.n - r.n_fixed;
     if (n_move == 0) return WTP_OK;
     const size_t bytes = tsize(r.dtype) * (size_t)n_move * r.dim;
-    int rc;
     if ((rc = ensure(ctx, ctx->scratch, bytes))) return rc;
-    if (r.dtype == WTP_F32)
-        rc = launch_unpermute<float>(ctx, (const float4*)ctx->pts[r.bufP].p, r.n, r.n_fixed, r.dim, (float*)ctx->scratch.p);
-    else
-        rc = launch_unpermute<double>(ctx, (const double4*)ctx->pts[r.bufP].p, r.n, r.n_fixed, r.dim, (double*)ctx->scratch.p);
-    if (rc) return rc;
+    if ((rc = unpermute_p(ctx, ctx->scratch.p))) return rc;
     WTP_HIP(ctx, hipMemcpyAsync(xyz_out, ctx->scratch.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     return sync(ctx);
 }
 
 WTP_API int wtp_relax_get_dev(wtp_ctx* ctx, void* d_xyz_out) {
-    if (!ctx) return WTP_ERR_ARG;
+    int rc = need_session(ctx, __func__);
+    if (rc) return rc;
     RelaxState& r = ctx->relax;
-    if (!r.active) return fail(ctx, WTP_ERR_STATE, "wtp_relax_get_dev before wtp_relax_init");
     if (!d_xyz_out) return fail(ctx, WTP_ERR_ARG, "xyz_out is NULL");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rcf = flush_pending(ctx)) return rcf;
+    if ((rc = flush_pending(ctx))) return rc;
     if (r.n - r.n_fixed == 0) return WTP_OK;
-    int rc;
-    if (r.dtype == WTP_F32)
-        rc = launch_unpermute<float>(ctx, (const float4*)ctx->pts[r.bufP].p, r.n, r.n_fixed, r.dim, (float*)d_xyz_out);
-    else
-        rc = launch_unpermute<double>(ctx, (const double4*)ctx->pts[r.bufP].p, r.n, r.n_fixed, r.dim, (double*)d_xyz_out);
-    if (rc) return rc;
+    if ((rc = unpermute_p(ctx, d_xyz_out))) return rc;
     return sync(ctx);
 }
 
@@ -1892,14 +1857,11 @@ WTP_API int wtp_relax_get_point_data(wtp_ctx* ctx, void* forces_out, void* nn_di
     void* no = base + ts * n_move;
     int32_t* io = (int32_t*)(base + 2 * ts * n_move);
     // per-point arrays are in the slot order of the sweep's query buffer (== bufOld)
-    if (r.dtype == WTP_F32)
-        rc = launch_unpermute_point_data<float>(ctx, (const float4*)ctx->pts[r.bufOld].p, r.n, r.n_fixed,
-                                                (const float*)ctx->forces.p, (const float*)ctx->nn_dist.p,
-                                                (const int32_t*)ctx->nn_id.p, (float*)fo, (float*)no, io);
-    else
-        rc = launch_unpermute_point_data<double>(ctx, (const double4*)ctx->pts[r.bufOld].p, r.n, r.n_fixed,
-                                                 (const double*)ctx->forces.p, (const double*)ctx->nn_dist.p,
-                                                 (const int32_t*)ctx->nn_id.p, (double*)fo, (double*)no, io);
+    rc = by_dtype(r.dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_unpermute_point_data<T>(ctx, pts_of<T>(ctx, r.bufOld), r.n, r.n_fixed, (const T*)ctx->forces.p,
+                                              (const T*)ctx->nn_dist.p, (const int32_t*)ctx->nn_id.p, (T*)fo, (T*)no, io);
+    });
     if (rc) return rc;
     if (forces_out) WTP_HIP(ctx, hipMemcpyAsync(forces_out, fo, ts * n_move, hipMemcpyDeviceToHost, ctx->stream));
     if (nn_dist_out) WTP_HIP(ctx, hipMemcpyAsync(nn_dist_out, no, ts * n_move, hipMemcpyDeviceToHost, ctx->stream));
@@ -1907,36 +1869,39 @@ WTP_API int wtp_relax_get_point_data(wtp_ctx* ctx, void* forces_out, void* nn_di
     return sync(ctx);
 }
 
-WTP_API int wtp_relax_set(wtp_ctx* ctx, int64_t i, const void* xyz) {
-    if (!ctx) return WTP_ERR_ARG;
+// P may alias the snapshot (fresh tree): moving points by hand must not move the tree's copy, so P gets its own buffer first
+static int own_p(wtp_ctx* ctx, const char* entry) {
     RelaxState& r = ctx->relax;
-    if (!r.active) return fail(ctx, WTP_ERR_STATE, "wtp_relax_set before wtp_relax_init");
+    if (r.bufP != r.bufS) return WTP_OK;
+    const int t = pick_free(r, r.bufS, r.can_revert ? r.bufOld : -1);
+    if (t == r.bufS) return fail(ctx, WTP_ERR_STATE, std::string("no free buffer for ") + entry);
+    const size_t bytes = pt_size(r.dtype) * (size_t)r.n;
+    int rc;
+    if ((rc = ensure(ctx, ctx->pts[t], bytes))) return rc;
+    WTP_HIP(ctx, hipMemcpyAsync(ctx->pts[t].p, ctx->pts[r.bufP].p, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    if (r.bufOld == t) r.can_revert = false;
+    r.bufP = t;
+    return WTP_OK;
+}
+
+WTP_API int wtp_relax_set(wtp_ctx* ctx, int64_t i, const void* xyz) {
+    int rc = need_session(ctx, __func__);
+    if (rc) return rc;
+    RelaxState& r = ctx->relax;
     if (!xyz) return fail(ctx, WTP_ERR_ARG, "xyz is NULL");
     if (i < 0 || i >= r.n - r.n_fixed) return fail(ctx, WTP_ERR_ARG, "movable point index out of range");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rcf = flush_pending(ctx)) return rcf;
+    if ((rc = flush_pending(ctx))) return rc;
     const size_t ts = tsize(r.dtype);
-    int rc;
     if ((rc = ensure(ctx, ctx->scratch, 64))) return rc;
-    // P may alias the snapshot (fresh tree): the kick must not move the tree's copy, so give P
-    // its own buffer first.
-    if (r.bufP == r.bufS) {
-        const int t = pick_free(r, r.bufS, r.can_revert ? r.bufOld : -1);
-        if (t == r.bufS) return fail(ctx, WTP_ERR_STATE, "no free buffer for wtp_relax_set");
-        const size_t ptsz = r.dtype == WTP_F32 ? sizeof(float4) : sizeof(double4);
-        if ((rc = ensure(ctx, ctx->pts[t], ptsz * (size_t)r.n))) return rc;
-        WTP_HIP(ctx, hipMemcpyAsync(ctx->pts[t].p, ctx->pts[r.bufP].p, ptsz * (size_t)r.n, hipMemcpyDeviceToDevice,
-                                    ctx->stream));
-        if (r.bufOld == t) r.can_revert = false;
-        r.bufP = t;
-    }
+    if ((rc = own_p(ctx, __func__))) return rc;
     WTP_HIP(ctx, hipMemcpyAsync(ctx->scratch.p, xyz, ts * r.dim, hipMemcpyHostToDevice, ctx->stream));
     const int32_t id = (int32_t)(i + r.n_fixed);
     r.moved_by_hand = true;
-    if (r.dtype == WTP_F32)
-        rc = launch_set_point<float>(ctx, (float4*)ctx->pts[r.bufP].p, r.n, id, r.dim, (const float*)ctx->scratch.p);
-    else
-        rc = launch_set_point<double>(ctx, (double4*)ctx->pts[r.bufP].p, r.n, id, r.dim, (const double*)ctx->scratch.p);
+    rc = by_dtype(r.dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_set_point<T>(ctx, pts_of<T>(ctx, r.bufP), r.n, id, r.dim, (const T*)ctx->scratch.p);
+    });
     if (rc) return rc;
     return sync(ctx);
 }
@@ -1944,9 +1909,9 @@ WTP_API int wtp_relax_set(wtp_ctx* ctx, int64_t i, const void* xyz) {
 // Many movable points placed at once (the deposition pass of the octree method lands a whole layer of
 // escapees in one iteration): idx ascending, strictly increasing; one pass over the snapshot.
 WTP_API int wtp_relax_set_batch(wtp_ctx* ctx, const int64_t* idx, const void* xyz, int64_t m) {
-    if (!ctx) return WTP_ERR_ARG;
+    int rc = need_session(ctx, __func__);
+    if (rc) return rc;
     RelaxState& r = ctx->relax;
-    if (!r.active) return fail(ctx, WTP_ERR_STATE, "wtp_relax_set_batch before wtp_relax_init");
     if (m < 0) return fail(ctx, WTP_ERR_ARG, "m must be >= 0");
     if (m == 0) return WTP_OK;
     if (!idx || !xyz) return fail(ctx, WTP_ERR_ARG, "NULL array");
@@ -1957,29 +1922,19 @@ WTP_API int wtp_relax_set_batch(wtp_ctx* ctx, const int64_t* idx, const void* xy
         ids[(size_t)j] = (int32_t)(idx[j] + r.n_fixed);
     }
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rcf = flush_pending(ctx)) return rcf;
+    if ((rc = flush_pending(ctx))) return rc;
     const size_t ts = tsize(r.dtype);
-    int rc;
     const size_t o_v = (sizeof(int32_t) * (size_t)m + 255) / 256 * 256;
     if ((rc = ensure(ctx, ctx->scratch, o_v + ts * (size_t)m * r.dim))) return rc;
-    if (r.bufP == r.bufS) { // P may alias the snapshot (fresh tree): give P its own buffer first (as wtp_relax_set)
-        const int t = pick_free(r, r.bufS, r.can_revert ? r.bufOld : -1);
-        if (t == r.bufS) return fail(ctx, WTP_ERR_STATE, "no free buffer for wtp_relax_set_batch");
-        const size_t ptsz = r.dtype == WTP_F32 ? sizeof(float4) : sizeof(double4);
-        if ((rc = ensure(ctx, ctx->pts[t], ptsz * (size_t)r.n))) return rc;
-        WTP_HIP(ctx, hipMemcpyAsync(ctx->pts[t].p, ctx->pts[r.bufP].p, ptsz * (size_t)r.n, hipMemcpyDeviceToDevice,
-                                    ctx->stream));
-        if (r.bufOld == t) r.can_revert = false;
-        r.bufP = t;
-    }
+    if ((rc = own_p(ctx, __func__))) return rc;
     char* b = (char*)ctx->scratch.p;
     WTP_HIP(ctx, hipMemcpyAsync(b, ids.data(), sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
     WTP_HIP(ctx, hipMemcpyAsync(b + o_v, xyz, ts * (size_t)m * r.dim, hipMemcpyHostToDevice, ctx->stream));
     r.moved_by_hand = true;
-    rc = r.dtype == WTP_F32 ? launch_set_points<float>(ctx, (float4*)ctx->pts[r.bufP].p, r.n, (const int32_t*)b, m, r.dim,
-                                                       (const float*)(b + o_v))
-                            : launch_set_points<double>(ctx, (double4*)ctx->pts[r.bufP].p, r.n, (const int32_t*)b, m, r.dim,
-                                                        (const double*)(b + o_v));
+    rc = by_dtype(r.dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_set_points<T>(ctx, pts_of<T>(ctx, r.bufP), r.n, (const int32_t*)b, m, r.dim, (const T*)(b + o_v));
+    });
     if (rc) return rc;
     return sync(ctx); // also keeps `ids` alive until the copy has run
 }
@@ -1995,9 +1950,9 @@ WTP_API int wtp_relax_revert(wtp_ctx* ctx) {
 }
 
 WTP_API int wtp_relax_set_spacing(wtp_ctx* ctx, const void* spacing) {
-    if (!ctx) return WTP_ERR_ARG;
+    int rc = need_session(ctx, __func__);
+    if (rc) return rc;
     RelaxState& r = ctx->relax;
-    if (!r.active) return fail(ctx, WTP_ERR_STATE, "wtp_relax_set_spacing before wtp_relax_init");
     if (r.spacing_kind != WTP_SPACING_PER_POINT) return fail(ctx, WTP_ERR_STATE, "spacing is not PER_POINT");
     if (!spacing) return fail(ctx, WTP_ERR_ARG, "spacing is NULL");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
@@ -2008,9 +1963,9 @@ WTP_API int wtp_relax_set_spacing(wtp_ctx* ctx, const void* spacing) {
 }
 
 WTP_API int wtp_relax_get_spacing(wtp_ctx* ctx, void* spacing_out) {
-    if (!ctx) return WTP_ERR_ARG;
+    int rc = need_session(ctx, __func__);
+    if (rc) return rc;
     RelaxState& r = ctx->relax;
-    if (!r.active) return fail(ctx, WTP_ERR_STATE, "wtp_relax_get_spacing before wtp_relax_init");
     if (!spacing_out) return fail(ctx, WTP_ERR_ARG, "spacing_out is NULL");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t ts = tsize(r.dtype);
@@ -2058,8 +2013,7 @@ WTP_API int wtp_relax_query_knn(wtp_ctx* ctx, const void* xyz, int64_t nq, int k
     if (nq == 0) return WTP_OK;
     if (!xyz || !idx_out) return fail(ctx, WTP_ERR_ARG, "NULL array");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    return r.dtype == WTP_F32 ? relax_query_knn_t<float>(ctx, xyz, nq, k, idx_out, dist_out)
-                              : relax_query_knn_t<double>(ctx, xyz, nq, k, idx_out, dist_out);
+    return by_dtype(r.dtype, [&](auto t) { return relax_query_knn_t<decltype(t)>(ctx, xyz, nq, k, idx_out, dist_out); });
 }
 
 WTP_API int wtp_spacing_eval(wtp_ctx* ctx, const wtp_spacing_desc* spacing, const void* xyz, int64_t n, int dim,
@@ -2076,12 +2030,11 @@ WTP_API int wtp_spacing_eval(wtp_ctx* ctx, const wtp_spacing_desc* spacing, cons
     if ((rc = ensure(ctx, ctx->ins_in, ts * (size_t)n * dim))) return rc;
     if ((rc = ensure(ctx, ctx->ins_out, ts * (size_t)n))) return rc;
     WTP_HIP(ctx, hipMemcpyAsync(ctx->ins_in.p, xyz, ts * (size_t)n * dim, hipMemcpyHostToDevice, ctx->stream));
-    if (dtype == WTP_F32)
-        rc = launch_spacing_eval<float>(ctx, (const float*)ctx->ins_in.p, n, dim, ctx->kd_nodes.p, ctx->kd_m, spacing->kind,
-                                        spacing->p0, spacing->p1, spacing->p2, (float*)ctx->ins_out.p);
-    else
-        rc = launch_spacing_eval<double>(ctx, (const double*)ctx->ins_in.p, n, dim, ctx->kd_nodes.p, ctx->kd_m,
-                                         spacing->kind, spacing->p0, spacing->p1, spacing->p2, (double*)ctx->ins_out.p);
+    rc = by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_spacing_eval<T>(ctx, (const T*)ctx->ins_in.p, n, dim, ctx->kd_nodes.p, ctx->kd_m, spacing->kind,
+                                      spacing->p0, spacing->p1, spacing->p2, (T*)ctx->ins_out.p);
+    });
     if (rc) return rc;
     WTP_HIP(ctx, hipMemcpyAsync(out, ctx->ins_out.p, ts * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     return sync(ctx);
@@ -2124,14 +2077,11 @@ WTP_API int wtp_isinside_greens(wtp_ctx* ctx, const void* test_xyz, int64_t n, c
     WTP_HIP(ctx, hipMemcpyAsync(in + o_a, elem_area, ts * m, hipMemcpyHostToDevice, ctx->stream));
     uint8_t* d_inside = (uint8_t*)(out + align256(ts * n));
     int sp = span_begin(ctx, 2);
-    if (dtype == WTP_F32)
-        rc = launch_isinside_greens<float>(ctx, (const float*)in, n, (const float*)(in + o_p), (const float*)(in + o_n),
-                                           (const float*)(in + o_a), m, ctx->ins_elems.p, chunks,
-                                           (float*)ctx->ins_partial.p, (float*)out, d_inside);
-    else
-        rc = launch_isinside_greens<double>(ctx, (const double*)in, n, (const double*)(in + o_p),
-                                            (const double*)(in + o_n), (const double*)(in + o_a), m, ctx->ins_elems.p,
-                                            chunks, (double*)ctx->ins_partial.p, (double*)out, d_inside);
+    rc = by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_isinside_greens<T>(ctx, (const T*)in, n, (const T*)(in + o_p), (const T*)(in + o_n), (const T*)(in + o_a),
+                                         m, ctx->ins_elems.p, chunks, (T*)ctx->ins_partial.p, (T*)out, d_inside);
+    });
     span_end(ctx, sp);
     if (rc) return rc;
     WTP_HIP(ctx, hipMemcpyAsync(inside_out, d_inside, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
@@ -2161,13 +2111,11 @@ WTP_API int wtp_isinside_winding(wtp_ctx* ctx, const void* test_xy, int64_t n, c
     WTP_HIP(ctx, hipMemcpyAsync(in, test_xy, ts * n * 2, hipMemcpyHostToDevice, ctx->stream));
     WTP_HIP(ctx, hipMemcpyAsync(in + o_p, poly_xy, ts * m * 2, hipMemcpyHostToDevice, ctx->stream));
     uint8_t* d_inside = (uint8_t*)(out + align256(ts * n));
-    if (dtype == WTP_F32)
-        rc = launch_isinside_winding<float>(ctx, (const float*)in, n, (const float*)(in + o_p), m, chunks,
-                                            (float*)ctx->ins_partial.p, (int32_t*)ctx->ins_elems.p, (float*)out, d_inside);
-    else
-        rc = launch_isinside_winding<double>(ctx, (const double*)in, n, (const double*)(in + o_p), m, chunks,
-                                             (double*)ctx->ins_partial.p, (int32_t*)ctx->ins_elems.p, (double*)out,
-                                             d_inside);
+    rc = by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_isinside_winding<T>(ctx, (const T*)in, n, (const T*)(in + o_p), m, chunks, (T*)ctx->ins_partial.p,
+                                          (int32_t*)ctx->ins_elems.p, (T*)out, d_inside);
+    });
     if (rc) return rc;
     WTP_HIP(ctx, hipMemcpyAsync(inside_out, d_inside, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     if (sum_out) WTP_HIP(ctx, hipMemcpyAsync(sum_out, out, ts * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -2203,24 +2151,21 @@ static int enqueue_layers(wtp_ctx* ctx, int axis, double lo_in, double hi_in, do
     const bool slot_ordered = r.have_tree && r.have_point_data && axis == r.dim - 1 && r.bufP != r.bufS &&
                               !r.moved_by_hand;
     const double reach = 1.001 * r.spacing_max * (double)(r.sweeps_since_rebuild > 0 ? r.sweeps_since_rebuild : 1);
-    if (r.dtype == WTP_F32)
-        rc = launch_layers<float>(ctx, (const float4*)ctx->pts[r.bufP].p, r.n, r.n_fixed, axis, lo_in, hi_in, lo_out,
-                                  hi_out, (float4*)d_lo4, (float4*)d_hi4, cap, d_blk, d_tot, slot_ordered, reach);
-    else
-        rc = launch_layers<double>(ctx, (const double4*)ctx->pts[r.bufP].p, r.n, r.n_fixed, axis, lo_in, hi_in, lo_out,
-                                   hi_out, (double4*)d_lo4, (double4*)d_hi4, cap, d_blk, d_tot, slot_ordered, reach);
+    rc = by_dtype(r.dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_layers<T>(ctx, pts_of<T>(ctx, r.bufP), r.n, r.n_fixed, axis, lo_in, hi_in, lo_out, hi_out, (Pt<T>*)d_lo4,
+                                (Pt<T>*)d_hi4, cap, d_blk, d_tot, slot_ordered, reach);
+    });
     *d_tot_out = d_tot;
     return rc;
 }
 
 WTP_API int wtp_relax_layers_dev(wtp_ctx* ctx, int axis, double lo_in, double hi_in, double lo_out, double hi_out,
                                  void* d_lo4, void* d_hi4, int64_t cap, int64_t counts[4]) {
-    if (!ctx) return WTP_ERR_ARG;
-    RelaxState& r = ctx->relax;
-    if (!r.active) return fail(ctx, WTP_ERR_STATE, "wtp_relax_layers_dev before wtp_relax_init");
+    int rc = need_session(ctx, __func__);
+    if (rc) return rc;
     if (!counts) return fail(ctx, WTP_ERR_ARG, "counts is NULL");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
     int32_t* d_tot = nullptr;
     if ((rc = enqueue_layers(ctx, axis, lo_in, hi_in, lo_out, hi_out, d_lo4, d_hi4, cap, &d_tot))) return rc;
     if ((rc = ensure_pinned(ctx, 64))) return rc;
@@ -2235,24 +2180,15 @@ WTP_API int wtp_relax_layers_dev(wtp_ctx* ctx, int axis, double lo_in, double hi
 WTP_API int wtp_relax_step_layers(wtp_ctx* ctx, int rebuild, wtp_step_stats* stats, int axis, double lo_in, double hi_in,
                                   double lo_out, double hi_out, void* d_lo4, void* d_hi4, int64_t cap,
                                   int64_t counts[4]) {
-    if (!ctx) return WTP_ERR_ARG;
-    if (!ctx->relax.active) return fail(ctx, WTP_ERR_STATE, "wtp_relax_step_layers before wtp_relax_init");
+    int rc = need_session(ctx, __func__);
+    if (rc) return rc;
     if (!stats || !counts) return fail(ctx, WTP_ERR_ARG, "stats/counts is NULL");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
     if ((rc = ensure(ctx, ctx->stats, sizeof(wtp_step_stats)))) return rc;
     if ((rc = relax_step_any(ctx, rebuild, (wtp_step_stats*)ctx->stats.p))) return rc;
     int32_t* d_tot = nullptr;
     if ((rc = enqueue_layers(ctx, axis, lo_in, hi_in, lo_out, hi_out, d_lo4, d_hi4, cap, &d_tot))) return rc;
-    const size_t off = (sizeof(wtp_step_stats) + 63) / 64 * 64;
-    if ((rc = ensure_pinned(ctx, off + 64))) return rc;
-    WTP_HIP(ctx, hipMemcpyAsync(ctx->host_pinned, ctx->stats.p, sizeof(wtp_step_stats), hipMemcpyDeviceToHost, ctx->stream));
-    WTP_HIP(ctx, hipMemcpyAsync((char*)ctx->host_pinned + off, d_tot, 4 * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                ctx->stream));
-    if ((rc = sync(ctx))) return rc;
-    memcpy(stats, ctx->host_pinned, sizeof(wtp_step_stats));
-    for (int j = 0; j < 4; ++j) counts[j] = ((const int32_t*)((const char*)ctx->host_pinned + off))[j];
-    return WTP_OK;
+    return read_step(ctx, stats, 1, &d_tot, counts);
 }
 
 // Materialise a pending input view (wtp_relax_set_fixed_dev below): stale fixed points dropped, the
@@ -2261,21 +2197,16 @@ WTP_API int wtp_relax_step_layers(wtp_ctx* ctx, int rebuild, wtp_step_stats* sta
 static int flush_pending(wtp_ctx* ctx) {
     RelaxState& r = ctx->relax;
     if (!r.pending.active) return WTP_OK;
-    const size_t ptsz = r.dtype == WTP_F32 ? sizeof(float4) : sizeof(double4);
     int rc;
     const int t = pick_free(r, r.bufP, -1);
-    if ((rc = ensure(ctx, ctx->pts[t], ptsz * (size_t)(r.n + r.shard_extra)))) return rc;
+    if ((rc = ensure(ctx, ctx->pts[t], pt_size(r.dtype) * (size_t)(r.n + r.shard_extra)))) return rc;
     if ((rc = ensure(ctx, ctx->scratch, 64))) return rc;
     const HashView v = r.pending;
-    if (r.dtype == WTP_F32) {
-        const float4* P = (const float4*)ctx->pts[r.bufP].p;
-        rc = launch_refix<float>(ctx, P, v.n_old, v.fixed_old, r.n_fixed, P + v.n_old, (float4*)ctx->pts[t].p,
-                                 (int32_t*)ctx->scratch.p);
-    } else {
-        const double4* P = (const double4*)ctx->pts[r.bufP].p;
-        rc = launch_refix<double>(ctx, P, v.n_old, v.fixed_old, r.n_fixed, P + v.n_old, (double4*)ctx->pts[t].p,
-                                  (int32_t*)ctx->scratch.p);
-    }
+    rc = by_dtype(r.dtype, [&](auto tt) {
+        using T = decltype(tt);
+        const Pt<T>* P = pts_of<T>(ctx, r.bufP);
+        return launch_refix<T>(ctx, P, v.n_old, v.fixed_old, r.n_fixed, P + v.n_old, pts_of<T>(ctx, t), (int32_t*)ctx->scratch.p);
+    });
     if (rc) return rc;
     r.bufP = t;
     r.pending.active = false;
@@ -2284,20 +2215,19 @@ static int flush_pending(wtp_ctx* ctx) {
 
 // (keep_alive: the caller's array stays valid until the copy has run in stream order — the block driver's own pool)
 int wtp::relax_set_fixed_dev_impl(wtp_ctx* ctx, const void* d_fixed4, int64_t n_fixed_new, bool keep_alive) {
-    if (!ctx) return WTP_ERR_ARG;
+    int rc = need_session(ctx, "wtp_relax_set_fixed_dev");
+    if (rc) return rc;
     RelaxState& r = ctx->relax;
-    if (!r.active) return fail(ctx, WTP_ERR_STATE, "wtp_relax_set_fixed_dev before wtp_relax_init");
     if (r.spacing_kind == WTP_SPACING_PER_POINT)
         return fail(ctx, WTP_ERR_STATE, "wtp_relax_set_fixed_dev: not with a caller-evaluated (PER_POINT) spacing array");
     if (n_fixed_new < 0 || (n_fixed_new > 0 && !d_fixed4)) return fail(ctx, WTP_ERR_ARG, "bad fixed-point array");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
     if ((rc = flush_pending(ctx))) return rc; // two calls in a row: the first one's view is materialised
     const int64_t n_move = r.n - r.n_fixed, n_new = n_move + n_fixed_new;
     if (n_new < 1) return fail(ctx, WTP_ERR_ARG, "the snapshot would be empty");
     if (n_new > 2000000000LL) return fail(ctx, WTP_ERR_ARG, "n exceeds the int32 index space");
     const size_t ts = tsize(r.dtype);
-    const size_t ptsz = r.dtype == WTP_F32 ? sizeof(float4) : sizeof(double4);
+    const size_t ptsz = pt_size(r.dtype);
     // from now on the point buffers keep room for a replaced head next to the old one
     const int64_t extra = n_fixed_new + n_fixed_new / 4 + 4096;
     if (extra > r.shard_extra) r.shard_extra = extra;
@@ -2320,12 +2250,10 @@ int wtp::relax_set_fixed_dev_impl(wtp_ctx* ctx, const void* d_fixed4, int64_t n_
         // build reads the array through a view that drops the stale fixed points and renumbers the
         // rest (HashView; 0.16 ms per iteration saved at 11 M points against rewriting the array).
         if (n_fixed_new > 0) {
-            if (r.dtype == WTP_F32)
-                rc = launch_append_fixed<float>(ctx, (const float4*)d_fixed4, n_fixed_new,
-                                                (float4*)ctx->pts[r.bufP].p + r.n);
-            else
-                rc = launch_append_fixed<double>(ctx, (const double4*)d_fixed4, n_fixed_new,
-                                                 (double4*)ctx->pts[r.bufP].p + r.n);
+            rc = by_dtype(r.dtype, [&](auto t) {
+                using T = decltype(t);
+                return launch_append_fixed<T>(ctx, (const Pt<T>*)d_fixed4, n_fixed_new, pts_of<T>(ctx, r.bufP) + r.n);
+            });
             if (rc) return rc;
         }
         r.pending.active = true;
@@ -2336,12 +2264,11 @@ int wtp::relax_set_fixed_dev_impl(wtp_ctx* ctx, const void* d_fixed4, int64_t n_
     } else { // first call of a session (buffers sized for the plain snapshot): rewrite once
         const int t = pick_free(r, r.bufP, -1);
         if ((rc = ensure(ctx, ctx->pts[t], ptsz * (size_t)(n_new + r.shard_extra)))) return rc;
-        if (r.dtype == WTP_F32)
-            rc = launch_refix<float>(ctx, (const float4*)ctx->pts[r.bufP].p, r.n, r.n_fixed, n_fixed_new,
-                                     (const float4*)d_fixed4, (float4*)ctx->pts[t].p, (int32_t*)ctx->scratch.p);
-        else
-            rc = launch_refix<double>(ctx, (const double4*)ctx->pts[r.bufP].p, r.n, r.n_fixed, n_fixed_new,
-                                      (const double4*)d_fixed4, (double4*)ctx->pts[t].p, (int32_t*)ctx->scratch.p);
+        rc = by_dtype(r.dtype, [&](auto tt) {
+            using T = decltype(tt);
+            return launch_refix<T>(ctx, pts_of<T>(ctx, r.bufP), r.n, r.n_fixed, n_fixed_new, (const Pt<T>*)d_fixed4,
+                                   pts_of<T>(ctx, t), (int32_t*)ctx->scratch.p);
+        });
         if (rc) return rc;
         r.bufP = t;
     }
@@ -2363,9 +2290,8 @@ WTP_API int wtp_relax_set_fixed_dev(wtp_ctx* ctx, const void* d_fixed4, int64_t 
 }
 
 WTP_API int wtp_relax_set_coverage(wtp_ctx* ctx, int axis, double lo, double hi) {
-    if (!ctx) return WTP_ERR_ARG;
+    if (int rc = need_session(ctx, __func__)) return rc;
     RelaxState& r = ctx->relax;
-    if (!r.active) return fail(ctx, WTP_ERR_STATE, "wtp_relax_set_coverage before wtp_relax_init");
     if (axis >= r.dim) return fail(ctx, WTP_ERR_ARG, "axis must be < dim (negative: unlimited)");
     if (axis >= 0 && !(lo <= hi)) return fail(ctx, WTP_ERR_ARG, "need lo <= hi");
     r.cover_axis = axis < 0 ? -1 : axis;
@@ -2380,12 +2306,11 @@ WTP_API int wtp_relax_set_coverage(wtp_ctx* ctx, int axis, double lo, double hi)
 WTP_API int wtp_relax_step_layers3(wtp_ctx* ctx, int rebuild, wtp_step_stats* stats, int axes_mask, const double lo_in[3],
                                    const double hi_in[3], const double lo_out[3], const double hi_out[3], void* const d_lo4[3],
                                    void* const d_hi4[3], int64_t cap, int64_t counts[12]) {
-    if (!ctx) return WTP_ERR_ARG;
-    if (!ctx->relax.active) return fail(ctx, WTP_ERR_STATE, "wtp_relax_step_layers3 before wtp_relax_init");
+    int rc = need_session(ctx, __func__);
+    if (rc) return rc;
     if (!stats || !counts || !lo_in || !hi_in || !lo_out || !hi_out || !d_lo4 || !d_hi4)
         return fail(ctx, WTP_ERR_ARG, "NULL argument");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
     if ((rc = ensure(ctx, ctx->stats, sizeof(wtp_step_stats)))) return rc;
     if ((rc = relax_step_any(ctx, rebuild, (wtp_step_stats*)ctx->stats.p))) return rc;
     int32_t* d_tot[3] = {nullptr, nullptr, nullptr};
@@ -2394,25 +2319,13 @@ WTP_API int wtp_relax_step_layers3(wtp_ctx* ctx, int rebuild, wtp_step_stats* st
             if ((rc = enqueue_layers(ctx, ax, lo_in[ax], hi_in[ax], lo_out[ax], hi_out[ax], d_lo4[ax], d_hi4[ax], cap,
                                      &d_tot[ax], ax)))
                 return rc;
-    const size_t off = (sizeof(wtp_step_stats) + 63) / 64 * 64;
-    if ((rc = ensure_pinned(ctx, off + 3 * 64))) return rc;
-    WTP_HIP(ctx, hipMemcpyAsync(ctx->host_pinned, ctx->stats.p, sizeof(wtp_step_stats), hipMemcpyDeviceToHost, ctx->stream));
-    for (int ax = 0; ax < 3; ++ax)
-        if (d_tot[ax])
-            WTP_HIP(ctx, hipMemcpyAsync((char*)ctx->host_pinned + off + 64 * ax, d_tot[ax], 4 * sizeof(int32_t),
-                                        hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = sync(ctx))) return rc;
-    memcpy(stats, ctx->host_pinned, sizeof(wtp_step_stats));
-    for (int ax = 0; ax < 3; ++ax)
-        for (int j = 0; j < 4; ++j)
-            counts[4 * ax + j] = d_tot[ax] ? ((const int32_t*)((const char*)ctx->host_pinned + off + 64 * ax))[j] : 0;
-    return WTP_OK;
+    return read_step(ctx, stats, 3, d_tot, counts);
 }
 
 WTP_API int wtp_relax_set_coverage_box(wtp_ctx* ctx, const double lo[3], const double hi[3]) {
     if (!ctx || !lo || !hi) return WTP_ERR_ARG;
+    if (int rc = need_session(ctx, __func__)) return rc;
     RelaxState& r = ctx->relax;
-    if (!r.active) return fail(ctx, WTP_ERR_STATE, "wtp_relax_set_coverage_box before wtp_relax_init");
     for (int ax = 0; ax < 3; ++ax) {
         if (!(lo[ax] <= hi[ax])) return fail(ctx, WTP_ERR_ARG, "need lo <= hi on every axis");
         r.cover_lo3[ax] = lo[ax];

@@ -79,11 +79,7 @@ void block_destroy(wtp_ctx* ctx) {
     BlockState* b = bs_of(ctx);
     if (!b) return;
     hipSetDevice(ctx->device);
-    DevBuf* bufs[] = {&b->flags, &b->span_counts, &b->totals, &b->send, &b->send_mig, &b->gid[0], &b->gid[1], &b->pool,
-                      &b->recv_mig, &b->gsend, &b->grecv, &b->lost};
-    for (DevBuf* d : bufs)
-        if (d->p) hipFree(d->p);
-    delete b;
+    delete b; // (frees the device buffers)
     ctx->block = nullptr;
 }
 

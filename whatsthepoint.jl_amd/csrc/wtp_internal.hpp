@@ -24,6 +24,9 @@ template <> struct PtOf<float> { using type = float4; };
 template <> struct PtOf<double> { using type = double4; };
 template <typename T> using Pt = typename PtOf<T>::type;
 
+// One call for both dtypes: f(float{}) for WTP_F32, f(double{}) for WTP_F64; f takes `auto t` and works on T = decltype(t).
+template <typename F> inline auto by_dtype(int dtype, F&& f) { return dtype == WTP_F32 ? f(float{}) : f(double{}); }
+
 __host__ __device__ inline float id_to_w(float, int32_t id) { return __builtin_bit_cast(float, id); }
 __host__ __device__ inline double id_to_w(double, int32_t id) {
     return __builtin_bit_cast(double, (int64_t)id);
@@ -166,10 +169,25 @@ template <typename T> struct SearchArgs {
     unsigned long long* diag;  // -DWTP_DIAG builds: per-phase wave-cycle sums (8 slots), else unused
 };
 
-// ---- device buffer with capacity -----------------------------------------------------------------
+// ---- device buffer with capacity: grown by ensure(), freed with its owner ------------------------
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) {
+        o.p = nullptr;
+        o.cap = 0;
+    }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+        return *this;
+    }
+    ~DevBuf() {
+        if (p) hipFree(p);
+    }
 };
 
 // Input view of a hash build whose input array still holds stale fixed points and has the new
@@ -388,6 +406,8 @@ int ensure_pinned(wtp_ctx* ctx, size_t bytes); // the context's page-locked stag
     } while (0)
 
 int ensure(wtp_ctx* ctx, DevBuf& b, size_t bytes);
+template <typename T> Pt<T>* pts_of(wtp_ctx* ctx, int i) { return (Pt<T>*)ctx->pts[i].p; } // point buffer i as Pt<T>
+int need_session(wtp_ctx* ctx, const char* entry); // guard of the relax entry points: a context with an active session
 // sets the kernel's dynamic-LDS limit once per (context, kernel, size) and returns the blocks per CU it can hold
 int launch_occupancy_of(wtp_ctx* ctx, const void* fn, int threads, size_t smem);
 

@@ -822,27 +822,17 @@ WTP_API int wtp_mesh_query(wtp_ctx* ctx, const void* xyz, int64_t n, int dtype, 
     if ((rc = ensure(ctx, ctx->mesh_io, o_in + (size_t)n))) return rc;
     char* b = (char*)ctx->mesh_io.p;
     WTP_HIP(ctx, hipMemcpyAsync(b, xyz, ts * n * 3, hipMemcpyHostToDevice, ctx->stream));
+    int32_t* tri = tri_out ? (int32_t*)(b + o_tr) : nullptr;
+    uint8_t* inside = inside_out ? (uint8_t*)(b + o_in) : nullptr;
     int sp = span_begin(ctx, 2);
-    if (dtype == WTP_F32) {
-        float *sd = sd_out ? (float*)(b + o_sd) : nullptr, *cp = closest_out ? (float*)(b + o_cp) : nullptr,
-              *pr = projected_out ? (float*)(b + o_pr) : nullptr;
-        rc = ctx->mesh_dtype == WTP_F32
-                 ? launch_mesh_query<float, float>(ctx, (const float*)b, n, offset, sd, tri_out ? (int32_t*)(b + o_tr) : nullptr,
-                                                   cp, inside_out ? (uint8_t*)(b + o_in) : nullptr, pr)
-                 : launch_mesh_query<double, float>(ctx, (const float*)b, n, offset, sd,
-                                                    tri_out ? (int32_t*)(b + o_tr) : nullptr, cp,
-                                                    inside_out ? (uint8_t*)(b + o_in) : nullptr, pr);
-    } else {
-        double *sd = sd_out ? (double*)(b + o_sd) : nullptr, *cp = closest_out ? (double*)(b + o_cp) : nullptr,
-               *pr = projected_out ? (double*)(b + o_pr) : nullptr;
-        rc = ctx->mesh_dtype == WTP_F32
-                 ? launch_mesh_query<float, double>(ctx, (const double*)b, n, offset, sd,
-                                                    tri_out ? (int32_t*)(b + o_tr) : nullptr, cp,
-                                                    inside_out ? (uint8_t*)(b + o_in) : nullptr, pr)
-                 : launch_mesh_query<double, double>(ctx, (const double*)b, n, offset, sd,
-                                                     tri_out ? (int32_t*)(b + o_tr) : nullptr, cp,
-                                                     inside_out ? (uint8_t*)(b + o_in) : nullptr, pr);
-    }
+    rc = by_dtype(dtype, [&](auto tp) { // the points' dtype, then the mesh's
+        using TP = decltype(tp);
+        TP *sd = sd_out ? (TP*)(b + o_sd) : nullptr, *cp = closest_out ? (TP*)(b + o_cp) : nullptr,
+           *pr = projected_out ? (TP*)(b + o_pr) : nullptr;
+        return by_dtype(ctx->mesh_dtype, [&](auto tm) {
+            return launch_mesh_query<decltype(tm), TP>(ctx, (const TP*)b, n, offset, sd, tri, cp, inside, pr);
+        });
+    });
     span_end(ctx, sp);
     if (rc) return rc;
     if (sd_out) WTP_HIP(ctx, hipMemcpyAsync(sd_out, b + o_sd, ts * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -859,15 +849,14 @@ WTP_API int wtp_mesh_query(wtp_ctx* ctx, const void* xyz, int64_t n, int dtype, 
 // is followed by _constrain_octree (src/repel.jl:448-469).  Movable points with index below
 // n_boundary (counted from the first movable one) start as boundary points.
 WTP_API int wtp_relax_set_wall(wtp_ctx* ctx, int64_t n_boundary, double offset_dist) {
-    if (!ctx) return WTP_ERR_ARG;
+    int rc = need_session(ctx, __func__);
+    if (rc) return rc;
     RelaxState& r = ctx->relax;
-    if (!r.active) return fail(ctx, WTP_ERR_STATE, "wtp_relax_set_wall before wtp_relax_init");
     if (ctx->mesh_nt < 1) return fail(ctx, WTP_ERR_STATE, "no mesh: call wtp_mesh_set first");
     if (r.dim != 3) return fail(ctx, WTP_ERR_ARG, "the wall rule is 3-D only (src/repel.jl:122)");
     const int64_t nm = r.n - r.n_fixed;
     if (n_boundary < 0 || n_boundary > nm) return fail(ctx, WTP_ERR_ARG, "n_boundary out of range");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
     // wall_flags: [is_bnd nm | escaped nm | counter (int32, 256-aligned)]; wall_tri: int32 nm, -1 = none
     const size_t o_cnt = al256(2 * (size_t)nm);
     if ((rc = ensure(ctx, ctx->wall_flags, o_cnt + 256))) return rc;
