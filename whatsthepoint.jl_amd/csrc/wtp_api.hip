@@ -469,14 +469,14 @@ static int knn_dev_t(wtp_ctx* ctx, const T* d_xyz, int64_t n, int dim, int k, in
     return rc;
 }
 
-// fp32 k-nearest candidates of a double4 cloud (knn_dev_f64, relax_f64_ksel_sweep): the cloud moved to its own origin
-// (*org4_out) and rounded to float by to_local(org4, raw32), hashed with the tuning cached in t, relabel(sorted32) run on
-// the sorted float copy, then the kc nearest per query (self included) into cand_idx / cand_dist, on the x-slowest layout
-// of wtp_ksel.hip where that applies (3-D, kc <= 24).  `b` comes with the caller's counter block; `sp`, the caller's
+// fp32 k-nearest candidates of a double4 cloud (knn_dev_f64, relax_f64_ksel_sweep; kernels in wtp_sweep64.hip): the cloud
+// (w = its row) moved to its own origin (*org4_out) and rounded to float, hashed with the tuning cached in t, relabel(sorted32)
+// run on the sorted float copy, then the kc nearest per query (self included) into cand_idx / cand_dist, on the x-slowest
+// layout of wtp_ksel.hip where that applies (3-D, kc <= 24).  `b` comes with the caller's counter block; `sp`, the caller's
 // hash span, is closed and the search span left open.
-template <typename ToLocal, typename Relabel>
+template <typename Relabel>
 static int f64_candidates(wtp_ctx* ctx, const double4* pts, int64_t n, int dim, int kc, GridTune& t, SearchArgs<float>& b,
-                          int& sp, const double** org4_out, ToLocal to_local, Relabel relabel) {
+                          int& sp, const double** org4_out, Relabel relabel) {
     int rc;
     if ((rc = ensure(ctx, ctx->f32_pts, 2 * sizeof(float4) * (size_t)n))) return rc;
     if ((rc = ensure(ctx, ctx->cand_idx, sizeof(int32_t) * (size_t)n * kc))) return rc;
@@ -487,7 +487,7 @@ static int f64_candidates(wtp_ctx* ctx, const double4* pts, int64_t n, int dim, 
     double* org4 = (double*)ctx->occ.p + 4; // behind the occupancy counters
     *org4_out = org4;
     if ((rc = launch_origin(ctx, pts, n, org4))) return rc;
-    if ((rc = to_local(org4, raw32))) return rc;
+    if ((rc = launch_to_local_f32(ctx, pts, n, org4, raw32))) return rc;
     const bool ksel = dim == 3 && ctx->ksel && kc <= ksel_kmax() && n >= 4096;
     ctx->topology_build = true; // rows are ordered by (d2, id) explicitly: no canonical-order pass
     rc = build_grid_cached<float>(ctx, t, raw32, sorted32, n, dim, kc, ksel);
@@ -544,10 +544,9 @@ static int knn_dev_f64(wtp_ctx* ctx, const double* d_xyz, int64_t n, int dim, in
     a.fb2_list = (int32_t*)ctx->fb2_list.p;
     a.fb2_count = (int32_t*)ctx->fb2_count.p;
     const double* org4 = nullptr;
-    rc = f64_candidates(
-        ctx, raw64, n, dim, kc, ctx->knn64_tune, a, sp, &org4,
-        [&](const double* o, float4* raw32) { return launch_to_local_f32(ctx, raw64, n, o, raw32); },
-        [&](float4* sorted32) { return slots ? launch_relabel_slots(ctx, raw64, sorted32, slot64, n) : WTP_OK; });
+    rc = f64_candidates(ctx, raw64, n, dim, kc, ctx->knn64_tune, a, sp, &org4, [&](float4* sorted32) {
+        return slots ? launch_relabel_slots(ctx, raw64, sorted32, slot64, nullptr, n) : WTP_OK;
+    });
     if (rc) return rc;
     // kept: the next fp32 call measures its cloud afresh, not with a scale measured before this call on a cloud of that size
     ctx->knn_tune.valid = false;
@@ -1226,12 +1225,9 @@ static int relax_f64_ksel_sweep(wtp_ctx* ctx, SearchArgs<double>& a, int* sp) {
     const void* ncells_session = ctx->ncells_dev;
     const bool box_session = ctx->box_active; // (a clipped box is in the session's coordinates)
     const double* org4 = nullptr;
-    rc = f64_candidates(
-        ctx, snap, n, 3, kc, r.f64k_tune, b, *sp, &org4,
-        [&](const double* o, float4* raw32) { return launch_f64k_local(ctx, snap, n, o, raw32); },
-        [&](float4* sorted32) {
-            return launch_f64k_relabel(ctx, snap, sorted32, (int32_t*)ctx->f64k_slot.p, (double4*)ctx->f64k_s64.p, n);
-        });
+    rc = f64_candidates(ctx, snap, n, 3, kc, r.f64k_tune, b, *sp, &org4, [&](float4* sorted32) {
+        return launch_relabel_slots(ctx, snap, sorted32, (double4*)ctx->f64k_s64.p, (int32_t*)ctx->f64k_slot.p, n);
+    });
     // the session's structures again (the float copy's stay where they are until the next sweep overwrites them)
     std::swap(ctx->grid, ctx->grid_b);
     std::swap(ctx->cell_start, ctx->cell_start_b);

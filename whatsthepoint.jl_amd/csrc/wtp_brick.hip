@@ -70,16 +70,7 @@ struct BrickSmem {
         k[j] = hi_;                          \
     }
 
-// ring entries are byte offsets into the staged point area (< 64 KiB)
-__device__ inline float4 lds_pt(const float4* pts, uint32_t byte_off) {
-    return *reinterpret_cast<const float4*>(reinterpret_cast<const unsigned char*>(pts) + byte_off);
-}
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-// SCAN_U consecutive staged points in one go: explicit ds_read_b128 (the compiler would shrink
-// the loads to b96 when .w is unused, which costs twice the LDS cycles per instruction) and a
-// single wait.  The wait is inside the statement, so the outputs are valid when it returns.
+// SCAN_U consecutive staged points in one go: the eight-point form of lds_read_group (wtp_device.hpp)
 __device__ inline void lds_read_group(f4 (&c)[8], uint32_t addr) {
     asm volatile(
         "ds_read_b128 %0, %8\n\t"
@@ -95,21 +86,6 @@ __device__ inline void lds_read_group(f4 (&c)[8], uint32_t addr) {
         : "v"(addr)
         : "memory");
 }
-
-__device__ inline void lds_read_group(f4 (&c)[4], uint32_t addr) {
-    asm volatile(
-        "ds_read_b128 %0, %4\n\t"
-        "ds_read_b128 %1, %4 offset:16\n\t"
-        "ds_read_b128 %2, %4 offset:32\n\t"
-        "ds_read_b128 %3, %4 offset:48\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(c[0]), "=&v"(c[1]), "=&v"(c[2]), "=&v"(c[3])
-        : "v"(addr)
-        : "memory");
-}
-
-__device__ inline uint32_t f2u(float f) { return __builtin_bit_cast(uint32_t, f); }
-__device__ inline float u2f(uint32_t u) { return __builtin_bit_cast(float, u); }
 
 // Sort this lane's ring keys (d2 recomputed from the staged points); return the k-th smallest
 // (index K-1) and the next one (index K).  KT > 0: K is the compile-time KT.
@@ -196,32 +172,6 @@ __device__ inline void ring_compact(const float4* __restrict__ pts, uint16_t* __
         keep += ok ? 1 : 0;
     }
     cnt = keep;
-}
-
-// Fast-math force law for the brick path (1-ulp rcp; the wave kernel keeps the IEEE forms).
-// Laws 0..2 are one branch-free expression  max((A - B*u2) / (u2+beta)^2, lo)  with
-// (A,B,lo) = (1,0,-inf) inverse distance, (1,1,-inf) equilibrium, (u0^2,1,0) clipped; law 3 swaps the
-// denominator for (u2+beta)^gamma.  u2 = d2/s^2.
-struct ForceCoef {
-    float A, B, lo, beta, gamma;
-    int strong;
-};
-__device__ inline ForceCoef force_coef(int kind, float beta, float u0, float gamma) {
-    ForceCoef c;
-    c.A = kind == WTP_FORCE_CLIPPED_SPACING ? u0 * u0 : 1.f;
-    c.B = kind == WTP_FORCE_INVERSE_DISTANCE ? 0.f : 1.f;
-    c.lo = kind == WTP_FORCE_CLIPPED_SPACING ? 0.f : -Lim<float>::inf();
-    c.beta = beta;
-    c.gamma = gamma;
-    c.strong = kind == WTP_FORCE_STRONG_SPACING;
-    return c;
-}
-__device__ inline float force_fast(const ForceCoef& c, float u2) {
-    const float d = u2 + c.beta;
-    float inv = __builtin_amdgcn_rcpf(d * d);
-    if (c.strong) inv = __builtin_amdgcn_exp2f(-c.gamma * __builtin_amdgcn_logf(d)); // wave-uniform
-    const float f = (c.A - c.B * u2) * inv;
-    return f > c.lo ? f : c.lo;
 }
 
 // Visitor of the sweep's final key pass.  Two things never depend on the k-th cut: the nearest

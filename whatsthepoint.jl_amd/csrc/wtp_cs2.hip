@@ -72,8 +72,6 @@ struct Cs2Smem {
     Acc acc[kCsThreads / 64];
 };
 
-typedef float cs_f4 __attribute__((ext_vector_type(4)));
-
 // Per-lane statistics in 9 registers instead of Acc's 14 (same values: a float compared as float or as the
 // double it converts to orders the same; the sums stay in double like acc_point's)
 struct CsAcc {
@@ -117,36 +115,12 @@ __device__ inline void cs_acc_point(CsAcc& c, float force, float nd, float s, in
     }
 }
 
-// ClippedSpacingForce (src/repel_forces.jl:96-100) on u2 = d2 / s^2, fast reciprocal (1 ulp), the same
-// expression as brick_kernel's force_fast with (A, B, lo) = (u0^2, 1, 0)
+// ClippedSpacingForce's coefficients (u0^2, beta) for cs2_kernel's force pass, which evaluates the law in its own
+// rsq form.  Kept apart from ForceCoef (wtp_device.hpp): taking them from force_coef reorders the kernel's code.
 struct ForceCoefCs {
     float A, beta;
 };
 __device__ inline ForceCoefCs force_coef_cs(float beta, float u0) { return ForceCoefCs{u0 * u0, beta}; }
-__device__ inline float force_fast_cs(const ForceCoefCs& c, float u2) {
-    const float d = u2 + c.beta;
-    const float inv = __builtin_amdgcn_rcpf(d * d);
-    const float f = (c.A - u2) * inv;
-    return f > 0.f ? f : 0.f;
-}
-
-// four consecutive staged points: explicit ds_read_b128 (the compiler would shrink the loads to b96 when .w
-// is unused, which costs twice the LDS cycles per instruction) and a single wait
-template <int OFF> __device__ inline void cs_read_group(cs_f4 (&c)[4], uint32_t addr) {
-    asm volatile(
-        "ds_read_b128 %0, %4 offset:%5\n\t"
-        "ds_read_b128 %1, %4 offset:%6\n\t"
-        "ds_read_b128 %2, %4 offset:%7\n\t"
-        "ds_read_b128 %3, %4 offset:%8\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(c[0]), "=&v"(c[1]), "=&v"(c[2]), "=&v"(c[3])
-        : "v"(addr), "n"(OFF), "n"(OFF + 16), "n"(OFF + 32), "n"(OFF + 48)
-        : "memory");
-}
-
-__device__ inline float4 cs_pt(const unsigned char* base, uint32_t byte_off) {
-    return *reinterpret_cast<const float4*>(base + byte_off);
-}
 
 static size_t cs2_smem_bytes(int hcap) {
     return (size_t)hcap * 16 + kCsPadBytes + sizeof(Cs2Smem);
@@ -510,7 +484,7 @@ __global__ __launch_bounds__(kCsThreads, 4) void cs2_kernel(SearchArgs<float> a,
                 // same registers) as soon as its three subtractions have consumed it, and a use waits only for ITS read
                 // (LDS returns in order: `lgkmcnt(3)` = everything but the three youngest reads has landed).  The wave no
                 // longer drains the LDS queue before every group of four.
-                cs_f4 c[4];
+                f4 c[4];
                 uint32_t pa = pa0;
                 uint32_t addr = lds_base + pa0;
                 asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:16\n\tds_read_b128 %2, %4 offset:32\n\tds_read_b128 %3, %4 offset:48"
@@ -605,7 +579,7 @@ __global__ __launch_bounds__(kCsThreads, 4) void cs2_kernel(SearchArgs<float> a,
                     asm("v_ffbh_u32 %0, %1" : "=v"(l2) : "v"(mw));
                     const uint32_t o2 = v2 ? base_w + (l2 << 4) : qoff;
                     mw &= ~(0x80000000u >> (l2 & 31u));
-                    const float4 c1 = cs_pt(smem_raw, o1), c2 = cs_pt(smem_raw, o2);
+                    const float4 c1 = lds_pt(smem_raw, o1), c2 = lds_pt(smem_raw, o2);
                     visit(c1);
                     visit(c2);
                 }
@@ -630,7 +604,7 @@ __global__ __launch_bounds__(kCsThreads, 4) void cs2_kernel(SearchArgs<float> a,
                     uint32_t o1, o2;
                     take(o1);
                     take(o2);
-                    const float4 c1 = cs_pt(smem_raw, o1), c2 = cs_pt(smem_raw, o2);
+                    const float4 c1 = lds_pt(smem_raw, o1), c2 = lds_pt(smem_raw, o2);
                     visit(c1);
                     visit(c2);
                 }
@@ -698,11 +672,11 @@ __global__ __launch_bounds__(kCsThreads, 4) void cs2_kernel(SearchArgs<float> a,
             const int nm = __builtin_amdgcn_readfirstlane(sm->miss_n[wave]);
             for (int m = 0; m < nm; ++m) {
                 const CsMiss e = sm->miss[wave][m];
-                const float4 qp = cs_pt(smem_raw, e.qoff);
+                const float4 qp = lds_pt(smem_raw, e.qoff);
                 float bd = Lim<float>::inf();
                 int32_t bi = 0x7FFFFFFF;
                 for (uint32_t p = e.pa + (uint32_t)lane * 16u; p < e.ea; p += 64u * 16u) {
-                    const float4 c = cs_pt(smem_raw, p);
+                    const float4 c = lds_pt(smem_raw, p);
                     const int32_t cid = w_to_id(c.w);
                     const float d = dist2<float>(qp.x, qp.y, qp.z, c.x, c.y, c.z);
                     if (cid != e.qid && lex_lt(d, cid, bd, bi)) {
@@ -929,7 +903,7 @@ __global__ __launch_bounds__(kBallThreads, 6) void cs_ball_kernel(SearchArgs<flo
     const int lane = threadIdx.x & 63;
     const int grp = lane / kBallLanes, l16 = lane % kBallLanes; // (l16: the lane's index inside its query's group)
     const int wave_g = (blockIdx.x * kBallThreads + threadIdx.x) >> 6, nwaves = (gridDim.x * kBallThreads) >> 6;
-    const ForceCoefCs fc = force_coef_cs(a.beta, a.u0);
+    const ForceCoef fc = force_coef(WTP_FORCE_CLIPPED_SPACING, a.beta, a.u0, 0.f);
     Acc acc = acc_empty();
     for (int i0 = wave_g * kBallPerWave; i0 < n; i0 += nwaves * kBallPerWave) {
         const int i = i0 + grp;
@@ -983,7 +957,7 @@ __global__ __launch_bounds__(kBallThreads, 6) void cs_ball_kernel(SearchArgs<flo
             nd2 = nearer ? d : nd2;
             nid = nearer ? cid : nid;
             const bool act = inl && other;
-            const float f = force_fast_cs(fc, d * inv_s2);
+            const float f = force_fast(fc, d * inv_s2);
             const float coef = (act && d > 0.f) ? f * __builtin_amdgcn_rsqf(d) : 0.f;
             Fx = __builtin_fmaf(coef, dx, Fx);
             Fy = __builtin_fmaf(coef, dy, Fy);

@@ -1,6 +1,7 @@
 // wtp_device.hpp — device functions shared by the generic and the brick kernels.
-// Arithmetic restates the reference expressions term by term (file:line cited per function);
-// the translation units are compiled with -ffp-contract=off so no FMA is formed.
+// Arithmetic restates the reference expressions term by term (file:line cited per function) in IEEE
+// operations, but for the fast-math section at the end; the translation units are compiled with
+// -ffp-contract=off so no FMA is formed.
 #pragma once
 #include "wtp_internal.hpp"
 
@@ -316,6 +317,60 @@ __device__ inline void reduce_partials_block(const Partial* __restrict__ parts, 
     }
     __syncthreads();
     if (counters && threadIdx.x < 16) counters[threadIdx.x] = 0;
+}
+
+// ---- fast-math (1-ulp) helpers of the fp32 fast paths (wtp_brick.hip, wtp_cs2.hip, wtp_ksel.hip) ----
+// Not IEEE: the hardware's 1-ulp reciprocal, log and exp.  One copy, so every fast path evaluates the same expression.
+
+typedef float f4 __attribute__((ext_vector_type(4)));
+
+__device__ inline uint32_t f2u(float f) { return __builtin_bit_cast(uint32_t, f); }
+__device__ inline float u2f(uint32_t u) { return __builtin_bit_cast(float, u); }
+
+// a staged point in LDS at a byte offset from the staging area's start (offsets < 64 KiB)
+__device__ inline float4 lds_pt(const void* base, uint32_t byte_off) {
+    return *reinterpret_cast<const float4*>(reinterpret_cast<const unsigned char*>(base) + byte_off);
+}
+
+// four consecutive staged points: explicit ds_read_b128 (the compiler would shrink the loads to b96
+// when .w is unused, which costs twice the LDS cycles per instruction) and a single wait.  The wait
+// is inside the statement, so the outputs are valid when it returns.
+__device__ inline void lds_read_group(f4 (&c)[4], uint32_t addr) {
+    asm volatile(
+        "ds_read_b128 %0, %4\n\t"
+        "ds_read_b128 %1, %4 offset:16\n\t"
+        "ds_read_b128 %2, %4 offset:32\n\t"
+        "ds_read_b128 %3, %4 offset:48\n\t"
+        "s_waitcnt lgkmcnt(0)"
+        : "=&v"(c[0]), "=&v"(c[1]), "=&v"(c[2]), "=&v"(c[3])
+        : "v"(addr)
+        : "memory");
+}
+
+// Force laws with the 1-ulp reciprocal (the wave kernel keeps the IEEE forms of force_law).
+// Laws 0..2 are one branch-free expression  max((A - B*u2) / (u2+beta)^2, lo)  with
+// (A,B,lo) = (1,0,-inf) inverse distance, (1,1,-inf) equilibrium, (u0^2,1,0) clipped; law 3 swaps the
+// denominator for (u2+beta)^gamma.  u2 = d2/s^2.
+struct ForceCoef {
+    float A, B, lo, beta, gamma;
+    int strong;
+};
+__device__ inline ForceCoef force_coef(int kind, float beta, float u0, float gamma) {
+    ForceCoef c;
+    c.A = kind == WTP_FORCE_CLIPPED_SPACING ? u0 * u0 : 1.f;
+    c.B = kind == WTP_FORCE_INVERSE_DISTANCE ? 0.f : 1.f;
+    c.lo = kind == WTP_FORCE_CLIPPED_SPACING ? 0.f : -Lim<float>::inf();
+    c.beta = beta;
+    c.gamma = gamma;
+    c.strong = kind == WTP_FORCE_STRONG_SPACING;
+    return c;
+}
+__device__ inline float force_fast(const ForceCoef& c, float u2) {
+    const float d = u2 + c.beta;
+    float inv = __builtin_amdgcn_rcpf(d * d);
+    if (c.strong) inv = __builtin_amdgcn_exp2f(-c.gamma * __builtin_amdgcn_logf(d)); // wave-uniform
+    const float f = (c.A - c.B * u2) * inv;
+    return f > c.lo ? f : c.lo;
 }
 
 } // namespace wtp

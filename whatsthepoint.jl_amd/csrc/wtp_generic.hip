@@ -111,12 +111,6 @@ __global__ __launch_bounds__(kThreads) void generic_kernel(SearchArgs<T> a, cons
     }
 }
 
-static inline int blocks_for(int64_t n, int cap) {
-    int64_t b = (n + kThreads - 1) / kThreads;
-    if (b < 1) b = 1;
-    return (int)(b > cap ? cap : b);
-}
-
 // ---- arbitrary query positions against the current snapshot (wtp_relax_query_knn) -----------------
 template <typename T>
 __global__ void pack_queries_kernel(const T* __restrict__ xyz, int64_t nq, int dim, Pt<T>* __restrict__ out) {
@@ -136,7 +130,7 @@ template <typename T> int launch_query_knn(wtp_ctx* ctx, SearchArgs<T>& a, const
                        (int64_t)a.n, dim, d_packed);
     a.query = d_packed;
     a.include_self = 1; // a query is not a snapshot point: nothing to drop
-    hipLaunchKernelGGL((generic_kernel<T, 0>), dim3(blocks_for(a.n, 4096)), dim3(kThreads), 0, ctx->stream, a,
+    hipLaunchKernelGGL((generic_kernel<T, 0>), dim3(grid_for(a.n, kThreads, 4096)), dim3(kThreads), 0, ctx->stream, a,
                        (const int32_t*)nullptr, (const int32_t*)nullptr, 1, 0);
     WTP_HIP(ctx, hipGetLastError());
     return WTP_OK;
@@ -209,7 +203,7 @@ template <typename T> int launch_generic_sweep(wtp_ctx* ctx, SearchArgs<T>& a, b
     int rc = launch_wave_sweep<T>(ctx, a, all);
     if (rc) return rc;
     // serial last resort over what the wave kernel could not buffer: a handful of queries at most
-    a.used_generic = blocks_for(a.n / 16, 256);
+    a.used_generic = grid_for(a.n / 16, kThreads, 256);
     hipLaunchKernelGGL((generic_kernel<T, 1>), dim3(a.used_generic), dim3(kThreads), 0, ctx->stream, a, a.fb2_list,
                        a.fb2_count, 0, part_base);
     WTP_HIP(ctx, hipGetLastError());
@@ -305,7 +299,7 @@ int launch_radius_fill(wtp_ctx* ctx, SearchArgs<T>& a, T r, const int64_t* d_off
     // the count phase parked the rows it found: copy them.  What it could not park (arena full, rows beyond the wave
     // kernel's list) is searched again: by the wave kernel over the brick kernel's hand-back list, which still stands
     // (fp32), or over all points (it skips the parked ones), then by the serial kernel
-    hipLaunchKernelGGL(radius_copy_rows_kernel, dim3(blocks_for((int64_t)a.n * 16, 16384)), dim3(kThreads), 0, ctx->stream,
+    hipLaunchKernelGGL(radius_copy_rows_kernel, dim3(grid_for((int64_t)a.n * 16, kThreads, 16384)), dim3(kThreads), 0, ctx->stream,
                        (int64_t)a.n, (const int32_t*)a.rad_tmp, (const uint8_t*)a.rad_done, (const int32_t*)a.rad_arena,
                        (const int64_t*)a.rad_arena_off, d_offsets, d_idx);
     int rc;

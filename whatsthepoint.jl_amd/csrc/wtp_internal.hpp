@@ -437,6 +437,12 @@ int launch_axis_hist(wtp_ctx* ctx, const Pt<T>* pts, int64_t n, int dim, const d
 template <typename T>
 int load_points(wtp_ctx* ctx, const T* d_xyz, Pt<T>* out, int64_t n, int dim);
 
+// blocks of a grid-stride launch: ceil(n / threads), clamped to [1, cap]
+inline int grid_for(int64_t n, int threads, int cap) {
+    int64_t b = (n + threads - 1) / threads;
+    if (b < 1) b = 1;
+    return (int)(b > cap ? cap : b);
+}
 template <typename T> int launch_topology(wtp_ctx* ctx, SearchArgs<T>& a);
 // fp32 sweep on 4 x 4 x 4 bricks (wtp_brick.hip), compact-support (cs) or explicit k-selection; hand-backs land in a.fb_list
 int launch_brick_sweep(wtp_ctx* ctx, SearchArgs<float>& a, bool cs);
@@ -509,21 +515,20 @@ template <typename T>
 int launch_spacing_session(wtp_ctx* ctx, const Pt<T>* pts, int64_t n, int64_t first_id, const void* d_nodes, int64_t m,
                            int kind, double p0, double p1, double p2, T* d_spacing_pp, int32_t* d_hint,
                            const int32_t* d_cell_start = nullptr, const void* d_grid = nullptr, void* d_cert = nullptr);
-// fp64 topology through an fp32 candidate search (wtp_hash.hip)
+// per-block bounding boxes of a Float64 cloud into ctx->bbox_part (wtp_hash.hip)
+int launch_bbox64(wtp_ctx* ctx, const double4* pts, int64_t n, int* nparts);
+// wtp_sweep64.hip: the Float64 candidate stage of fp64 topology and of fp64 sweeps of the k-nearest laws
 int launch_origin(wtp_ctx* ctx, const double4* pts, int64_t n, double* d_org4);
-// wtp_sweep64.hip: fp64 sweeps of the k-nearest laws through fp32 candidates
-int launch_f64k_local(wtp_ctx* ctx, const double4* snap, int64_t n, const double* d_org4, float4* out);
-int launch_f64k_relabel(wtp_ctx* ctx, const double4* snap, float4* sorted32, int32_t* sslot, double4* s64, int64_t n);
-int launch_refine_sweep_f64(wtp_ctx* ctx, SearchArgs<double>& a, const double4* s64, const int32_t* sslot, const int32_t* cand,
-                            const float* cdist, const double* d_org4);
 int launch_to_local_f32(wtp_ctx* ctx, const double4* in, int64_t n, const double* d_org4, float4* out);
+int launch_relabel_slots(wtp_ctx* ctx, const double4* raw, float4* sorted32, double4* sorted64, int32_t* sslot, int64_t n);
 int launch_refine_f64(wtp_ctx* ctx, const double4* raw, const int32_t* cand, const float* cdist, int64_t n, int kc, int k,
                       int include_self, const double* d_org4, int32_t* idx_out, double* dist_out, int32_t* fail_list,
                       int32_t* fail_count);
-int launch_relabel_slots(wtp_ctx* ctx, const double4* raw, float4* sorted32, double4* sorted64, int64_t n);
 int launch_refine_f64_slots(wtp_ctx* ctx, const double4* sorted, const int32_t* cand, const float* cdist, int64_t n, int kc, int k,
                             int include_self, const double* d_org4, int32_t* idx_out, double* dist_out, int32_t* fail_list,
                             int32_t* fail_count);
+int launch_refine_sweep_f64(wtp_ctx* ctx, SearchArgs<double>& a, const double4* s64, const int32_t* sslot, const int32_t* cand,
+                            const float* cdist, const double* d_org4);
 // isinside post-filter (wtp_inside.hip)
 int isinside_chunks(wtp_ctx* ctx, int64_t n, int64_t m, int points_per_block);
 int isinside_greens_ppb();

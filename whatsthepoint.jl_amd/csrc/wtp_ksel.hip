@@ -75,37 +75,6 @@ struct KsSmem {
     Acc acc[kKsThreads / 64];
 };
 
-typedef float ks_f4 __attribute__((ext_vector_type(4)));
-
-__device__ inline float4 ks_pt(const unsigned char* base, uint32_t byte_off) {
-    return *reinterpret_cast<const float4*>(base + byte_off);
-}
-__device__ inline uint32_t ks_f2u(float f) { return __builtin_bit_cast(uint32_t, f); }
-
-// Fast-math force law (1-ulp rcp), the expression of brick_kernel's force_fast: laws 0..2 are
-//   max((A - B u2) / (u2 + beta)^2, lo)  with (A, B, lo) = (1,0,-inf) | (1,1,-inf) | (u0^2,1,0);  law 3: (u2 + beta)^gamma below.
-struct KsForce {
-    float A, B, lo, beta, gamma;
-    int strong;
-};
-__device__ inline KsForce ks_force_coef(int kind, float beta, float u0, float gamma) {
-    KsForce c;
-    c.A = kind == WTP_FORCE_CLIPPED_SPACING ? u0 * u0 : 1.f;
-    c.B = kind == WTP_FORCE_INVERSE_DISTANCE ? 0.f : 1.f;
-    c.lo = kind == WTP_FORCE_CLIPPED_SPACING ? 0.f : -Lim<float>::inf();
-    c.beta = beta;
-    c.gamma = gamma;
-    c.strong = kind == WTP_FORCE_STRONG_SPACING;
-    return c;
-}
-__device__ inline float ks_force(const KsForce& c, float u2) {
-    const float d = u2 + c.beta;
-    float inv = __builtin_amdgcn_rcpf(d * d);
-    if (c.strong) inv = __builtin_amdgcn_exp2f(-c.gamma * __builtin_amdgcn_logf(d)); // wave-uniform
-    const float f = (c.A - c.B * u2) * inv;
-    return f > c.lo ? f : c.lo;
-}
-
 static size_t ksel_smem_bytes(int hcap) {
     return (size_t)hcap * 16 + kKsPadBytes + kKsRingBytes + sizeof(KsSmem);
 }
@@ -388,7 +357,7 @@ __global__ __launch_bounds__(kKsThreads, 2) void ksel_kernel(SearchArgs<float> a
                 // as its three subtractions have consumed it, a use waits only for ITS read (`lgkmcnt(3)`).  One trip of
                 // the loop fills one mask word (four steps of eight); finished words are parked in the lane's ring, so the
                 // loop is code of one word, not of eight (the instruction cache is shared by two compute units).
-                ks_f4 c[4];
+                f4 c[4];
                 uint32_t pa = pa0;
                 uint32_t addr = lds_base + pa0;
                 asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:16\n\tds_read_b128 %2, %4 offset:32\n\tds_read_b128 %3, %4 offset:48"
@@ -517,14 +486,14 @@ __global__ __launch_bounds__(kKsThreads, 2) void ksel_kernel(SearchArgs<float> a
                 // the asm that waits for it.)
 #define KS_USE(v4) asm volatile("" : "+v"(v4))
 #define KS_KEEP(x) asm volatile("" : "+v"(x))
-                auto ld = [&](uint32_t off) { return *reinterpret_cast<const ks_f4*>(smem_raw + off); };
-                ks_f4 cA[4], cB[4];
+                auto ld = [&](uint32_t off) { return *reinterpret_cast<const f4*>(smem_raw + off); };
+                f4 cA[4], cB[4];
                 uint32_t pA[4], pB[4];
                 // ---- keys from the ring: positions four to a word ----
                 uint32_t rp[kKsRing / 4];
 #pragma unroll
                 for (int gq = 0; gq < kKsRing / 4; ++gq) rp[gq] = *reinterpret_cast<const uint32_t*>(smem_raw + ring_l + 4u * (uint32_t)gq);
-                auto chunk_issue = [&](int c4, uint32_t (&ps)[4], ks_f4 (&cc)[4]) {
+                auto chunk_issue = [&](int c4, uint32_t (&ps)[4], f4 (&cc)[4]) {
 #pragma unroll
                     for (int u = 0; u < 4; ++u) ps[u] = (c4 * 4 + u) < cnt ? ((rp[c4] >> (8 * u)) & 255u) : 0u;
 #pragma unroll
@@ -533,8 +502,8 @@ __global__ __launch_bounds__(kKsThreads, 2) void ksel_kernel(SearchArgs<float> a
                 chunk_issue(0, pA, cA);
 #pragma unroll
                 for (int c4 = 0; c4 < kKsRing / 4; ++c4) {
-                    ks_f4(&cc)[4] = (c4 & 1) ? cB : cA;
-                    ks_f4(&cn)[4] = (c4 & 1) ? cA : cB;
+                    f4(&cc)[4] = (c4 & 1) ? cB : cA;
+                    f4(&cn)[4] = (c4 & 1) ? cA : cB;
                     uint32_t(&pc)[4] = (c4 & 1) ? pB : pA;
                     uint32_t(&pn)[4] = (c4 & 1) ? pA : pB;
                     if (__any(cnt > c4 * 4)) { // wave-uniform: skip chunks no lane has filled
@@ -543,7 +512,7 @@ __global__ __launch_bounds__(kKsThreads, 2) void ksel_kernel(SearchArgs<float> a
 #pragma unroll
                         for (int u = 0; u < 4; ++u) {
                             KS_USE(cc[u]);
-                            uint32_t key = (ks_f2u(dist2<float>(qp.x, qp.y, qp.z, cc[u].x, cc[u].y, cc[u].z)) & ~255u) | pc[u];
+                            uint32_t key = (f2u(dist2<float>(qp.x, qp.y, qp.z, cc[u].x, cc[u].y, cc[u].z)) & ~255u) | pc[u];
                             KS_KEEP(key);
                             k[c4 * 4 + u] = (c4 * 4 + u) < cnt ? key : 0x7F800000u;
                         }
@@ -556,15 +525,15 @@ __global__ __launch_bounds__(kKsThreads, 2) void ksel_kernel(SearchArgs<float> a
                 WTP_SORTNET_64(k)
                 // ---- window: exact (d2, id) of the first K + 2 sorted entries, chunks of four ----
                 constexpr int NCH = (KW + 3) / 4;
-                auto win_issue = [&](int ch, ks_f4 (&cc)[4]) {
+                auto win_issue = [&](int ch, f4 (&cc)[4]) {
 #pragma unroll
                     for (int u = 0; u < 4; ++u) cc[u] = ld(pa0 + (k[ch * 4 + u] & 255u) * 16u);
                 };
                 win_issue(0, cA);
 #pragma unroll
                 for (int ch = 0; ch < NCH; ++ch) {
-                    ks_f4(&cc)[4] = (ch & 1) ? cB : cA;
-                    ks_f4(&cn)[4] = (ch & 1) ? cA : cB;
+                    f4(&cc)[4] = (ch & 1) ? cB : cA;
+                    f4(&cn)[4] = (ch & 1) ? cA : cB;
                     if (ch + 1 < NCH) win_issue(ch + 1, cn);
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -642,7 +611,7 @@ __global__ __launch_bounds__(kKsThreads, 2) void ksel_kernel(SearchArgs<float> a
                     if (row_ok) {
 #pragma unroll
                         for (int j = 0; j < KR; ++j)
-                            if (j < K) ost[lane * K + j] = pass == 0 ? (uint32_t)ii[j] : ks_f2u(wsqrt(dd[j]));
+                            if (j < K) ost[lane * K + j] = pass == 0 ? (uint32_t)ii[j] : f2u(wsqrt(dd[j]));
                     }
                     __builtin_amdgcn_wave_barrier();
                     uint32_t* dst = pass == 0 ? reinterpret_cast<uint32_t*>(a.idx_out) : reinterpret_cast<uint32_t*>(a.dist_out);
@@ -670,7 +639,7 @@ __global__ __launch_bounds__(kKsThreads, 2) void ksel_kernel(SearchArgs<float> a
                     // the k-th pair in canonical order; the window entries are read again for their coordinates
                     const float s = a.spacing_pp ? a.spacing_pp[qid] : a.spacing_const;
                     const float inv_s2 = 1.f / (s * s);
-                    const KsForce fc = ks_force_coef(a.force_kind, a.beta, a.u0, a.gamma);
+                    const ForceCoef fc = force_coef(a.force_kind, a.beta, a.u0, a.gamma);
                     float Fx = 0.f, Fy = 0.f, Fz = 0.f, nd2 = Lim<float>::inf();
                     int32_t nid = 0x7FFFFFFF;
                     bool coincident = false;
@@ -679,7 +648,7 @@ __global__ __launch_bounds__(kKsThreads, 2) void ksel_kernel(SearchArgs<float> a
                         float4 c[4];
 #pragma unroll
                         for (int u = 0; u < 4; ++u)
-                            if (j0 + u < KW) c[u] = ks_pt(smem_raw, pa0 + (k[j0 + u] & 255u) * 16u);
+                            if (j0 + u < KW) c[u] = lds_pt(smem_raw, pa0 + (k[j0 + u] & 255u) * 16u);
 #pragma unroll
                         for (int u = 0; u < 4; ++u) {
                             const int j = j0 + u;
@@ -691,7 +660,7 @@ __global__ __launch_bounds__(kKsThreads, 2) void ksel_kernel(SearchArgs<float> a
                                 const bool nearer = in && lex_lt(d, cid, nd2, nid);
                                 nd2 = nearer ? d : nd2;
                                 nid = nearer ? cid : nid;
-                                const float f = ks_force(fc, d * inv_s2);
+                                const float f = force_fast(fc, d * inv_s2);
                                 const float coef = (in && d > 0.f) ? f * __builtin_amdgcn_rsqf(d) : 0.f;
                                 Fx += coef * dx;
                                 Fy += coef * dy;
