@@ -44,6 +44,30 @@ def test_sweep_with_far_outliers_matches_oracle(O, wtp, ctx):
     assert st["n_move"] == n
 
 
+def test_float64_candidate_sweeps_with_far_outliers_are_exact(O, wtp, monkeypatch):
+    """Float64 and a k-nearest law: every sweep searches fp32 candidates on a float copy whose first grid needs a
+    quantile box of its own (in the copy's coordinates), and every rebuild clips to the session's box (in the
+    session's).  Rebuilt every sweep, positions and forces stay bit-identical to the exact wave-per-query path
+    (WTP_F64_KSEL=0) and to the oracle loop."""
+    n, iters = 20000, 4
+    x = _cloud(wtp, n, np.float64, 3e3)
+    s = float(n) ** (-1.0 / 3.0)
+    force = dict(kind=1, beta=0.2, u0=1.0, gamma=3.0)        # SpacingEquilibrium
+    res = {}
+    for flag in ("1", "0"):
+        monkeypatch.setenv("WTP_F64_KSEL", flag)
+        with wtp.Context(0) as c:
+            with c.relax(x, 0, s, force, 21, s / 2000, s / 20) as t:
+                conv, _ = t.run(iters, 1)
+                res[flag] = (t.positions(), t.point_data()["forces"], np.asarray(conv))
+    p, f, conv = res["1"]
+    assert np.array_equal(p, res["0"][0]) and np.array_equal(f, res["0"][1]) and np.array_equal(conv, res["0"][2])
+    ref = O.relax_loop(x, 0, s, 1, 0.2, 1.0, 3.0, 21, s / 2000, s / 20, max_iters=iters, tol=0.0, rebuild_every=1,
+                       stall_after=0, cv_target=0.0)
+    assert np.array_equal(p, ref["p"])
+    assert np.array_equal(conv, ref["conv"])
+
+
 def test_non_finite_points_do_not_disturb_the_rest(O, wtp, ctx):
     n = 20000
     x = wtp.synth.uniform(n, 3, np.float32, 29)

@@ -220,27 +220,26 @@ static int find_robust_box(wtp_ctx* ctx, const Pt<T>* in, int64_t n, int dim, co
     }
     memcpy(ctx->host_pinned, box, sizeof(box));
     WTP_HIP(ctx, hipMemcpyAsync(ctx->box_dev.p, ctx->host_pinned, sizeof(box), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = sync(ctx))) return rc;
-    ctx->box_active = true;
-    return WTP_OK;
+    return sync(ctx);
 }
 
-// Measured build: the cell scale into t.scale (from 1) and the occupancy asked for into t.rho; the grid of the last build and
-// the occupancy its points see into *hg_out / *rho_eff_out.
+// Measured build b: the cell scale into t.scale (from 1), the occupancy asked for into t.rho and whether the grid lies over a
+// quantile box into t.clipped; the grid of the last build and the occupancy its points see into *hg_out / *rho_eff_out.
 template <typename T>
-static int build_hash_tuned(wtp_ctx* ctx, GridTune& t, const Pt<T>* in, Pt<T>* out, int64_t n, int dim, int k,
-                            double rho_direct, double min_cell, Grid<T>* hg_out, double* rho_eff_out) {
-    const double target = hash_target_rho(ctx, dim, k, rho_direct);
+static int build_hash_tuned(wtp_ctx* ctx, GridTune& t, HashBuild<T> b, Grid<T>* hg_out, double* rho_eff_out) {
+    const double target = hash_target_rho(ctx, b.dim, b.k, b.rho_direct);
     double scale = 1.0;
     double prev_c = -1;
     int rc;
     if ((rc = ensure(ctx, ctx->occ, 64))) return rc;
     if ((rc = ensure_pinned(ctx, 16384))) return rc;
-    ctx->box_active = false; // every tuned build starts from the true bounding box
-    bool boxed = false;
+    t.clipped = false; // every tuned build starts from the true bounding box
+    b.keep_grid = false;
     for (int round = 0; round < 3; ++round) {
-        if ((rc = build_hash<T>(ctx, in, out, n, dim, k, 0.0, rho_direct, min_cell, scale))) return rc;
-        if ((rc = launch_occupancy(ctx, (unsigned long long*)ctx->occ.p))) return rc;
+        b.cell_scale = scale;
+        b.box = t.clipped ? (const double*)ctx->box_dev.p : nullptr;
+        if ((rc = build_hash<T>(ctx, b))) return rc;
+        if ((rc = launch_occupancy<T>(ctx, (const Grid<T>*)ctx->grid.p, (unsigned long long*)ctx->occ.p))) return rc;
         char* hp = (char*)ctx->host_pinned;
         WTP_HIP(ctx, hipMemcpyAsync(hp, ctx->occ.p, 24, hipMemcpyDeviceToHost, ctx->stream));
         WTP_HIP(ctx, hipMemcpyAsync(hp + 64, ctx->grid.p, sizeof(Grid<T>), hipMemcpyDeviceToHost, ctx->stream));
@@ -255,10 +254,10 @@ static int build_hash_tuned(wtp_ctx* ctx, GridTune& t, const Pt<T>* in, Pt<T>* o
         // the caps on the cell count bind (4096 per axis / 8 n) and the cells are still far over-full:
         // the box is stretched by outliers — lay the grid over the bulk and start over, once
         const bool capped = hg.n[0] >= kMaxAxisCells || hg.n[1] >= kMaxAxisCells || hg.n[2] >= kMaxAxisCells ||
-                            (double)hg.ncells > 6.0 * (double)n;
-        if (excess > 4.0 && capped && !boxed) {
-            if ((rc = find_robust_box<T>(ctx, in, n, dim, hg))) return rc;
-            boxed = true;
+                            (double)hg.ncells > 6.0 * (double)b.n;
+        if (excess > 4.0 && capped && !t.clipped) {
+            if ((rc = find_robust_box<T>(ctx, b.in, b.n, b.dim, hg))) return rc;
+            t.clipped = true;
             scale = 1.0;
             prev_c = -1;
             round = -1;
@@ -273,7 +272,7 @@ static int build_hash_tuned(wtp_ctx* ctx, GridTune& t, const Pt<T>* in, Pt<T>* o
         if (scale < 0.02) scale = 0.02;
     }
     t.scale = scale;
-    t.rho = rho_direct;
+    t.rho = b.rho_direct;
     return WTP_OK;
 }
 
@@ -356,44 +355,47 @@ static double ksel_cap_count(int kq) {
     return (double)kq + (kCapKsel - 22.0) / std::sqrt(22.0) * std::sqrt((double)kq);
 }
 
-// The k-selection layout on the grid just measured (hg, with rho_eff the occupancy its points see): the occupancy whose grid
-// fills the bricks' lanes best — one more measured build when the pick moves t.rho by more than 1 % — and the brick
-// geometry of the final grid, into t.
+// The k-selection layout of build b on the grid just measured (hg, with rho_eff the occupancy its points see): the occupancy
+// whose grid fills the bricks' lanes best — one more measured build when the pick moves t.rho by more than 1 % — and the
+// brick geometry of the final grid, into t.
 template <typename T>
-static int ksel_tune(wtp_ctx* ctx, GridTune& t, const Pt<T>* in, Pt<T>* out, int64_t n, int dim, int k, Grid<T>& hg,
-                     double& rho_eff) {
-    const double pick = ksel_pick_rho((double)n, (double)hg.ncells, hg.n[0], t.rho, rho_eff);
+static int ksel_tune(wtp_ctx* ctx, GridTune& t, HashBuild<T> b, Grid<T>& hg, double& rho_eff) {
+    const double pick = ksel_pick_rho((double)b.n, (double)hg.ncells, hg.n[0], t.rho, rho_eff);
     int rc;
-    if (std::fabs(pick - t.rho) > 0.01 * t.rho && (rc = build_hash_tuned<T>(ctx, t, in, out, n, dim, k, pick, 0.0, &hg, &rho_eff)))
-        return rc;
-    ksel_geometry(ctx, (double)n, (double)hg.ncells, hg.n[0], rho_eff, &t.bx, &t.hcap);
+    if (std::fabs(pick - t.rho) > 0.01 * t.rho) {
+        b.rho_direct = pick;
+        if ((rc = build_hash_tuned<T>(ctx, t, b, &hg, &rho_eff))) return rc;
+    }
+    ksel_geometry(ctx, (double)b.n, (double)hg.ncells, hg.n[0], rho_eff, &t.bx, &t.hcap);
     return WTP_OK;
 }
 
-// The grid of a cloud with the tuning cached in t.  When t was measured for this cloud size, dim, kq and layout (the usual
-// case: rebuild_topology! on the same points) it is one build_hash: no occupancy passes, no host synchronisation.  The
-// tuning only affects speed, never the result.  Otherwise the grid is measured (build_hash_tuned, then ksel_tune on the k-selection layout) and stored with its key.
-template <typename T>
-static int build_grid_cached(wtp_ctx* ctx, GridTune& t, const Pt<T>* in, Pt<T>* out, int64_t n, int dim, int kq, bool ksel) {
+// The grid of build b (b.k: neighbours sought per query, self included) with the tuning cached in t.  When t was measured
+// for this cloud size, dim, k and layout (the usual case: rebuild_topology! on the same points) it is one build_hash on the
+// full box: no occupancy passes, no host synchronisation.  The tuning only affects speed, never the result.  Otherwise the
+// grid is measured (build_hash_tuned, then ksel_tune on the k-selection layout) and stored with its key.
+template <typename T> static int build_grid_cached(wtp_ctx* ctx, GridTune& t, HashBuild<T> b, bool ksel) {
     // (loose: a Float64 session's cloud changes size with every swapped head; an exact match would measure again each sweep)
-    const int64_t slack = t.loose ? n / 20 : 0;
-    if (t.valid && t.dim == dim && t.kq == kq && t.ksel == ksel && std::llabs((long long)(n - t.n)) <= slack) {
-        ctx->box_active = false;
-        return build_hash<T>(ctx, in, out, n, dim, kq, 0.0, t.rho, 0.0, t.scale);
+    const int64_t slack = t.loose ? b.n / 20 : 0;
+    if (t.valid && t.dim == b.dim && t.kq == b.k && t.ksel == ksel && std::llabs((long long)(b.n - t.n)) <= slack) {
+        b.rho_direct = t.rho;
+        b.cell_scale = t.scale;
+        return build_hash<T>(ctx, b);
     }
     t.valid = false;
     double rho_eff = 0;
     Grid<T> hg;
-    int rc = build_hash_tuned<T>(ctx, t, in, out, n, dim, kq, ksel ? ksel_rho_for(kq) : 0.0, 0.0, &hg, &rho_eff);
-    if (!rc && ksel) rc = ksel_tune<T>(ctx, t, in, out, n, dim, kq, hg, rho_eff);
+    b.rho_direct = ksel ? ksel_rho_for(b.k) : 0.0;
+    int rc = build_hash_tuned<T>(ctx, t, b, &hg, &rho_eff);
+    if (!rc && ksel) rc = ksel_tune<T>(ctx, t, b, hg, rho_eff);
     if (rc) return rc;
-    t.n = n;
-    t.dim = dim;
-    t.kq = kq;
+    t.n = b.n;
+    t.dim = b.dim;
+    t.kq = b.k;
     t.ksel = ksel;
     // A clipped box belongs to this very cloud: a topology call never reuses its scale on the full box a hit builds.  (loose:
     // kept, as a Float64 session has always kept it — measuring again would cost three builds and host reads per sweep.)
-    t.valid = t.loose || !ctx->box_active;
+    t.valid = t.loose || !t.clipped;
     return WTP_OK;
 }
 
@@ -430,10 +432,9 @@ static int knn_dev_t(wtp_ctx* ctx, const T* d_xyz, int64_t n, int dim, int k, in
     // fp32 3-D clouds with k + self <= 24 (the reference's k = 21 among them): the x-slowest layout of wtp_ksel.hip —
     // cells of ~1.2 points, the k nearest inside the 5 x 5 x 5 block around the query's cell
     const bool ksel = sizeof(T) == 4 && dim == 3 && ctx->ksel && !ctx->force_generic && kq <= ksel_kmax() && n >= 4096;
-    ctx->topology_build = true;
-    rc = build_grid_cached<T>(ctx, ctx->knn_tune, raw, sorted, n, dim, kq, ksel);
-    ctx->topology_build = false;
-    if (rc) return rc;
+    HashBuild<T> b(raw, sorted, n, dim, kq);
+    b.canonical = false; // rows are ordered by (d2, id) explicitly (canon_kernel: 0.3 of a 1.1 ms KNN call on unsorted input)
+    if ((rc = build_grid_cached<T>(ctx, ctx->knn_tune, b, ksel))) return rc;
     span_end(ctx, sp);
     SearchArgs<T> a{};
     init_search(a, ctx, sorted, sorted, n, k, include_self);
@@ -489,9 +490,9 @@ static int f64_candidates(wtp_ctx* ctx, const double4* pts, int64_t n, int dim, 
     if ((rc = launch_origin(ctx, pts, n, org4))) return rc;
     if ((rc = launch_to_local_f32(ctx, pts, n, org4, raw32))) return rc;
     const bool ksel = dim == 3 && ctx->ksel && kc <= ksel_kmax() && n >= 4096;
-    ctx->topology_build = true; // rows are ordered by (d2, id) explicitly: no canonical-order pass
-    rc = build_grid_cached<float>(ctx, t, raw32, sorted32, n, dim, kc, ksel);
-    ctx->topology_build = false;
+    HashBuild<float> hb(raw32, sorted32, n, dim, kc);
+    hb.canonical = false; // rows are ordered by (d2, id) explicitly: no canonical-order pass
+    rc = build_grid_cached<float>(ctx, t, hb, ksel);
     if (!rc) rc = relabel(sorted32);
     if (rc) return rc;
     span_end(ctx, sp);
@@ -567,11 +568,9 @@ static int knn_dev_f64(wtp_ctx* ctx, const double* d_xyz, int64_t n, int dim, in
     const int32_t n_fail = *(const int32_t*)ctx->host_pinned;
     if (n_fail > 0) { // exact fp64 path for the uncertified queries: wave kernel over their ids, fp64 grid
         double4* sorted64 = (double4*)ctx->pts[1].p;
-        ctx->box_active = false;
-        ctx->topology_build = true; // rows are ordered by (d2, id) explicitly: no canonical-order pass (0.5 ms on unsorted input)
-        rc = build_hash<double>(ctx, raw64, sorted64, n, dim, kq, 0.0);
-        ctx->topology_build = false;
-        if (rc) return rc;
+        HashBuild<double> hb(raw64, sorted64, n, dim, kq);
+        hb.canonical = false; // rows are ordered by (d2, id) explicitly: no canonical-order pass (0.5 ms on unsorted input)
+        if ((rc = build_hash<double>(ctx, hb))) return rc;
         SearchArgs<double> b{};
         init_search(b, ctx, sorted64, raw64, n, k, include_self); // list entries are ids: raw64[id] is the query, its w the id
         b.idx_out = d_idx;
@@ -800,11 +799,10 @@ template <typename T> static int radius_count_t(wtp_ctx* ctx, int64_t n, int dim
     Pt<T>* sorted = (Pt<T>*)ctx->pts[1].p;
     int sp = span_begin(ctx, 0);
     if ((rc = load_points<T>(ctx, (const T*)ctx->raw_in.p, raw, n, dim))) return rc;
-    ctx->box_active = false;
-    ctx->topology_build = true;
-    rc = build_hash<T>(ctx, raw, sorted, n, dim, 0, r > 0 ? r : 1e-300);
-    ctx->topology_build = false;
-    if (rc) return rc;
+    HashBuild<T> b(raw, sorted, n, dim, 0);
+    b.radius = r > 0 ? r : 1e-300;
+    b.canonical = false; // rows are ordered by (d2, id) explicitly
+    if ((rc = build_hash<T>(ctx, b))) return rc;
     span_end(ctx, sp);
     SearchArgs<T> a{};
     init_search(a, ctx, sorted, sorted, n, 0, 0);
@@ -1196,8 +1194,16 @@ static int cs2_tune(wtp_ctx* ctx, RelaxState& r, const Grid<float>& hg, double r
     return WTP_OK;
 }
 
+// The session's grid, cell table and box trade places with the float copy's (relax_f64_ksel_sweep): what the float copy
+// builds and measures — a quantile box among it, in its own coordinates — stays in its own buffers.
+static void swap_float_copy_grid(wtp_ctx* ctx) {
+    std::swap(ctx->grid, ctx->grid_b);
+    std::swap(ctx->cell_start, ctx->cell_start_b);
+    std::swap(ctx->box_dev, ctx->box_b);
+}
+
 // Float64 sweep of a k-nearest law on a fresh snapshot (wtp_sweep64.hip): candidates from the fp32 k-selection kernels on a
-// float copy of the snapshot with its own grid — the session's grid and cell table are parked meanwhile and come back
+// float copy of the snapshot with its own grid — the session's grid, cell table and box are parked meanwhile and come back
 // untouched for the exact path —, exact re-ranking + force sum + step per query; what is not certified is left in a.fb_list.
 // *sp: the hash span it opens is closed and the search span left open.
 static int relax_f64_ksel_sweep(wtp_ctx* ctx, SearchArgs<double>& a, int* sp) {
@@ -1220,31 +1226,24 @@ static int relax_f64_ksel_sweep(wtp_ctx* ctx, SearchArgs<double>& a, int* sp) {
     *sp = span_begin(ctx, 0);
     WTP_HIP(ctx, hipMemsetAsync(ctx->f64k_cnt.p, 0, 64, ctx->stream));
     b.counters_cleared = 1;
-    std::swap(ctx->grid, ctx->grid_b);
-    std::swap(ctx->cell_start, ctx->cell_start_b);
-    const void* ncells_session = ctx->ncells_dev;
-    const bool box_session = ctx->box_active; // (a clipped box is in the session's coordinates)
+    swap_float_copy_grid(ctx);
     const double* org4 = nullptr;
     rc = f64_candidates(ctx, snap, n, 3, kc, r.f64k_tune, b, *sp, &org4, [&](float4* sorted32) {
         return launch_relabel_slots(ctx, snap, sorted32, (double4*)ctx->f64k_s64.p, (int32_t*)ctx->f64k_slot.p, n);
     });
     // the session's structures again (the float copy's stay where they are until the next sweep overwrites them)
-    std::swap(ctx->grid, ctx->grid_b);
-    std::swap(ctx->cell_start, ctx->cell_start_b);
-    ctx->ncells_dev = ncells_session;
-    ctx->box_active = box_session;
+    swap_float_copy_grid(ctx);
     if (rc) return rc;
     return launch_refine_sweep_f64(ctx, a, (const double4*)ctx->f64k_s64.p, (const int32_t*)ctx->f64k_slot.p,
                                    (const int32_t*)ctx->cand_idx.p, (const float*)ctx->cand_dist.p, org4);
 }
 
 // Will the next rebuild keep its grid (no bounding-box pass) for a head of n_fixed_next points?  head_swapped: it reads a
-// replaced fixed head (HashView).  relax_step_t decides by it, relax_prerank guesses by it ahead of the ghost rows.
-static bool grid_reusable(const wtp_ctx* ctx, int64_t n_fixed_next, bool head_swapped) {
-    const RelaxState& r = ctx->relax;
+// replaced fixed head (HashView).  relax_rebuild decides by it, relax_prerank guesses by it ahead of the ghost rows.
+static bool grid_reusable(const RelaxState& r, int64_t n_fixed_next, bool head_swapped) {
     const bool head_ok = !head_swapped || (r.shard_grid_reuse && r.grid_fixed > 0 &&
                                            std::llabs((long long)(n_fixed_next - r.grid_fixed)) * 10 <= (long long)r.grid_fixed + 640);
-    return r.grid_age < kGridReuseMax && !r.moved_by_hand && head_ok && !ctx->box_active;
+    return r.grid_age < kGridReuseMax && !r.moved_by_hand && head_ok && !r.tune.clipped;
 }
 
 // The brick geometry of the round-2 sweep (and which queries its bricks hand to the exact path, whose sums round
@@ -1385,94 +1384,108 @@ template <typename T> static int launch_sweep(wtp_ctx* ctx, SearchArgs<T>& a, Sw
     return rc;
 }
 
+// The session's hash build of the snapshot `in` (n points, k neighbours; read through `view` when a replaced fixed head waits
+// behind it) into `out`, on its route's grid with the measured cell scale and clipped box.  The Float64 candidate route orders
+// every sum by (d2, index) explicitly, on the exact path behind it too: no canonical-order pass (0.37 ms per 10 M Float64
+// points) — except in the builds that measure the grid.
+template <typename T>
+static HashBuild<T> relax_request(const wtp_ctx* ctx, const RelaxState& r, const Pt<T>* in, Pt<T>* out, int64_t n, int k,
+                                  const HashView& view, bool keep_grid) {
+    const RouteGrid g = route_grid(ctx, r);
+    HashBuild<T> b(in, out, n, r.dim, k);
+    b.rho_direct = g.rho;
+    b.min_cell = g.min_cell;
+    b.cell_scale = r.tune.scale;
+    b.view = view;
+    b.keep_grid = keep_grid;
+    b.canonical = !r.tune.valid || r.route != SweepRoute::F64Ksel;
+    b.box = r.tune.clipped ? (const double*)ctx->box_dev.p : nullptr;
+    return b;
+}
+
+// Snapshot tail <- p, tree rebuilt (src/repel.jl:245-253): the route for the snapshot as it stands, P (through the replaced
+// fixed head waiting in it, wtp_relax_set_fixed_dev) hashed into a free buffer — on the session's first rebuild with a
+// measured grid —, and the session's bookkeeping of its grid.
+template <typename T> static int relax_rebuild(wtp_ctx* ctx) {
+    RelaxState& r = ctx->relax;
+    int rc;
+    const int t = pick_free(r, r.bufP, -1);
+    if ((rc = ensure(ctx, ctx->pts[t], sizeof(Pt<T>) * (size_t)(r.n + r.shard_extra)))) return rc;
+    int sp = span_begin(ctx, 0);
+    r.route = sweep_route<T>(ctx, r);
+    if (r.spacing_typ <= 0) { // once per session: the spacing a typical point asks for
+        r.spacing_typ = r.spacing_const;
+        if (r.spacing_kind != WTP_SPACING_CONSTANT) {
+            if ((rc = ensure(ctx, ctx->occ, 64))) return rc;
+            if ((rc = ensure_pinned(ctx, 1024))) return rc;
+            if ((rc = launch_sum<T>(ctx, (const T*)ctx->spacing_pp.p, r.n, (double*)ctx->occ.p))) return rc;
+            WTP_HIP(ctx, hipMemcpyAsync(ctx->host_pinned, ctx->occ.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            if ((rc = sync(ctx))) return rc;
+            r.spacing_typ = ((const double*)ctx->host_pinned)[0] / (double)r.n; // the mean (mean + sigma measured only slower)
+            if (!(r.spacing_typ > 0)) r.spacing_typ = r.spacing_max;
+        }
+    }
+    const Pt<T>* in = pts_of<T>(ctx, r.bufP);
+    Pt<T>* out = pts_of<T>(ctx, t);
+    if (!r.tune.valid) { // once per session: measured cell edge, LDS point area sized from the real grid
+        double rho_eff = 0;
+        Grid<T> hg;
+        HashBuild<T> b = relax_request<T>(ctx, r, in, out, r.n, r.k, r.pending, false);
+        if ((rc = build_hash_tuned<T>(ctx, r.tune, b, &hg, &rho_eff))) return rc;
+        // A spacing far coarser than the cloud (the reference's own tests repel 46 786 face centres 0.22 apart
+        // with a spacing of 3): cells that cover the law's support then hold hundreds of points, every support
+        // ball holds more than k of them and each query would go to the exact path one by one.  Such a session
+        // takes the k-selection sweep on cells sized for the k-th neighbour instead (same results).  Only when
+        // the crowded points are themselves queries: a dense FIXED wall around a few movable points is served
+        // well by the support cells (their balls hold few points), and badly by small cells (the movable
+        // points' k-th neighbour is many cells away).
+        if (route_cs(r.route) && rho_eff > (r.route == SweepRoute::Cs2 ? 5.0 : 4.0 * b.rho_direct) && 2 * r.n_fixed < r.n) {
+            r.cs_disabled = true;
+            r.route = sweep_route<T>(ctx, r);
+            b = relax_request<T>(ctx, r, in, out, r.n, r.k, r.pending, false);
+            if ((rc = build_hash_tuned<T>(ctx, r.tune, b, &hg, &rho_eff))) return rc;
+        }
+        r.cs2_bx = 0;
+        if (r.route == SweepRoute::Cs2) {
+            Grid<float> hgf;
+            memcpy(&hgf, &hg, sizeof(hgf)); // T == float here
+            if ((rc = cs2_tune(ctx, r, hgf, rho_eff))) return rc;
+        } else if (route_cs(r.route)) {
+            int hc = (int)(HCELLS * rho_eff * 1.15) + 128;
+            hc = (hc + 63) / 64 * 64;
+            r.brick_hcap = hc < 640 ? 640 : (hc > 2560 ? 2560 : hc);
+        }
+        if (r.route == SweepRoute::Ksel && (rc = ksel_tune<T>(ctx, r.tune, b, hg, rho_eff))) return rc;
+        r.tune.valid = true;
+        r.tuned_fixed = r.n_fixed;
+        r.grid_fixed = r.n_fixed;
+        r.grid_age = 0;
+    } else {
+        // The bounding box moves by at most a spacing per sweep: it is recomputed every few rebuilds only
+        // (and always after a point was placed by hand, a fixed head was swapped, or with a clipped box).
+        // A block session swaps its ghost head every iteration; the layer keeps its place and, nearly, its size, so the
+        // box of the last full pass still fits (what sticks out is clamped into edge cells: exact, as for a moved point).
+        const bool reuse = grid_reusable(r, r.n_fixed, r.pending.active);
+        r.grid_age = reuse ? r.grid_age + 1 : 0;
+        if (!reuse) r.grid_fixed = r.n_fixed;
+        rc = build_hash<T>(ctx, relax_request<T>(ctx, r, in, out, r.n, r.k, r.pending, reuse));
+    }
+    span_end(ctx, sp);
+    if (rc) return rc;
+    r.pending.active = false;
+    r.bufS = t;
+    r.bufP = t;
+    r.have_tree = true;
+    r.sweeps_since_rebuild = 0;
+    r.moved_by_hand = false;
+    return WTP_OK;
+}
+
 template <typename T> static int relax_step_t(wtp_ctx* ctx, int rebuild, wtp_step_stats* d_slot) {
     RelaxState& r = ctx->relax;
     int rc;
     if (!r.have_tree || r.pending.active) rebuild = 1; // the reference builds its first tree in the setup (src/repel.jl:218)
-    if (rebuild) {
-        // snapshot tail <- p, tree rebuilt (src/repel.jl:245-253): scatter P into a free buffer
-        const int t = pick_free(r, r.bufP, -1);
-        if ((rc = ensure(ctx, ctx->pts[t], sizeof(Pt<T>) * (size_t)(r.n + r.shard_extra)))) return rc;
-        ctx->hash_view = r.pending; // a replaced fixed head waiting in P (wtp_relax_set_fixed_dev)
-        int sp = span_begin(ctx, 0);
-        r.route = sweep_route<T>(ctx, r);
-        if (r.spacing_typ <= 0) { // once per session: the spacing a typical point asks for
-            r.spacing_typ = r.spacing_const;
-            if (r.spacing_kind != WTP_SPACING_CONSTANT) {
-                if ((rc = ensure(ctx, ctx->occ, 64))) return rc;
-                if ((rc = ensure_pinned(ctx, 1024))) return rc;
-                if ((rc = launch_sum<T>(ctx, (const T*)ctx->spacing_pp.p, r.n, (double*)ctx->occ.p))) return rc;
-                WTP_HIP(ctx, hipMemcpyAsync(ctx->host_pinned, ctx->occ.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-                if ((rc = sync(ctx))) return rc;
-                r.spacing_typ = ((const double*)ctx->host_pinned)[0] / (double)r.n; // the mean (mean + sigma measured only slower)
-                if (!(r.spacing_typ > 0)) r.spacing_typ = r.spacing_max;
-            }
-        }
-        RouteGrid g = route_grid(ctx, r);
-        const Pt<T>* in = (const Pt<T>*)ctx->pts[r.bufP].p;
-        Pt<T>* out = (Pt<T>*)ctx->pts[t].p;
-        if (!r.tune.valid) { // once per session: measured cell edge, LDS point area sized from the real grid
-            double rho_eff = 0;
-            Grid<T> hg;
-            if ((rc = build_hash_tuned<T>(ctx, r.tune, in, out, r.n, r.dim, r.k, g.rho, g.min_cell, &hg, &rho_eff))) return rc;
-            // A spacing far coarser than the cloud (the reference's own tests repel 46 786 face centres 0.22 apart
-            // with a spacing of 3): cells that cover the law's support then hold hundreds of points, every support
-            // ball holds more than k of them and each query would go to the exact path one by one.  Such a session
-            // takes the k-selection sweep on cells sized for the k-th neighbour instead (same results).  Only when
-            // the crowded points are themselves queries: a dense FIXED wall around a few movable points is served
-            // well by the support cells (their balls hold few points), and badly by small cells (the movable
-            // points' k-th neighbour is many cells away).
-            if (route_cs(r.route) && rho_eff > (r.route == SweepRoute::Cs2 ? 5.0 : 4.0 * g.rho) && 2 * r.n_fixed < r.n) {
-                r.cs_disabled = true;
-                r.route = sweep_route<T>(ctx, r);
-                g = route_grid(ctx, r);
-                if ((rc = build_hash_tuned<T>(ctx, r.tune, in, out, r.n, r.dim, r.k, g.rho, g.min_cell, &hg, &rho_eff))) return rc;
-            }
-            r.cs2_bx = 0;
-            if (r.route == SweepRoute::Cs2) {
-                Grid<float> hgf;
-                memcpy(&hgf, &hg, sizeof(hgf)); // T == float here
-                if ((rc = cs2_tune(ctx, r, hgf, rho_eff))) return rc;
-            } else if (route_cs(r.route)) {
-                int hc = (int)(HCELLS * rho_eff * 1.15) + 128;
-                hc = (hc + 63) / 64 * 64;
-                r.brick_hcap = hc < 640 ? 640 : (hc > 2560 ? 2560 : hc);
-            }
-            if (r.route == SweepRoute::Ksel) {
-                if ((rc = ksel_tune<T>(ctx, r.tune, in, out, r.n, r.dim, r.k, hg, rho_eff))) return rc;
-                g.rho = r.tune.rho;
-            }
-            r.tune.valid = true;
-            r.tuned_fixed = r.n_fixed;
-            r.grid_fixed = r.n_fixed;
-            r.grid_age = 0;
-        } else {
-            // The bounding box moves by at most a spacing per sweep: it is recomputed every few rebuilds only
-            // (and always after a point was placed by hand, a fixed head was swapped, or with a clipped box).
-            // A block session swaps its ghost head every iteration; the layer keeps its place and, nearly, its size, so the
-            // box of the last full pass still fits (what sticks out is clamped into edge cells: exact, as for a moved point).
-            const bool reuse = grid_reusable(ctx, r.n_fixed, ctx->hash_view.active);
-            ctx->reuse_grid = reuse;
-            r.grid_age = reuse ? r.grid_age + 1 : 0;
-            if (!reuse) r.grid_fixed = r.n_fixed;
-            // the Float64 candidate route orders every sum by (d2, index) explicitly, on the exact path behind it too: no
-            // canonical-order pass (0.37 ms per 10 M Float64 points)
-            ctx->topology_build = r.route == SweepRoute::F64Ksel;
-            rc = build_hash<T>(ctx, in, out, r.n, r.dim, r.k, 0.0, g.rho, g.min_cell, r.tune.scale);
-            ctx->topology_build = false;
-            ctx->reuse_grid = false;
-        }
-        r.last_rho_cs = g.rho;
-        span_end(ctx, sp);
-        ctx->hash_view.active = false;
-        if (rc) return rc;
-        r.pending.active = false;
-        r.bufS = t;
-        r.bufP = t;
-        r.have_tree = true;
-        r.sweeps_since_rebuild = 0;
-        r.moved_by_hand = false;
-    }
+    if (rebuild && (rc = relax_rebuild<T>(ctx))) return rc;
     if (spacing_on_device(r.spacing_kind)) {
         // s = spacing(x_i) at the point's current position (src/repel.jl:251 on rebuilds, :260 in every
         // sweep): the movable tail is re-evaluated before each sweep, the wall keeps its setup values
@@ -1576,20 +1589,27 @@ static int relax_step_any(wtp_ctx* ctx, int rebuild, wtp_step_stats* d_slot) {
 int wtp::relax_step_enqueue(wtp_ctx* ctx, int rebuild, wtp_step_stats* d_slot) { return relax_step_any(ctx, rebuild, d_slot); }
 
 // The block driver knows, before the ghost rows of an iteration have arrived, how many there will be.  When the rebuild that
-// follows is going to keep its grid (grid_reusable, as in relax_step_t), the snapshot's own entries are ranked into the
+// follows is going to keep its grid (grid_reusable, as in relax_rebuild), the snapshot's own entries are ranked into the
 // cells right away, on the context's stream, while the rows travel on another; build_hash then ranks the appended head
-// only.  A wrong guess costs one wasted pass, never a wrong result (build_hash checks what it finds).
+// only.  The guess is the request relax_rebuild will form once wtp_relax_set_fixed_dev has appended the head (the same
+// view, n and k); a wrong guess costs one wasted pass, never a wrong result (build_hash checks what it finds).
 int wtp::relax_prerank(wtp_ctx* ctx, int64_t n_fixed_new) {
     RelaxState& r = ctx->relax;
     ctx->prerank.valid = false;
     if (!r.active || !r.tune.valid || !r.have_tree || r.pending.active) return WTP_OK;
-    if (!grid_reusable(ctx, n_fixed_new, true) || head_remeasures(r, n_fixed_new)) return WTP_OK;
+    if (!grid_reusable(r, n_fixed_new, true) || head_remeasures(r, n_fixed_new)) return WTP_OK;
     const int64_t n_new = r.n - r.n_fixed + n_fixed_new;
     if (ctx->pts[r.bufP].cap < pt_size(r.dtype) * (size_t)(r.n + n_fixed_new)) return WTP_OK; // (the head would be rewritten, not appended)
     const int k = (int64_t)r.k_req < n_new ? r.k_req : (int)n_new;
+    HashView view;
+    view.active = true;
+    view.n_in = r.n + n_fixed_new;
+    view.n_old = r.n;
+    view.fixed_old = (int32_t)r.n_fixed;
+    view.id_shift = (int32_t)(n_fixed_new - r.n_fixed);
     return by_dtype(r.dtype, [&](auto t) {
-        return prerank_old_snapshot<decltype(t)>(ctx, pts_of<decltype(t)>(ctx, r.bufP), r.n, (int32_t)r.n_fixed, n_new,
-                                                 r.n + n_fixed_new, k, r.last_rho_cs, r.tune.scale);
+        using T = decltype(t);
+        return prerank_old_snapshot<T>(ctx, relax_request<T>(ctx, r, pts_of<T>(ctx, r.bufP), nullptr, n_new, k, view, true));
     });
 }
 

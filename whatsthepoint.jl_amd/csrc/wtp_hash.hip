@@ -567,21 +567,20 @@ int launch_axis_hist(wtp_ctx* ctx, const Pt<T>* pts, int64_t n, int dim, const d
     return WTP_OK;
 }
 
-int launch_occupancy(wtp_ctx* ctx, unsigned long long* d_out3) {
+template <typename T> int launch_occupancy(wtp_ctx* ctx, const Grid<T>* g, unsigned long long* d_out3) {
     WTP_HIP(ctx, hipMemsetAsync(d_out3, 0, 3 * sizeof(unsigned long long), ctx->stream));
     hipLaunchKernelGGL(occupancy_kernel, dim3(1024), dim3(kThreads), 0, ctx->stream, (const int32_t*)ctx->cell_start.p,
-                       (const int32_t*)ctx->ncells_dev, d_out3);
+                       (const int32_t*)&g->ncells, d_out3);
     WTP_HIP(ctx, hipGetLastError());
     return WTP_OK;
 }
 
 // The per-build scratch (cell counts and starts, one rank per input entry, the dirty map, the scan's block sums), sized for
-// a structure of n points read from n_in input entries; *fresh = the counts or the map moved (their contents are gone).
-static int hash_scratch(wtp_ctx* ctx, int64_t n, int64_t n_in, int k, double radius, double rho_direct, double cell_scale,
-                        int* cap_out, bool* fresh) {
+// build b; *fresh = the counts or the map moved (their contents are gone).
+template <typename T> static int hash_scratch(wtp_ctx* ctx, const HashBuild<T>& b, int* cap_out, bool* fresh) {
     // k-equivalent of the occupancy the caller fixed (rho = 8 <-> k = 21)
-    const int k_cap = rho_direct > 0 ? (int)(rho_direct * 21.0 / ctx->rho) : (radius > 0 ? 6 : k);
-    const int cap = cell_capacity(ctx, n, k_cap > 0 ? k_cap : 1, cell_scale);
+    const int k_cap = b.rho_direct > 0 ? (int)(b.rho_direct * 21.0 / ctx->rho) : (b.radius > 0 ? 6 : b.k);
+    const int cap = cell_capacity(ctx, b.n, k_cap > 0 ? k_cap : 1, b.cell_scale > 0 ? b.cell_scale : 1.0);
     int rc;
     if ((rc = ensure(ctx, ctx->grid, sizeof(Grid<double>)))) return rc;
     if ((rc = ensure(ctx, ctx->bbox_part, sizeof(double) * 6 * 1024))) return rc;
@@ -589,7 +588,7 @@ static int hash_scratch(wtp_ctx* ctx, int64_t n, int64_t n_in, int k, double rad
     const void* dirty_before = ctx->rank_of.p;
     if ((rc = ensure(ctx, ctx->cell_cnt, sizeof(int32_t) * (size_t)(cap + 1)))) return rc;
     if ((rc = ensure(ctx, ctx->cell_start, sizeof(int32_t) * (size_t)(cap + 2)))) return rc;
-    if ((rc = ensure(ctx, ctx->cell_of, sizeof(int32_t) * (size_t)n_in))) return rc;
+    if ((rc = ensure(ctx, ctx->cell_of, sizeof(int32_t) * (size_t)b.n_in()))) return rc;
     if ((rc = ensure(ctx, ctx->rank_of, (size_t)cap + 64))) return rc; // one byte per cell: filled by more than one run of the input
     const int nscan = (cap + kScanTile - 1) / kScanTile;
     if ((rc = ensure(ctx, ctx->scan_tmp, sizeof(int32_t) * (size_t)(nscan + 1)))) return rc;
@@ -598,19 +597,16 @@ static int hash_scratch(wtp_ctx* ctx, int64_t n, int64_t n_in, int k, double rad
     return WTP_OK;
 }
 
-// First half of the next build_hash, issued early: the entries [0, n_old) of `in` (the snapshot as it stands, its fixed
+// First half of the build `next`, issued early: the entries [0, n_old) of its view (the snapshot as it stands, its fixed
 // head of fixed_old points stale) are ranked into the cells of the grid in place, which the build is going to keep
-// (ctx->reuse_grid).  The build that follows appends n_in - n_old new entries and ranks only those (block driver: the
-// owned points are ranked while the ghost rows travel).  Nothing depends on the guess being right: build_hash
-// checks ctx->prerank against what it is asked to build and otherwise starts over.
-template <typename T>
-int prerank_old_snapshot(wtp_ctx* ctx, const Pt<T>* in, int64_t n_old, int32_t fixed_old, int64_t n_next, int64_t n_in_next,
-                         int k, double rho_direct, double cell_scale) {
-    if (!(cell_scale > 0)) cell_scale = 1.0;
+// (next.keep_grid).  The build then ranks only the n_in - n_old appended entries (block driver: the owned points are
+// ranked while the ghost rows travel).  Nothing depends on the guess being right: build_hash checks
+// ctx->prerank against what it is asked to build (prerank_matches) and otherwise starts over.
+template <typename T> int prerank_old_snapshot(wtp_ctx* ctx, const HashBuild<T>& next) {
     int cap = 0, rc;
     bool fresh = false;
     ctx->prerank.valid = false;
-    if ((rc = hash_scratch(ctx, n_next, n_in_next, k, 0.0, rho_direct, cell_scale, &cap, &fresh))) return rc;
+    if ((rc = hash_scratch(ctx, next, &cap, &fresh))) return rc;
     int32_t* cnt = (int32_t*)ctx->cell_cnt.p;
     uint8_t* dirty = (uint8_t*)ctx->rank_of.p;
     if (!ctx->hash_scratch_clean || fresh) {
@@ -618,99 +614,105 @@ int prerank_old_snapshot(wtp_ctx* ctx, const Pt<T>* in, int64_t n_old, int32_t f
         WTP_HIP(ctx, hipMemsetAsync(dirty, 0, ctx->rank_of.cap, ctx->stream));
     }
     ctx->hash_scratch_clean = false; // (the counts hold the first half from here on)
+    const int64_t n_old = next.view.n_old;
     const int nb = grid_for(n_old, kThreads, 16384);
-    hipLaunchKernelGGL(cell_rank_kernel<T>, dim3(nb), dim3(kThreads), 0, ctx->stream, in, n_old, (const Grid<T>*)ctx->grid.p, cnt,
-                       (int32_t*)ctx->cell_of.p, ctx->topology_build ? (uint8_t*)nullptr : dirty, n_old, fixed_old, ctx->stop_dev);
+    hipLaunchKernelGGL(cell_rank_kernel<T>, dim3(nb), dim3(kThreads), 0, ctx->stream, next.in, n_old, (const Grid<T>*)ctx->grid.p,
+                       cnt, (int32_t*)ctx->cell_of.p, next.canonical ? dirty : (uint8_t*)nullptr, n_old, next.view.fixed_old,
+                       ctx->stop_dev);
     WTP_HIP(ctx, hipGetLastError());
-    ctx->prerank.valid = true;
-    ctx->prerank.in = in;
-    ctx->prerank.n_old = n_old;
-    ctx->prerank.fixed_old = fixed_old;
-    ctx->prerank.cnt = cnt;
-    ctx->prerank.cr = ctx->cell_of.p;
-    ctx->prerank.dirty = dirty;
+    Prerank& p = ctx->prerank;
+    p.valid = true;
+    p.in = next.in;
+    p.n_old = n_old;
+    p.fixed_old = next.view.fixed_old;
+    p.canonical = next.canonical;
+    p.cnt = cnt;
+    p.cr = ctx->cell_of.p;
+    p.dirty = dirty;
     return WTP_OK;
 }
-template int prerank_old_snapshot<float>(wtp_ctx*, const Pt<float>*, int64_t, int32_t, int64_t, int64_t, int, double, double);
-template int prerank_old_snapshot<double>(wtp_ctx*, const Pt<double>*, int64_t, int32_t, int64_t, int64_t, int, double, double);
 
-template <typename T>
-int build_hash(wtp_ctx* ctx, const Pt<T>* in, Pt<T>* out, int64_t n, int dim, int k, double radius, double rho_direct,
-               double min_cell, double cell_scale) {
-    if (!(cell_scale > 0)) cell_scale = 1.0;
-    // n = points of the structure; the input array may be longer (ctx->hash_view: stale fixed points
-    // still in place, new ones appended)
-    const HashView hv = ctx->hash_view;
-    const int64_t n_in = hv.active ? hv.n_in : n;
+// The first half of build b is done: prerank_old_snapshot ranked the old snapshot of this very view, with the same marks,
+// into the grid b keeps and the scratch it has now (fresh: the scratch moved since).
+template <typename T> static bool prerank_matches(const wtp_ctx* ctx, const HashBuild<T>& b, bool fresh) {
+    const Prerank& p = ctx->prerank;
+    const bool same_request = b.keep_grid && b.view.active && p.in == (const void*)b.in && p.n_old == b.view.n_old &&
+                              p.fixed_old == b.view.fixed_old && p.canonical == b.canonical;
+    const bool same_scratch = !fresh && p.cnt == ctx->cell_cnt.p && p.cr == ctx->cell_of.p && p.dirty == ctx->rank_of.p;
+    return p.valid && same_request && same_scratch;
+}
+
+template <typename T> int build_hash(wtp_ctx* ctx, const HashBuild<T>& b) {
+    const double cell_scale = b.cell_scale > 0 ? b.cell_scale : 1.0;
+    // n = points of the structure; the input array may be longer (b.view: stale fixed points still in place, new ones
+    // appended)
+    const HashView& hv = b.view;
+    const int64_t n = b.n, n_in = b.n_in();
     const int64_t v_old = hv.active ? hv.n_old : 0;
     const int32_t v_fixed_old = hv.active ? hv.fixed_old : 0, v_shift = hv.active ? hv.id_shift : 0;
     const int nbb = grid_for(n_in, kThreads, 1024);
     int cap = 0, rc;
     bool fresh = false;
-    if ((rc = hash_scratch(ctx, n, n_in, k, radius, rho_direct, cell_scale, &cap, &fresh))) return rc;
+    if ((rc = hash_scratch(ctx, b, &cap, &fresh))) return rc;
     const int nscan = (cap + kScanTile - 1) / kScanTile;
 
+    const Pt<T>* in = b.in;
+    Pt<T>* out = b.out;
     Grid<T>* g = (Grid<T>*)ctx->grid.p;
     T* part = (T*)ctx->bbox_part.p;
     int32_t* cnt = (int32_t*)ctx->cell_cnt.p;
     int32_t* start = (int32_t*)ctx->cell_start.p;
     int32_t* cr = (int32_t*)ctx->cell_of.p;
     uint8_t* dirty = (uint8_t*)ctx->rank_of.p;
+    uint8_t* marks = b.canonical ? dirty : nullptr;
     int32_t* bs = (int32_t*)ctx->scan_tmp.p;
     hipStream_t st = ctx->stream;
 
     // target occupancy: c = 1.17 r_k  (r_k = k-th neighbour distance at uniform density)
-    double rho_k = (dim == 3 ? 0.381 : 0.436) * (double)(k > 0 ? k : 21) * (ctx->rho / 8.0);
-    if (rho_direct > 0) rho_k = rho_direct; // caller fixes the occupancy (compact-support sweep)
+    double rho_k = (b.dim == 3 ? 0.381 : 0.436) * (double)(b.k > 0 ? b.k : 21) * (ctx->rho / 8.0);
+    if (b.rho_direct > 0) rho_k = b.rho_direct; // caller fixes the occupancy (compact-support sweep)
     if (rho_k < 1.0) rho_k = 1.0;
 
     // Counts and dirty map are consumed (zeroed) by the scan and by the canonical-order pass of every build, so
     // a build normally finds them all-zero: the two fills (4 + 1 bytes per cell) run only after a reallocation or
     // after a build that did not complete.
-    // ctx->reuse_grid (one-shot, set by the relax session): keep the Grid of the previous build — origin, cell edge,
-    // cell counts — and skip the bounding-box pass.  A point that has left the old box since is clamped into an
-    // edge cell, which the kernels treat as unbounded outward, so the search stays exact.
-    const bool reuse = ctx->reuse_grid;
-    ctx->reuse_grid = false;
-    // the old snapshot's entries may have been ranked already (prerank_old_snapshot): same array, same view, same
-    // scratch, same grid — then only the appended entries are left
-    const Prerank pre = ctx->prerank;
+    // b.keep_grid (the relax session's rebuilds): keep the Grid of the previous build — origin, cell edge, cell
+    // counts — and skip the bounding-box pass.  A point that has left the old box since is clamped into an edge
+    // cell, which the kernels treat as unbounded outward, so the search stays exact.
+    // The old snapshot's entries may have been ranked already (prerank_old_snapshot): then only the appended
+    // entries are left.
+    const bool half_done = prerank_matches(ctx, b, fresh);
     ctx->prerank.valid = false;
-    const bool half_done = pre.valid && reuse && hv.active && !fresh && pre.in == (const void*)in && pre.n_old == v_old &&
-                           pre.fixed_old == v_fixed_old && pre.cnt == (const void*)cnt && pre.cr == (const void*)cr &&
-                           pre.dirty == (const void*)dirty;
     if (!half_done && (!ctx->hash_scratch_clean || fresh)) {
         WTP_HIP(ctx, hipMemsetAsync(cnt, 0, ctx->cell_cnt.cap, st));
         WTP_HIP(ctx, hipMemsetAsync(dirty, 0, ctx->rank_of.cap, st));
     }
     ctx->hash_scratch_clean = false;
     ctx->preranked_builds += half_done ? 1 : 0;
-    if (!reuse) {
+    if (!b.keep_grid) {
         hipLaunchKernelGGL(bbox_kernel<T>, dim3(nbb), dim3(kThreads), 0, st, in, n_in, part, v_old, v_fixed_old);
-        hipLaunchKernelGGL(grid_setup_kernel<T>, dim3(1), dim3(64), 0, st, part, nbb, g, n, dim, rho_k, radius, min_cell,
-                           cap, cell_scale, ctx->box_active ? (const double*)ctx->box_dev.p : (const double*)nullptr, ctx->stop_dev);
+        hipLaunchKernelGGL(grid_setup_kernel<T>, dim3(1), dim3(64), 0, st, part, nbb, g, n, b.dim, rho_k, b.radius, b.min_cell,
+                           cap, cell_scale, b.box, ctx->stop_dev);
     }
-    ctx->ncells_dev = &g->ncells;
     const int nb = grid_for(n_in, kThreads, 16384);
     if (half_done) {
         if (n_in > v_old) // (the appended entries: nothing stale among them)
             hipLaunchKernelGGL(cell_rank_kernel<T>, dim3(grid_for(n_in - v_old, kThreads, 16384)), dim3(kThreads), 0, st, in + v_old,
-                               n_in - v_old, g, cnt, cr + v_old, ctx->topology_build ? (uint8_t*)nullptr : dirty, (int64_t)0, 0,
-                               ctx->stop_dev);
+                               n_in - v_old, g, cnt, cr + v_old, marks, (int64_t)0, 0, ctx->stop_dev);
     } else {
-        hipLaunchKernelGGL(cell_rank_kernel<T>, dim3(nb), dim3(kThreads), 0, st, in, n_in, g, cnt, cr,
-                           ctx->topology_build ? (uint8_t*)nullptr : dirty, v_old, v_fixed_old, ctx->stop_dev);
+        hipLaunchKernelGGL(cell_rank_kernel<T>, dim3(nb), dim3(kThreads), 0, st, in, n_in, g, cnt, cr, marks, v_old, v_fixed_old,
+                           ctx->stop_dev);
     }
     hipLaunchKernelGGL(scan_reduce_kernel<T>, dim3(nscan), dim3(kThreads), 0, st, cnt, g, bs);
     hipLaunchKernelGGL(scan_apply_kernel<T>, dim3(nscan), dim3(kThreads), 0, st, cnt, bs, g, start, ctx->stop_dev);
     hipLaunchKernelGGL(scatter_kernel<T>, dim3(nb), dim3(kThreads), 0, st, in, n_in, cr, g, start, out, v_old, v_fixed_old,
                        v_shift, ctx->stop_dev);
-    if (!ctx->topology_build) {
+    if (b.canonical) {
         hipLaunchKernelGGL(canon_kernel<T>, dim3(grid_for((cap + 15) / 16, kThreads, 4096)), dim3(kThreads), 0, st, out, start,
                            dirty, g, ctx->stop_dev);
     }
     WTP_HIP(ctx, hipGetLastError());
-    ctx->hash_scratch_clean = true; // (the scan consumed the counts; a topology build wrote no marks, the canonical-order pass cleared the others)
+    ctx->hash_scratch_clean = true; // (the scan consumed the counts; a build without marks wrote none, the canonical-order pass cleared the others)
     return WTP_OK;
 }
 
@@ -1202,7 +1204,9 @@ int launch_refix(wtp_ctx* ctx, const Pt<T>* in, int64_t n_old, int64_t n_fixed_o
     template int launch_append_fixed<T>(wtp_ctx*, const Pt<T>*, int64_t, Pt<T>*);                       \
     template int launch_refix<T>(wtp_ctx*, const Pt<T>*, int64_t, int64_t, int64_t, const Pt<T>*, Pt<T>*, int32_t*); \
     template int load_points<T>(wtp_ctx*, const T*, Pt<T>*, int64_t, int);                              \
-    template int build_hash<T>(wtp_ctx*, const Pt<T>*, Pt<T>*, int64_t, int, int, double, double, double, double); \
+    template int build_hash<T>(wtp_ctx*, const HashBuild<T>&);                                          \
+    template int prerank_old_snapshot<T>(wtp_ctx*, const HashBuild<T>&);                                \
+    template int launch_occupancy<T>(wtp_ctx*, const Grid<T>*, unsigned long long*);                     \
     template int launch_unpermute<T>(wtp_ctx*, const Pt<T>*, int64_t, int64_t, int, T*);                \
     template int launch_unpermute_point_data<T>(wtp_ctx*, const Pt<T>*, int64_t, int64_t, const T*,    \
                                                 const T*, const int32_t*, T*, T*, int32_t*);            \

@@ -201,14 +201,36 @@ struct HashView {
     int32_t id_shift = 0;
 };
 
+// One hash build (build_hash in wtp_hash.hip): from the Pt array `in` the sorted `out`, cell_start and the grid.  The
+// constructor takes what every build names; the rest reads as what the caller sets, on top of these defaults.
+template <typename T> struct HashBuild {
+    const Pt<T>* in;
+    Pt<T>* out;
+    int64_t n;                   // points of the structure (a view may read them from a longer input array)
+    int dim;
+    int k;                       // scales the target occupancy
+    double radius = 0.0;         // > 0: cell edge >= radius (RadiusTopology)
+    double rho_direct = 0.0;     // > 0: the caller fixes the occupancy (points per cell) instead
+    double min_cell = 0.0;       // floor of the cell edge (the force law's support)
+    double cell_scale = 1.0;     // measured cell scale (GridTune::scale)
+    HashView view;               // inactive: `in` holds exactly the n points
+    bool keep_grid = false;      // keep the previous Grid (no bounding-box pass): the relax session's rebuilds
+    bool canonical = true;       // order each cell by id (dirty marks, canon_kernel); false where rows are ordered by (d2, id) explicitly
+    const double* box = nullptr; // clip the bounding box to this device box {lo xyz, hi xyz} (GridTune::clipped)
+    HashBuild(const Pt<T>* in_, Pt<T>* out_, int64_t n_, int dim_, int k_) : in(in_), out(out_), n(n_), dim(dim_), k(k_) {}
+    int64_t n_in() const { return view.active ? view.n_in : n; } // entries of the input array
+};
+
 // Part of a hash build issued ahead of time (block driver: while the ghost rows of the iteration travel): the old
 // snapshot's entries [0, n_old) of `in` are already ranked into the cell counts.  One-shot; build_hash takes it over only
-// when every pointer and number still matches, otherwise it zeroes the counts and ranks everything itself.
+// when it matches the build it is asked for (prerank_matches in wtp_hash.hip), otherwise it zeroes the counts and ranks
+// everything itself.
 struct Prerank {
     bool valid = false;
     const void* in = nullptr;
     int64_t n_old = 0;
     int32_t fixed_old = 0;
+    bool canonical = true; // dirty marks written
     const void *cnt = nullptr, *cr = nullptr, *dirty = nullptr;
 };
 
@@ -218,6 +240,7 @@ struct Prerank {
 struct GridTune {
     bool loose = false;      // Float64 sweeps: a cloud within 5 % of n fits, and a scale measured on a clipped box is kept (build_grid_cached)
     bool valid = false;
+    bool clipped = false;    // the measured grid lies over a quantile box (find_robust_box, in ctx->box_dev): the rebuilds of a relax session clip to it
     int64_t n = 0;
     int dim = 0, kq = 0;     // kq: neighbours sought per query (self included)
     bool ksel = false;       // the grid was built for the k-selection kernels of wtp_ksel.hip
@@ -272,7 +295,6 @@ struct RelaxState {
     bool shard_grid_reuse = false; // block sessions: the grid is kept across a swapped ghost head (points outside it pile into edge cells, which every search treats as unbounded outward)
     int64_t grid_fixed = -1;       // fixed points the current grid's bounding box was computed with
     GridTune f64k_tune{/*loose=*/true}; // fp64 sweeps through fp32 candidates: the float copy's grid
-    double last_rho_cs = 0.0;      // occupancy argument of the session's last hash build (relax_prerank sizes its scratch alike)
     bool wall_active = false; // octree method: _constrain_octree runs after every sweep (wtp_relax_set_wall)
     double wall_offset = 0;   // inward nudge of a projected boundary point (src/repel.jl:143)
     int64_t wall_nm = 0;      // movable points the wall arrays are sized for
@@ -314,18 +336,12 @@ struct wtp_ctx {
     wtp::DevBuf raw_in;        // AoS staging of host input
     wtp::DevBuf cell_of, rank_of, cell_cnt, cell_start, scan_tmp;
     wtp::DevBuf grid, bbox_part, occ;
-    wtp::HashView hash_view;   // consumed by the next build_hash call (set and cleared by the caller)
     wtp::DevBuf box_dev;       // robust box {lo xyz, hi xyz} (doubles) + histogram scratch behind it
-    bool topology_build = false; // set around the hash builds of KNN / radius topology calls: their rows are ordered by (d2, id) explicitly, so the
-                                 // within-cell order by id (canon_kernel: 0.3 of a 1.1 ms KNN call on unsorted input) buys nothing there
-    bool reuse_grid = false;   // one-shot: the next build_hash keeps the previous Grid (no bounding-box pass)
-    bool box_active = false;   // grid_setup clips the bounding box to box_dev (outliers piled into edge cells)
-    const void* ncells_dev = nullptr; // device address of Grid::ncells of the last build_hash
     wtp::DevBuf idx_out, dist_out, counts_out;
     wtp::DevBuf cand_idx, cand_dist, f32_pts; // fp64 topology: fp32 candidate lists and the float copy of the cloud
-    // fp64 sweeps through fp32 candidates (wtp_sweep64.hip): the session's grid and cell table parked while the float copy's
-    // are built and searched; the fp64 points and their session slots in the float copy's order; the search's own lists
-    wtp::DevBuf grid_b, cell_start_b, f64k_s64, f64k_slot, f64k_lists, f64k_cnt;
+    // fp64 sweeps through fp32 candidates (wtp_sweep64.hip): the session's grid, cell table and box parked while the float
+    // copy's are built and searched; the fp64 points and their session slots in the float copy's order; the search's own lists
+    wtp::DevBuf grid_b, cell_start_b, box_b, f64k_s64, f64k_slot, f64k_lists, f64k_cnt;
     wtp::DevBuf forces, nn_dist, nn_id, spacing_pp;
     wtp::DevBuf partials, stats, fb_list, fb_count, fb2_list, fb2_count, nn_list;
     wtp::DevBuf rad_pos;           // counter block: [0, 8) next free id of the arena (wtp_radb.hip takes pieces of it), [8, 12) bricks listed
@@ -417,16 +433,12 @@ void span_end(wtp_ctx* ctx, int span);
 void spans_collect(wtp_ctx* ctx);
 
 // ---- launch wrappers (implemented per translation unit) ----------------------------------------
-// hash build: from Pt array `in` (n points) produce sorted `out`, cell_start and the grid.
-// radius > 0 forces cell edge >= radius (RadiusTopology); k scales the target occupancy.
-template <typename T>
-int build_hash(wtp_ctx* ctx, const Pt<T>* in, Pt<T>* out, int64_t n, int dim, int k, double radius,
-               double rho_direct = 0.0, double min_cell = 0.0, double cell_scale = 1.0);
-template <typename T>
-int prerank_old_snapshot(wtp_ctx* ctx, const Pt<T>* in, int64_t n_old, int32_t fixed_old, int64_t n_next, int64_t n_in_next,
-                         int k, double rho_direct, double cell_scale);
-// occupancy of the grid the last build_hash made: d_out3 = [sum cnt^2, sum cnt, max cnt]
-int launch_occupancy(wtp_ctx* ctx, unsigned long long* d_out3);
+// hash build (HashBuild above) into ctx->grid, ctx->cell_start and b.out
+template <typename T> int build_hash(wtp_ctx* ctx, const HashBuild<T>& b);
+// the first half of the build `next` ahead of time (ctx->prerank): its view's old snapshot ranked into the kept grid
+template <typename T> int prerank_old_snapshot(wtp_ctx* ctx, const HashBuild<T>& next);
+// occupancy of the cells of grid g (the one in ctx->cell_start): d_out3 = [sum cnt^2, sum cnt, max cnt]
+template <typename T> int launch_occupancy(wtp_ctx* ctx, const Grid<T>* g, unsigned long long* d_out3);
 template <typename T> int launch_sum(wtp_ctx* ctx, const T* d_v, int64_t n, double* d_out);
 int launch_offsets_scan(wtp_ctx* ctx, const int32_t* d_cnt, int64_t n, int64_t* d_tmp, int64_t* d_off);
 size_t offsets_scan_tmp_bytes(int64_t n);
