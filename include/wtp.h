@@ -433,6 +433,54 @@ int wtp_block_close(wtp_ctx* ctx);
  * are spatial neighbours (src/octree/spatial_octree.jl:283 `find_leaf` is the reference's only use of that order). */
 int wtp_block_grid(int nranks, int p_out[3]);
 int wtp_block_morton_rank(int ix, int iy, int iz, const int p[3]);
+/* ---- sharded set_topology ("same decomposition, no iteration; output stays sharded") ----------------
+ * KNNTopology / RadiusTopology rows (src/topology.jl:79-97) of a cloud that stays split across ranks, e.g. what
+ * wtp_block_get leaves behind after a block repel (call wtp_block_get, wtp_block_close, then these).  Every rank holds
+ * its owned points and their global ids; the assembled cloud is cloud[gid[i]] = xyz[i] on the rank that owns point i,
+ * so the gids of all ranks together are exactly 0 .. N_total - 1 (N_total < 2^31).  Per call and rank:
+ *   1. one all-gather of {owned count, bounding box of the owned points, gid range and fingerprint, status, arguments}:
+ *      every check that needs global knowledge (k against N_total, k <= 128, gids in range and each owned once, the same
+ *      k / r everywhere, a NULL output with n_owned > 0, a busy context) runs on the gathered words, so ALL RANKS
+ *      RETURN THE SAME STATUS and none is left waiting in a collective.  A rank's region is the bounding box of its own
+ *      points (no caller-supplied box: points a lazy migration left outside their box cost ghosts, never correctness).
+ *   2. ghosts: rank r sends rank q every owned point inside q's box grown by q's own width w_q (inclusive, fp32
+ *      thresholds rounded outward), 16-byte rows {x, y, z, bits(gid)}, in one grouped exchange whose row counts
+ *      reached every rank in an all-gather first.
+ *   3. the local set [owned + ghosts] is laid out in ascending gid order, so the search's (d², index) order IS the
+ *      single-GPU (d², gid) order: ties inside a row and at the k-th place resolve as on one GPU.
+ *   4. the single-context k-NN / radius kernels search the local set.
+ *   5. row i is complete if its k-th d² (radius: r²) lies strictly below the squared distance to the nearest face of
+ *      the rank's box grown by w_q, with a margin for the fp32 rounding of d²; a face beyond the global bounding box
+ *      counts as infinitely far.  If any rank has an incomplete row, every such rank widens w_q by 1.5x and all redo
+ *      2-5.  Radius: w_q is r rounded outward, so the first round completes every row.
+ * Rows carry GLOBAL ids and equal, bit for bit, the rows wtp_knn / wtp_radius_fill return for the assembled cloud;
+ * distances too.  fp32, 3-D.  Collective; uses the context's RCCL communicator (wtp_comm_init with the same rank /
+ * nranks) or wtp_block_set_transport's callbacks.  WTP_ERR_STATE while a relax or block session is open on the
+ * context.  */
+typedef struct wtp_block_topo_info {
+    double  width;        /* ghost width this rank ended with                                                  */
+    int64_t n_ghost;      /* foreign points in this rank's local set                                           */
+    int64_t n_recv_rows;  /* rows received in the last exchange                                                */
+    int32_t n_peers;      /* ranks this rank received from in the last round                                   */
+    int32_t widened;      /* widening rounds (all ranks report the same number)                                */
+    int32_t host_syncs;   /* host synchronisations this call made                                              */
+    int32_t reserved;
+} wtp_block_topo_info;
+
+/* Collective.  Rows of this rank's owned points, in the caller's order: row i equals wtp_knn's row of point gid[i] of
+ * the assembled cloud, in global ids.  d_xyz: n_owned x 3 fp32 (device), d_gid: n_owned int64 (device); n_owned may
+ * be 0.  width <= 0: the library estimates a first width from each rank's point count and box.  d_idx_out:
+ * n_owned x k int64 (device); d_dist_out: n_owned x k fp32 (device) or NULL; info may be NULL.  */
+int wtp_block_knn(wtp_ctx* ctx, int rank, int nranks, const void* d_xyz, const int64_t* d_gid, int64_t n_owned, int k,
+                  int include_self, double width, int64_t* d_idx_out, float* d_dist_out, wtp_block_topo_info* info);
+/* Collective first phase of the sharded RadiusTopology.  d_offsets_out: n_owned + 1 int64 (device; exclusive scan of
+ * this rank's row lengths, caller order).  The rows are computed here and kept on the context for the fill.  */
+int wtp_block_radius_offsets(wtp_ctx* ctx, int rank, int nranks, const void* d_xyz, const int64_t* d_gid, int64_t n_owned,
+                             double r, int64_t* d_offsets_out, wtp_block_topo_info* info);
+/* Local second phase: d_idx_out (device, offsets[n_owned] int64) gets the rows in global ids, each sorted ascending by
+ * (d², gid): equal to wtp_radius_fill's rows of the assembled cloud.  WTP_ERR_STATE without a preceding
+ * wtp_block_radius_offsets on this context.  */
+int wtp_block_radius_fill(wtp_ctx* ctx, int64_t* d_idx_out);
 /* Grouped point-to-point primitive of the exchange, exposed for callers that drive their own iteration: message j is
  * sent to and received from rank peers[j], rows of 16 bytes, device buffers, stream-ordered on the context's stream.
  * Counts must agree on both sides (ncclSend/ncclRecv semantics).  peers[j] may equal the caller's own rank. */

@@ -58,6 +58,11 @@ class BlockInfo(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class BlockTopoInfo(C.Structure):
+    _fields_ = [("width", C.c_double), ("n_ghost", C.c_int64), ("n_recv_rows", C.c_int64), ("n_peers", C.c_int32),
+                ("widened", C.c_int32), ("host_syncs", C.c_int32), ("reserved", C.c_int32)]
+
+
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                           C.POINTER(C.c_void_p), C.POINTER(C.c_int64))
@@ -130,6 +135,9 @@ SIGNATURES = {
     "wtp_block_close": (_i, [_vp]),
     "wtp_block_grid": (_i, [_i, C.POINTER(_i)]),
     "wtp_block_morton_rank": (_i, [_i, _i, _i, C.POINTER(_i)]),
+    "wtp_block_knn": (_i, [_vp, _i, _i, _vp, _vp, _i64, _i, _i, _d, _vp, _vp, C.POINTER(BlockTopoInfo)]),
+    "wtp_block_radius_offsets": (_i, [_vp, _i, _i, _vp, _vp, _i64, _d, _vp, C.POINTER(BlockTopoInfo)]),
+    "wtp_block_radius_fill": (_i, [_vp, _vp]),
     "wtp_comm_exchange_peers": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_vp), C.POINTER(_i64)]),
     "wtp_comm_allgather_dev": (_i, [_vp, _vp, _vp, _i64]),
     "wtp_timers_get": (_i, [_vp, C.POINTER(_d)]),

@@ -224,6 +224,108 @@ class BlockRelax:
         self.close()
 
 
+# ---- sharded set_topology (wtp_block_knn, wtp_block_radius_*) -----------------------------------------------------------
+def _topo_inputs(owned_xyz, gid) -> int:
+    """Shapes and dtypes of a rank's share, checked on the host before anything touches a GPU; returns n_owned."""
+    def meta(a):
+        if not isinstance(a, np.ndarray) and hasattr(a, "data_ptr"):  # a torch tensor
+            return tuple(a.shape), str(a.dtype).replace("torch.", "")
+        a = np.asarray(a)
+        return a.shape, a.dtype.name
+
+    xs, xd = meta(owned_xyz)
+    gs, gd = meta(gid)
+    if len(xs) != 2 or xs[1] != 3:
+        raise L.WtpArgumentError(f"owned_xyz must have shape (n, 3), got {xs}")
+    if xd != "float32":
+        raise L.WtpArgumentError(f"owned_xyz must be float32 (the sharded topology is fp32), got {xd}")
+    if tuple(gs) != (xs[0],):
+        raise L.WtpArgumentError(f"gid must have shape ({xs[0]},), got {gs}")
+    if gd != "int64":
+        raise L.WtpArgumentError(f"gid must be int64, got {gd}")
+    return int(xs[0])
+
+
+def _on_device(a, dev):
+    import torch
+
+    if not torch.is_tensor(a):
+        a = torch.from_numpy(np.ascontiguousarray(a))
+    return a.to(dev).contiguous()
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+
+
+class _TransportFor:
+    """wtp_block_set_transport for the duration of one collective call, then back to RCCL."""
+
+    def __init__(self, ctx, transport):
+        self.ctx, self.transport = ctx, transport
+
+    def __enter__(self):
+        if self.transport is not None:
+            L.check(self.ctx._h, self.ctx._lib.wtp_block_set_transport(self.ctx._h, C.byref(self.transport.struct)))
+
+    def __exit__(self, *exc):
+        if self.transport is not None:
+            self.ctx._lib.wtp_block_set_transport(self.ctx._h, None)
+
+
+def _topo_info(i: L.BlockTopoInfo):
+    return {name: getattr(i, name) for name, _ in L.BlockTopoInfo._fields_ if name != "reserved"}
+
+
+def block_knn(ctx, rank: int, nranks: int, owned_xyz, gid, k: int, include_self: bool = False, return_dist: bool = False,
+              width: float = 0.0, transport=None):
+    """KNNTopology rows of this rank's owned points, in global ids (collective: every rank calls it).
+    owned_xyz (n, 3) float32 / gid (n,) int64: numpy arrays or torch tensors.  Returns (idx int64 (n, k), dist float32
+    (n, k) or None, info) as torch tensors on the context's device; row i equals ctx.knn's row gid[i] of the assembled
+    cloud.  width <= 0: the library picks the first ghost width."""
+    k = int(k)
+    if k < 1:
+        raise L.WtpArgumentError("k must be >= 1")
+    n = _topo_inputs(owned_xyz, gid)
+    import torch
+
+    dev = torch.device("cuda", ctx.device)
+    x, g = _on_device(owned_xyz, dev), _on_device(gid, dev)
+    idx = torch.empty((n, k), dtype=torch.int64, device=dev)
+    dist = torch.empty((n, k), dtype=torch.float32, device=dev) if return_dist else None
+    info = L.BlockTopoInfo()
+    torch.cuda.synchronize(dev)
+    with _TransportFor(ctx, transport):
+        rc = ctx._lib.wtp_block_knn(ctx._h, int(rank), int(nranks), _ptr(x), _ptr(g), n, k, int(bool(include_self)), float(width),
+                                    _ptr(idx), _ptr(dist), C.byref(info))
+    L.check(ctx._h, rc)
+    return idx, dist, _topo_info(info)
+
+
+def block_radius(ctx, rank: int, nranks: int, owned_xyz, gid, r: float, transport=None):
+    """RadiusTopology rows of this rank's owned points, in global ids (collective: every rank calls it).  Returns
+    (offsets int64 (n + 1), idx int64 (nnz), info) as torch tensors on the context's device; row i equals ctx.radius's
+    row gid[i] of the assembled cloud, translated to global ids."""
+    r = float(r)
+    if not (r > 0 and math.isfinite(r)):
+        raise L.WtpArgumentError("r must be finite and > 0")
+    n = _topo_inputs(owned_xyz, gid)
+    import torch
+
+    dev = torch.device("cuda", ctx.device)
+    x, g = _on_device(owned_xyz, dev), _on_device(gid, dev)
+    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    info = L.BlockTopoInfo()
+    torch.cuda.synchronize(dev)
+    with _TransportFor(ctx, transport):
+        rc = ctx._lib.wtp_block_radius_offsets(ctx._h, int(rank), int(nranks), _ptr(x), _ptr(g), n, r, _ptr(off), C.byref(info))
+    L.check(ctx._h, rc)
+    nnz = int(off[-1].item())
+    idx = torch.empty(max(nnz, 1), dtype=torch.int64, device=dev)
+    L.check(ctx._h, ctx._lib.wtp_block_radius_fill(ctx._h, _ptr(idx)))
+    return off, idx[:nnz], _topo_info(info)
+
+
 # ---- transports for wtp_block_set_transport ---------------------------------------------------------------------------
 class _Transport:
     def __init__(self, allgather, exchange):

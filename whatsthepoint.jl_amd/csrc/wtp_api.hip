@@ -657,6 +657,7 @@ WTP_API int wtp_create(const int* device_ordinals, int n_dev, wtp_ctx** out) {
 
 WTP_API int wtp_destroy(wtp_ctx* ctx) {
     if (ctx) block_destroy(ctx);
+    if (ctx) block_topo_destroy(ctx);
     if (!ctx) return WTP_OK;
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
@@ -953,6 +954,37 @@ WTP_API int wtp_radius_fill(wtp_ctx* ctx, const int64_t* offsets, int32_t* idx_o
         WTP_HIP(ctx, hipMemcpyAsync(idx_out, ctx->idx_out.p, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost,
                                     ctx->stream));
     return sync(ctx);
+}
+
+// ---- the sharded topology's local searches (wtp_block_topo.hip): the kernels of wtp_knn_dev / wtp_radius_* on the
+// rank's gid-ordered local set, fp32 3-D, on the device; the caller has checked the context is idle
+int wtp::topo_knn_local(wtp_ctx* ctx, const float* d_xyz, int64_t n, int k, int include_self, int32_t* d_idx, float* d_dist) {
+    return knn_dev_t<float>(ctx, d_xyz, n, 3, k, include_self, d_idx, d_dist);
+}
+
+int wtp::topo_radius_local(wtp_ctx* ctx, const float* d_xyz, int64_t n, double r, int32_t* d_counts, int64_t* d_off,
+                           DevBuf& d_idx, int64_t* nnz) {
+    int rc;
+    ctx->rad_valid = false; // (wtp_radius_fill has nothing to continue from: the rows go to the caller's buffers)
+    ctx->rad_offsets_dev = false;
+    ctx->relax.have_tree = false;
+    if ((rc = ensure(ctx, ctx->raw_in, sizeof(float) * 3 * (size_t)n))) return rc;
+    WTP_HIP(ctx, hipMemcpyAsync(ctx->raw_in.p, d_xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
+    if ((rc = radius_count_t<float>(ctx, n, 3, r, d_counts))) return rc;
+    if ((rc = ensure(ctx, ctx->scratch, offsets_scan_tmp_bytes(n)))) return rc;
+    if ((rc = launch_offsets_scan(ctx, d_counts, n, (int64_t*)ctx->scratch.p, d_off))) return rc;
+    if ((rc = ensure_pinned(ctx, 64))) return rc;
+    WTP_HIP(ctx, hipMemcpyAsync(ctx->host_pinned, d_off + n, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = sync(ctx))) return rc;
+    *nnz = *(const int64_t*)ctx->host_pinned;
+    if ((rc = ensure(ctx, d_idx, sizeof(int32_t) * (size_t)(*nnz + 1)))) return rc;
+    if ((rc = ensure(ctx, ctx->fb2_list, sizeof(int32_t) * (size_t)n))) return rc;
+    if ((rc = ensure(ctx, ctx->fb2_count, 64))) return rc;
+    ctx->rad_n = n;
+    ctx->rad_dim = 3;
+    ctx->rad_dtype = WTP_F32;
+    ctx->rad_r = r;
+    return radius_fill_t<float>(ctx, d_off, (int32_t*)d_idx.p);
 }
 
 // ---- variable spacings: kd-tree over the law's boundary points, cached per context -----------------

@@ -539,6 +539,20 @@ static int blk_plan(wtp_ctx* ctx, BlockState* b, const wtp_step_stats* d_stats, 
     return WTP_OK;
 }
 
+// ---- what the sharded topology (wtp_block_topo.hip) takes from the driver -------------------------------------------
+bool block_session_open(wtp_ctx* ctx) { return bs_of(ctx) && bs_of(ctx)->active; }
+
+const wtp_transport* block_host_transport(wtp_ctx* ctx) {
+    BlockState* b = bs_of(ctx);
+    return b && b->host_transport ? &b->tr : nullptr;
+}
+
+int launch_blk_scan(wtp_ctx* ctx, int32_t* span_counts, int64_t nspans, int ncol, int32_t* totals) {
+    hipLaunchKernelGGL(blk_scan_kernel, dim3(ncol), dim3(256), 0, ctx->stream, span_counts, nspans, ncol, totals);
+    WTP_HIP(ctx, hipGetLastError());
+    return WTP_OK;
+}
+
 } // namespace wtp
 
 using namespace wtp;

@@ -382,6 +382,7 @@ struct wtp_ctx {
     int kd_dim = 0, kd_dtype = -1;
     int64_t n_syncs = 0;       // host synchronisations of the context's stream so far (wtp_block_info.host_syncs counts with it)
     void* block = nullptr;     // wtp::BlockState (wtp_block.hip): this rank's share of a block-decomposed repel
+    void* block_topo = nullptr; // wtp::TopoState (wtp_block_topo.hip): buffers of the sharded KNN / radius rows
     void* comm = nullptr;      // ncclComm_t (wtp_comm.hip); rank and size of the communicator
     int comm_rank = 0, comm_size = 0;
     wtp::DevBuf comm_scratch;
@@ -572,6 +573,15 @@ int launch_cs_all_slots(wtp_ctx* ctx, int32_t* list, int32_t n, int32_t* count);
 int launch_cs_ball64(wtp_ctx* ctx, SearchArgs<double>& a, int32_t* rest_list, int32_t* rest_count); // wtp_ball64.hip
 int relax_prerank(wtp_ctx* ctx, int64_t n_fixed_new); // first half of the next rebuild's hash, ahead of wtp_relax_set_fixed_dev (see wtp_api.hip)
 void block_destroy(wtp_ctx* ctx);                                          // frees ctx->block (wtp_destroy)
+// sharded topology (wtp_block_topo.hip) <-> block driver (wtp_block.hip) and the single-context searches (wtp_api.hip)
+void block_topo_destroy(wtp_ctx* ctx);                                     // frees ctx->block_topo (wtp_destroy)
+bool block_session_open(wtp_ctx* ctx);                                     // a wtp_block_open session is active
+const wtp_transport* block_host_transport(wtp_ctx* ctx);                   // wtp_block_set_transport's callbacks, or NULL: RCCL
+int launch_blk_scan(wtp_ctx* ctx, int32_t* span_counts, int64_t nspans, int ncol, int32_t* totals); // column scan of per-span counts
+int topo_knn_local(wtp_ctx* ctx, const float* d_xyz, int64_t n, int k, int include_self, int32_t* d_idx, float* d_dist);
+// radius rows of a device fp32 3-D cloud: counts -> d_off (n + 1, exclusive scan) -> rows into *d_idx (grown to fit); *nnz
+int topo_radius_local(wtp_ctx* ctx, const float* d_xyz, int64_t n, double r, int32_t* d_counts, int64_t* d_off, DevBuf& d_idx,
+                      int64_t* nnz);
 template <typename T>
 int launch_refix(wtp_ctx* ctx, const Pt<T>* in, int64_t n_old, int64_t n_fixed_old, int64_t n_fixed_new,
                  const Pt<T>* d_fixed_new, Pt<T>* out, int32_t* d_counter);
