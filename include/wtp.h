@@ -410,13 +410,25 @@ typedef struct wtp_transport {
 } wtp_transport;
 int wtp_block_set_transport(wtp_ctx* ctx, const wtp_transport* t); /* NULL: back to RCCL */
 
+/* The boundary wall of the volume-only repel (src/repel.jl:75-87) for the NEXT wtp_block_open on this context:
+ * d_wall_xyz n_wall x 3 fp32 on the context's GPU, the SAME array (same order) on every rank; n_wall = 0 clears it.
+ * Copied; the caller's array is free on return.  WTP_ERR_STATE while a block session is open.
+ * Every rank keeps the wall points inside its coverage box (its box grown by ghost_width + margin, the box of
+ * wtp_relax_set_coverage_box) as the leading part of its snapshot's fixed head: searched, never moved, never sent,
+ * migrated, counted in n_move or returned by wtp_block_get; selected again on every widening.  One rank whose box
+ * holds the whole wall runs the session of wtp_relax_init([wall ; owned], n_fixed = n_wall): same positions.  */
+int wtp_block_set_wall(wtp_ctx* ctx, const void* d_wall_xyz, int64_t n_wall);
+
 /* d_owned_xyz: n_owned x 3 fp32 on the context's GPU; d_gid: n_owned int64 global ids (device).  spacing / force / k /
  * alpha as wtp_relax_init.  Collective: every rank calls it.  */
 int wtp_block_open(wtp_ctx* ctx, const wtp_block_desc* desc, const void* d_owned_xyz, const int64_t* d_gid,
                    int64_t n_owned, const wtp_spacing_desc* spacing, const wtp_force_desc* force, int k,
                    double alpha_lo, double alpha_max);
-/* One iteration; stats = the GLOBAL view (max / sums over all ranks; argmin_i / argmin_j are global ids, on every rank);
- * info may be NULL.  */
+/* One iteration; stats = the GLOBAL view (max / sums over all ranks), on every rank.  The closest pair argmin_i /
+ * argmin_j / argmin_r is numbered as the snapshot of the assembled cloud [wall ; volume]: wall point k is k, the volume
+ * point with global id g is n_wall + g (without a wall: g).  Of equally close pairs the one with the smallest argmin_i.
+ * argmin_j is -1 if it is a ghost whose global id is 2^32 - 1 or more (ghost rows carry 32 bits of it).  info may be
+ * NULL.  */
 int wtp_block_step(wtp_ctx* ctx, wtp_step_stats* stats, wtp_block_info* info);
 /* n_iters iterations; conv_out[n_iters] = global max |F| s per iteration (may be NULL).  */
 int wtp_block_run(wtp_ctx* ctx, int n_iters, double* conv_out, wtp_step_stats* last, wtp_block_info* info);

@@ -127,6 +127,7 @@ SIGNATURES = {
     "wtp_comm_exchange_rows": (_i, [_vp, _i, _i, _vp, _i64, _vp, _i64, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
     "wtp_comm_allreduce_stats": (_i, [_vp, C.POINTER(StepStats)]),
     "wtp_block_set_transport": (_i, [_vp, C.POINTER(Transport)]),
+    "wtp_block_set_wall": (_i, [_vp, _vp, _i64]),
     "wtp_block_open": (_i, [_vp, C.POINTER(BlockDesc), _vp, _vp, _i64, C.POINTER(SpacingDesc), C.POINTER(ForceDesc), _i, _d, _d]),
     "wtp_block_step": (_i, [_vp, C.POINTER(StepStats), C.POINTER(BlockInfo)]),
     "wtp_block_run": (_i, [_vp, _i, _vp, C.POINTER(StepStats), C.POINTER(BlockInfo)]),

@@ -124,10 +124,12 @@ def shard_stream(gen, boxes, rank: int, n_total: int, chunk: int = 8_000_000):
 class BlockRelax:
     """This rank's share of a block-decomposed repel, driven through wtp_block_* (the iteration is C).
     owned_xyz / gid: torch CUDA tensors (n, 3) float32 / (n,) int64 on the context's device, or numpy arrays
-    (copied to the device through torch)."""
+    (copied to the device through torch).  wall_xyz: the boundary points of the volume-only repel (n_wall, 3), the same
+    array on every rank (wtp_block_set_wall): fixed, searched, never moved; the closest pair in the statistics is then
+    numbered as the snapshot [wall ; volume] (wall point k is k, volume point g is n_wall + g)."""
 
     def __init__(self, ctx, rank: int, nranks: int, boxes, owned_xyz, gid, ghost_width: float, spacing, force, k: int,
-                 alpha_lo: float, alpha_max: float, margin: float = -1.0, transport=None):
+                 alpha_lo: float, alpha_max: float, margin: float = -1.0, transport=None, wall_xyz=None):
         import torch
 
         self.ctx, self._lib = ctx, ctx._lib
@@ -157,11 +159,24 @@ class BlockRelax:
         fd = L.ForceDesc(int(force["kind"]), float(force["beta"]), float(force.get("u0", 1.0)), float(force.get("gamma", 3.0)))
         desc = L.BlockDesc(self.rank, self.nranks, self._boxes.ctypes.data_as(C.POINTER(C.c_double)), float(ghost_width),
                            float(margin))
+        wall = None
+        if wall_xyz is not None:
+            wall = _on_device(wall_xyz, dev).to(torch.float32).contiguous()
+            if wall.dim() != 2 or wall.shape[1] != 3:
+                raise L.WtpArgumentError(f"wall_xyz must have shape (n_wall, 3), got {tuple(wall.shape)}")
+        self.n_wall = 0 if wall is None else int(wall.shape[0])
         torch.cuda.synchronize(dev)
+        if wall is not None:  # (close() clears it again)
+            L.check(ctx._h, self._lib.wtp_block_set_wall(ctx._h, _ptr(wall), self.n_wall))
         rc = self._lib.wtp_block_open(ctx._h, C.byref(desc), C.c_void_p(owned_xyz.data_ptr()),
                                       C.c_void_p(gid.data_ptr()) if gid is not None else None, int(owned_xyz.shape[0]),
                                       C.byref(sd), C.byref(fd), int(k), float(alpha_lo), float(alpha_max))
-        L.check(ctx._h, rc)
+        try:
+            L.check(ctx._h, rc)
+        except BaseException:
+            if wall is not None:  # (a failed open leaves no wall behind for the next session on this context)
+                self._lib.wtp_block_set_wall(ctx._h, None, 0)
+            raise
         self._open = True
         self.history = []
 
@@ -213,6 +228,8 @@ class BlockRelax:
     def close(self):
         if self._open and self.ctx._h:
             self._lib.wtp_block_close(self.ctx._h)
+            if self.n_wall:
+                self._lib.wtp_block_set_wall(self.ctx._h, None, 0)
             if self._transport is not None:
                 self._lib.wtp_block_set_transport(self.ctx._h, None)
         self._open = False

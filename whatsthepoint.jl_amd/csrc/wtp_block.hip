@@ -11,7 +11,9 @@
 //      are already known on both sides: they rode with the previous iteration's all-gather.
 //   2. migration: arrivals are appended to the owned set, departures leave it (ordered compaction; 64-bit global ids
 //      follow); only when somebody actually crossed a box face by more than `margin`.
-//   3. ghosts -> fixed head of the snapshot (wtp_relax_set_fixed_dev: appended, no pass over the cloud).
+//   3. [selected wall points ; ghosts] -> fixed head of the snapshot (wtp_relax_set_fixed_dev: appended, no pass over
+//      the cloud).  The wall (wtp_block_set_wall) is replicated: every rank holds all of it and keeps the points inside
+//      its coverage box; nobody sends one.
 //   4. hash + sweep of [ghosts ; owned] (relax_step_enqueue).
 //   5. from the new positions: classify every owned point against the peers' boxes (which ranks need it as a ghost,
 //      does it change owner), count per peer, fill the send rows of the NEXT exchange — three launches.
@@ -21,6 +23,10 @@
 //
 // Order of the rows a peer receives = slot order of the sender's sorted state = a pure function of the sender's
 // points, so the ghost ids on the receiving side (and with them every sum) do not depend on scheduling.
+//
+// Global numbering of the closest pair: the snapshot index of the assembled cloud [wall ; volume] — wall point k is k,
+// the volume point with global id g is n_wall + g.  A ghost row carries the low 32 bits of its gid in the w word
+// (the fixed-head install overwrites w without reading it), so the pack kernel can translate either end of the pair.
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -36,6 +42,7 @@ constexpr int kBlkSpan = 64 * kBlkPasses;
 constexpr int kBlkWaves = 4;                   // waves per workgroup
 constexpr uint32_t kBlkMigrate = 0x80000000u;  // flag bit 31: the point changes owner; bits 26..30: peer index of the new owner
 constexpr int kBlkStatWords = 10;              // wtp_step_stats as 8-byte words
+constexpr uint32_t kBlkNoGid = 0xFFFFFFFFu;    // w word of a ghost row whose gid does not fit in 32 bits
 
 struct BlkGeom {
     int np;
@@ -68,6 +75,14 @@ struct BlockState {
     bool host_transport = false;
     wtp_transport tr{};
     std::vector<unsigned char> hbuf_a, hbuf_b;
+    // the boundary wall (wtp_block_set_wall): all of it on the host, the part inside the coverage box as 16-byte rows
+    // {x, y, z, bits(wall index)} in ascending wall index on both sides; the rows lead the fixed head
+    std::vector<float> wall;             // n_wall x 3
+    std::vector<float> wall_sel;         // n_sel x 4
+    int64_t n_wall = 0, n_sel = 0;
+    DevBuf wall_rows, snap;              // selected rows (device); [selection ; owned] xyz while a session opens
+    bool wall_dirty = false;             // the selection changed since the session's head was installed
+    bool pool_wall_ok = false;           // the pool's prefix holds the current selection (false after any regrowth)
     // last info
     wtp_block_info info{};
     // stop rules (wtp_block_run_until)
@@ -173,14 +188,39 @@ __global__ __launch_bounds__(256) void blk_scan_kernel(int32_t* __restrict__ spa
     }
 }
 
-// The all-gather payload: [0, 10) the step's statistics as they are, then per DESTINATION rank the ghost rows and the
-// migrants this rank will send, then {points lost, owned points}.  One thread: a few dozen words.
-__global__ void blk_pack_kernel(const wtp_step_stats* __restrict__ st, const int32_t* __restrict__ totals, int np,
+// Where a local snapshot index of the pair lies in the global numbering (see the top of the file); -1 if unknown.
+struct BlkIds {
+    const int64_t* gid;      // owned points, by movable index
+    const float4* wall_rows; // [0, n_sel) of the head
+    const float4* ghosts;    // [n_sel, n_fixed) of the head
+    int64_t n_fixed, n_sel, n_wall;
+};
+
+__device__ inline int64_t blk_global_id(const BlkIds& t, int64_t l) {
+    if (l < 0) return -1;
+    if (l >= t.n_fixed) return t.n_wall + t.gid[l - t.n_fixed];
+    if (l < t.n_sel) return (int64_t)__builtin_bit_cast(uint32_t, t.wall_rows[l].w);
+    const uint32_t g = __builtin_bit_cast(uint32_t, t.ghosts[l - t.n_sel].w);
+    return g == kBlkNoGid ? -1 : t.n_wall + (int64_t)g;
+}
+
+// The all-gather payload: [0, 10) the step's statistics, the closest pair in global numbering, then per DESTINATION
+// rank the ghost rows and the migrants this rank will send, then {points lost, owned points}.  One thread: a few
+// dozen words.
+__global__ void blk_pack_kernel(const wtp_step_stats* __restrict__ st, BlkIds ids, const int32_t* __restrict__ totals, int np,
                                 const int* __restrict__ peer_rank, int nranks, const int32_t* __restrict__ lost,
                                 int64_t n_owned, int64_t* __restrict__ out) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const int64_t* sw = (const int64_t*)st;
-    for (int j = 0; j < kBlkStatWords; ++j) out[j] = st ? sw[j] : 0;
+    wtp_step_stats s{};
+    if (st) {
+        s = *st;
+        if (s.argmin_i >= 0) {
+            s.argmin_i = blk_global_id(ids, s.argmin_i);
+            s.argmin_j = blk_global_id(ids, s.argmin_j);
+        }
+    }
+    const int64_t* sw = (const int64_t*)&s;
+    for (int j = 0; j < kBlkStatWords; ++j) out[j] = sw[j];
     for (int r = 0; r < 2 * nranks; ++r) out[kBlkStatWords + r] = 0;
     for (int q = 0; q < np; ++q) {
         out[kBlkStatWords + peer_rank[q]] = totals[q];
@@ -190,9 +230,9 @@ __global__ void blk_pack_kernel(const wtp_step_stats* __restrict__ st, const int
     out[kBlkStatWords + 2 * nranks + 1] = n_owned;
 }
 
-// Pass 3: the send rows.  Ghost rows {x, y, z, 0} of peer q start at row sum_{j<q} totals[j]; a migrant is two rows
-// {x, y, z, bits(gid low)}, {bits(gid high), 0, 0, 0}, peer q's start at 2 * sum_{j<q} totals[np + j].  Order inside a
-// peer's rows: slot order.
+// Pass 3: the send rows.  Ghost rows {x, y, z, bits(gid low)} (kBlkNoGid for gid >= 2^32 - 1) of peer q start at row
+// sum_{j<q} totals[j]; a migrant is two rows {x, y, z, bits(gid low)}, {bits(gid high), 0, 0, 0}, peer q's start at
+// 2 * sum_{j<q} totals[np + j].  Order inside a peer's rows: slot order.
 __global__ __launch_bounds__(64 * kBlkWaves) void blk_fill_kernel(const float4* __restrict__ P, int64_t n, int32_t n_fixed, int np,
                                                                  const uint32_t* __restrict__ flags,
                                                                  const int32_t* __restrict__ span_off,
@@ -225,7 +265,12 @@ __global__ __launch_bounds__(64 * kBlkWaves) void blk_fill_kernel(const float4* 
         const uint32_t flag = ff[pass];
         if (__ballot(flag != 0) == 0ull) continue;
         float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (flag) p = P[i];
+        int64_t gd = 0;
+        if (flag) {
+            p = P[i];
+            gd = gid[w_to_id(p.w) - n_fixed];
+        }
+        const float gw = __builtin_bit_cast(float, (uint64_t)gd < kBlkNoGid ? (uint32_t)gd : kBlkNoGid);
         for (int q = 0; q < np; ++q) {
             const bool g = (flag >> q) & 1u;
             const unsigned long long m = __ballot(g);
@@ -233,7 +278,7 @@ __global__ __launch_bounds__(64 * kBlkWaves) void blk_fill_kernel(const float4* 
                 const int off = __builtin_amdgcn_readlane(run, q);
                 if (g) {
                     const int64_t o = (int64_t)off + __popcll(m & below);
-                    if (o < send_cap) send[o] = make_float4(p.x, p.y, p.z, 0.f);
+                    if (o < send_cap) send[o] = make_float4(p.x, p.y, p.z, gw);
                 }
                 if (lane == q) run += __popcll(m);
             }
@@ -243,7 +288,6 @@ __global__ __launch_bounds__(64 * kBlkWaves) void blk_fill_kernel(const float4* 
                 const int off = __builtin_amdgcn_readlane(run, np + q);
                 if (mg) {
                     const int64_t o = (int64_t)off + __popcll(mm & below);
-                    const int64_t gd = gid[w_to_id(p.w) - n_fixed];
                     if (o < mig_cap) {
                         send_mig[2 * o] = make_float4(p.x, p.y, p.z, __builtin_bit_cast(float, (uint32_t)(gd & 0xFFFFFFFFll)));
                         send_mig[2 * o + 1] = make_float4(__builtin_bit_cast(float, (uint32_t)((uint64_t)gd >> 32)), 0.f, 0.f, 0.f);
@@ -301,8 +345,9 @@ __global__ void blk_arrivals_kernel(const float4* __restrict__ rows, int64_t n_a
 // this rank's own emigrants stay around as ghosts for the iteration (their new owner cut its layers before they arrived)
 __global__ void blk_emigrant_ghosts_kernel(const float4* __restrict__ mig_rows, int64_t n_mig, float4* __restrict__ pool_tail) {
     for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n_mig; k += (int64_t)gridDim.x * blockDim.x) {
-        const float4 a = mig_rows[2 * k];
-        pool_tail[k] = make_float4(a.x, a.y, a.z, 0.f);
+        const float4 a = mig_rows[2 * k], b = mig_rows[2 * k + 1];
+        const uint32_t lo = __builtin_bit_cast(uint32_t, a.w), hi = __builtin_bit_cast(uint32_t, b.x);
+        pool_tail[k] = make_float4(a.x, a.y, a.z, hi == 0 && lo != kBlkNoGid ? a.w : __builtin_bit_cast(float, kBlkNoGid));
     }
 }
 
@@ -332,6 +377,51 @@ static bool boxes_near(const double* a, const double* c, double reach) {
     for (int ax = 0; ax < 3; ++ax)
         if (a[ax] - reach >= c[3 + ax] || c[ax] - reach >= a[3 + ax]) return false;
     return true;
+}
+
+// what the snapshot is complete for: the box plus the layers the peers send, rounded to fp32
+static void blk_coverage(const BlockState* b, double lo[3], double hi[3]) {
+    const double w_eff = b->w + b->margin;
+    const double* mine = &b->boxes[(size_t)b->rank * 6];
+    for (int ax = 0; ax < 3; ++ax) {
+        lo[ax] = (double)(float)(mine[ax] - w_eff);
+        hi[ax] = (double)(float)(mine[3 + ax] + w_eff);
+    }
+}
+
+// The wall points inside the coverage box (inclusive, fp32 compares on the coverage thresholds), ascending wall index.
+// Host work on the replicated copy, at open and on a widening only.  A changed selection goes to the device and marks
+// the session's head and the pool's prefix stale.
+static int blk_select_wall(wtp_ctx* ctx, BlockState* b, const double lo[3], const double hi[3]) {
+    std::vector<float> sel;
+    float flo[3], fhi[3];
+    for (int ax = 0; ax < 3; ++ax) {
+        flo[ax] = (float)lo[ax];
+        fhi[ax] = (float)hi[ax];
+    }
+    for (int64_t k = 0; k < b->n_wall; ++k) {
+        const float* q = &b->wall[(size_t)k * 3];
+        bool in = true;
+        for (int ax = 0; ax < 3; ++ax) in = in && q[ax] >= flo[ax] && q[ax] <= fhi[ax];
+        if (!in) continue;
+        uint32_t kb = (uint32_t)k;
+        float kw;
+        memcpy(&kw, &kb, 4);
+        sel.insert(sel.end(), {q[0], q[1], q[2], kw});
+    }
+    if (sel.size() == b->wall_sel.size() && (sel.empty() || !memcmp(sel.data(), b->wall_sel.data(), 4 * sel.size())))
+        return WTP_OK;
+    // (the previous rows may still be the source of a copy in flight: the stream drains before they are replaced)
+    int rc;
+    if ((rc = blk_sync(ctx, b))) return rc;
+    b->wall_sel.swap(sel);
+    b->n_sel = (int64_t)(b->wall_sel.size() / 4);
+    b->wall_dirty = true;
+    b->pool_wall_ok = false;
+    if ((rc = ensure(ctx, b->wall_rows, 16 * (size_t)b->n_sel))) return rc;
+    if (b->n_sel)
+        WTP_HIP(ctx, hipMemcpyAsync(b->wall_rows.p, b->wall_sel.data(), 16 * (size_t)b->n_sel, hipMemcpyHostToDevice, ctx->stream));
+    return WTP_OK;
 }
 
 // peers and the kernel's geometry block for the current ghost width
@@ -372,12 +462,11 @@ static int blk_geometry(wtp_ctx* ctx, BlockState* b) {
     b->mig_cnt.assign(np, 0);
     b->recv_cnt.assign(np, 0);
     b->rmig_cnt.assign(np, 0);
-    // what the snapshot is complete for: the box plus the layers the peers send
+    // the coverage box certifies the wall and the ghosts together
     double lo[3], hi[3];
-    for (int ax = 0; ax < 3; ++ax) {
-        lo[ax] = (double)(float)(mine[ax] - w_eff);
-        hi[ax] = (double)(float)(mine[3 + ax] + w_eff);
-    }
+    blk_coverage(b, lo, hi);
+    int rc;
+    if ((rc = blk_select_wall(ctx, b, lo, hi))) return rc;
     return wtp_relax_set_coverage_box(ctx, lo, hi);
 }
 
@@ -433,7 +522,9 @@ static int blk_classify(wtp_ctx* ctx, BlockState* b, const wtp_step_stats* d_sta
     } else {
         WTP_HIP(ctx, hipMemsetAsync(totals, 0, sizeof(int32_t) * (size_t)ncol, ctx->stream));
     }
-    hipLaunchKernelGGL(blk_pack_kernel, dim3(1), dim3(64), 0, ctx->stream, d_stats, (const int32_t*)totals, np,
+    BlkIds ids{(const int64_t*)b->gid[b->gid_cur].p, (const float4*)b->wall_rows.p, (const float4*)b->pool.p + b->n_sel,
+               r.n_fixed, b->n_sel, b->n_wall};
+    hipLaunchKernelGGL(blk_pack_kernel, dim3(1), dim3(64), 0, ctx->stream, d_stats, ids, (const int32_t*)totals, np,
                        (const int*)d_peer_rank, b->nranks, (const int32_t*)b->lost.p, b->n_owned, (int64_t*)b->gsend.p);
     WTP_HIP(ctx, hipGetLastError());
     return WTP_OK;
@@ -505,9 +596,11 @@ static int blk_gather(wtp_ctx* ctx, BlockState* b, wtp_step_stats* g, bool* over
             out.n_fallback += s.n_fallback;
             out.n_uncovered += s.n_uncovered;
             out.n_escaped += s.n_escaped;
-            if (s.n_move > 0 && s.argmin_r < out.argmin_r) {
+            // the closest pair in global numbering: smallest distance, on a tie the smallest argmin_i (cs2_kernel's rule)
+            if (s.n_move > 0 && s.argmin_i >= 0 &&
+                (out.argmin_i < 0 || s.argmin_r < out.argmin_r || (s.argmin_r == out.argmin_r && s.argmin_i < out.argmin_i))) {
                 out.argmin_r = s.argmin_r;
-                out.argmin_i = s.argmin_i; // (local indices of the rank that holds the pair; see wtp_block_step)
+                out.argmin_i = s.argmin_i;
                 out.argmin_j = s.argmin_j;
             }
         }
@@ -614,6 +707,25 @@ WTP_API int wtp_block_set_transport(wtp_ctx* ctx, const wtp_transport* t) {
     return WTP_OK;
 }
 
+WTP_API int wtp_block_set_wall(wtp_ctx* ctx, const void* d_wall_xyz, int64_t n_wall) {
+    if (!ctx) return WTP_ERR_ARG;
+    if (n_wall < 0 || (n_wall > 0 && !d_wall_xyz)) return fail(ctx, WTP_ERR_ARG, "wtp_block_set_wall: n_wall >= 0, and an array when n_wall > 0");
+    if (n_wall > 2000000000LL) return fail(ctx, WTP_ERR_ARG, "wtp_block_set_wall: n_wall exceeds the int32 index space");
+    if (!ctx->block) ctx->block = new BlockState();
+    BlockState* b = bs_of(ctx);
+    if (b->active) return fail(ctx, WTP_ERR_STATE, "wtp_block_set_wall while a block session is open");
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<float> h((size_t)n_wall * 3);
+    if (n_wall) WTP_HIP(ctx, hipMemcpyAsync(h.data(), d_wall_xyz, 12 * (size_t)n_wall, hipMemcpyDeviceToHost, ctx->stream));
+    WTP_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the caller's array is free again, no copy reads the old selection
+    b->wall.swap(h);
+    b->n_wall = n_wall;
+    b->wall_sel.clear();
+    b->n_sel = 0;
+    b->pool_wall_ok = false;
+    return WTP_OK;
+}
+
 WTP_API int wtp_block_close(wtp_ctx* ctx) {
     if (!ctx) return WTP_ERR_ARG;
     BlockState* b = bs_of(ctx);
@@ -643,14 +755,30 @@ WTP_API int wtp_block_open(wtp_ctx* ctx, const wtp_block_desc* desc, const void*
             if (!(desc->boxes[(size_t)r * 6 + ax] < desc->boxes[(size_t)r * 6 + 3 + ax]))
                 return fail(ctx, WTP_ERR_ARG, "wtp_block_open: every box needs lo < hi on every axis");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    if ((rc = wtp_relax_init_dev(ctx, d_owned_xyz, n_owned, 0, 3, WTP_F32, spacing, force, k, alpha_lo, alpha_max))) return rc;
-    ctx->relax.shard_grid_reuse = true;
     b->rank = desc->rank;
     b->nranks = desc->nranks;
     b->boxes.assign(desc->boxes, desc->boxes + (size_t)desc->nranks * 6);
     b->w = desc->ghost_width;
     b->margin = desc->margin < 0 ? 0.25 * desc->ghost_width : desc->margin;
+    int rc;
+    // the session starts on [selected wall ; owned] with the wall as its fixed head: one rank is the plain session
+    double lo[3], hi[3];
+    blk_coverage(b, lo, hi);
+    if ((rc = blk_select_wall(ctx, b, lo, hi))) return rc;
+    const void* snap = d_owned_xyz;
+    if (b->n_sel) {
+        if (b->n_sel + n_owned > 2000000000LL) return fail(ctx, WTP_ERR_ARG, "wtp_block_open: wall + owned points exceed the int32 index space");
+        if ((rc = ensure(ctx, b->snap, 12 * (size_t)(b->n_sel + n_owned)))) return rc;
+        WTP_HIP(ctx, hipMemcpy2DAsync(b->snap.p, 12, b->wall_rows.p, 16, 12, (size_t)b->n_sel, hipMemcpyDeviceToDevice, ctx->stream));
+        WTP_HIP(ctx, hipMemcpyAsync((char*)b->snap.p + 12 * (size_t)b->n_sel, d_owned_xyz, 12 * (size_t)n_owned,
+                                    hipMemcpyDeviceToDevice, ctx->stream));
+        snap = b->snap.p;
+    }
+    if ((rc = wtp_relax_init_dev(ctx, snap, b->n_sel + n_owned, b->n_sel, 3, WTP_F32, spacing, force, k, alpha_lo, alpha_max)))
+        return rc;
+    b->wall_dirty = false;
+    b->pool_wall_ok = false;
+    ctx->relax.shard_grid_reuse = true;
     b->widened = 0;
     b->n_owned = n_owned;
     b->n_ghost = 0;
@@ -665,6 +793,7 @@ WTP_API int wtp_block_open(wtp_ctx* ctx, const wtp_block_desc* desc, const void*
         hipLaunchKernelGGL(blk_iota_gid_kernel, dim3(1024), dim3(256), 0, ctx->stream, (int64_t*)b->gid[0].p, n_owned);
     }
     WTP_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the caller's arrays are free again
+    b->snap = DevBuf();                               // (the session holds its own copy of [wall ; owned])
     if ((rc = blk_geometry(ctx, b))) {
         wtp_relax_end(ctx);
         return rc;
@@ -694,7 +823,17 @@ static int blk_exchange_and_apply(wtp_ctx* ctx, BlockState* b) {
     }
     int rc;
     const int64_t n_pool = n_recv + n_mig; // peers' rows + my own emigrants
-    if ((rc = ensure(ctx, b->pool, 16 * (size_t)(n_pool + 16)))) return rc;
+    // pool = [selected wall (a resident prefix) ; peers' rows ; my emigrants]: the whole fixed head in one array
+    const int64_t n_sel = b->n_sel;
+    // (ensure frees and allocates anew when it grows the buffer, possibly at the same address: the capacity tells)
+    const size_t pool_cap0 = b->pool.cap;
+    if ((rc = ensure(ctx, b->pool, 16 * (size_t)(n_sel + n_pool + 16)))) return rc;
+    if (b->pool.cap != pool_cap0) b->pool_wall_ok = false;
+    if (n_sel && !b->pool_wall_ok) {
+        WTP_HIP(ctx, hipMemcpyAsync(b->pool.p, b->wall_rows.p, 16 * (size_t)n_sel, hipMemcpyDeviceToDevice, ctx->stream));
+        b->pool_wall_ok = true;
+    }
+    char* const ghost_base = (char*)b->pool.p + 16 * (size_t)n_sel;
     if ((rc = ensure(ctx, b->recv_mig, 32 * (size_t)(n_rmig + 16)))) return rc;
     // nobody crosses in this iteration (the usual case): the owned set stays, so its part of the rebuild can start early
     const bool early = ctx->block_overlap && np > 0 && n_mig == 0 && n_rmig == 0;
@@ -708,7 +847,7 @@ static int blk_exchange_and_apply(wtp_ctx* ctx, BlockState* b) {
         peers.push_back(b->peers[q]);
         sp.push_back((const char*)b->send.p + 16 * (size_t)so);
         sn.push_back(b->send_cnt[q]);
-        rp.push_back((char*)b->pool.p + 16 * (size_t)ro);
+        rp.push_back(ghost_base + 16 * (size_t)ro);
         rn.push_back(b->recv_cnt[q]);
         peers.push_back(b->peers[q]);
         sp.push_back((const char*)b->send_mig.p + 32 * (size_t)mo);
@@ -734,7 +873,7 @@ static int blk_exchange_and_apply(wtp_ctx* ctx, BlockState* b) {
                 // the host waits for the rows only; the stream goes on ranking the owned points under the callback
                 if ((rc = blk_streams(ctx))) return rc;
                 WTP_HIP(ctx, hipEventRecord(ctx->ev_comm_a, ctx->stream));
-                if ((rc = relax_prerank(ctx, n_pool))) return rc;
+                if ((rc = relax_prerank(ctx, n_sel + n_pool))) return rc;
                 ctx->ev_last_end = -1;
                 WTP_HIP(ctx, hipEventSynchronize(ctx->ev_comm_a));
                 ctx->n_syncs += 1;
@@ -747,13 +886,13 @@ static int blk_exchange_and_apply(wtp_ctx* ctx, BlockState* b) {
                 const bool mig = j & 1;
                 hs[j] = mig ? ha + 16 * (size_t)n_send + ((const char*)sp[j] - (const char*)b->send_mig.p)
                             : ha + ((const char*)sp[j] - (const char*)b->send.p);
-                hr[j] = mig ? hb + 16 * (size_t)n_recv + ((char*)rp[j] - (char*)b->recv_mig.p) : hb + ((char*)rp[j] - (char*)b->pool.p);
+                hr[j] = mig ? hb + 16 * (size_t)n_recv + ((char*)rp[j] - (char*)b->recv_mig.p) : hb + ((char*)rp[j] - ghost_base);
                 sb[j] = 16 * sn[j];
                 rb[j] = 16 * rn[j];
             }
             if (b->tr.exchange(b->tr.user, (int)peers.size(), peers.data(), hs.data(), sb.data(), hr.data(), rb.data()) != 0)
                 return fail(ctx, WTP_ERR_STATE, "wtp_block: the caller's exchange callback failed");
-            if (n_recv) WTP_HIP(ctx, hipMemcpyAsync(b->pool.p, hb, 16 * (size_t)n_recv, hipMemcpyHostToDevice, ctx->stream));
+            if (n_recv) WTP_HIP(ctx, hipMemcpyAsync(ghost_base, hb, 16 * (size_t)n_recv, hipMemcpyHostToDevice, ctx->stream));
             if (n_rmig) WTP_HIP(ctx, hipMemcpyAsync(b->recv_mig.p, hb + 16 * (size_t)n_recv, 32 * (size_t)n_rmig, hipMemcpyHostToDevice, ctx->stream));
             if ((rc = blk_sync(ctx, b))) return rc; // (the host buffers are reused)
         } else if (early) {
@@ -767,7 +906,7 @@ static int blk_exchange_and_apply(wtp_ctx* ctx, BlockState* b) {
                                              rn.data())))
                 return rc;
             WTP_HIP(ctx, hipEventRecord(ctx->ev_comm_b, ctx->comm_stream));
-            rc = relax_prerank(ctx, n_pool);
+            rc = relax_prerank(ctx, n_sel + n_pool);
             WTP_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_comm_b, 0)); // (also when the ranking failed: the streams join again)
             if (rc) return rc;
         } else {
@@ -777,7 +916,7 @@ static int blk_exchange_and_apply(wtp_ctx* ctx, BlockState* b) {
     // my emigrants: ghosts for this iteration
     if (n_mig)
         hipLaunchKernelGGL(blk_emigrant_ghosts_kernel, dim3(64), dim3(256), 0, ctx->stream, (const float4*)b->send_mig.p, n_mig,
-                           (float4*)b->pool.p + n_recv);
+                           (float4*)ghost_base + n_recv);
     // the owned set changes only when somebody crossed
     if (n_mig || n_rmig) {
         const int64_t n_stay = b->n_owned - n_mig, n_new = n_stay + n_rmig;
@@ -808,8 +947,11 @@ static int blk_exchange_and_apply(wtp_ctx* ctx, BlockState* b) {
     b->info.n_recv_rows = n_recv;
     b->n_ghost = n_pool;
     WTP_HIP(ctx, hipGetLastError());
-    if (n_pool == 0 && r.n_fixed == 0) return WTP_OK; // no ghosts before, none now: the session is untouched (one rank: it IS the plain session)
-    return relax_set_fixed_dev_impl(ctx, n_pool ? b->pool.p : nullptr, n_pool, true); // (the pool is ours: no wait for the copy)
+    // no ghosts before, none now, the same wall: the session is untouched (one rank: it IS the plain session)
+    if (n_pool == 0 && r.n_fixed == n_sel && !b->wall_dirty) return WTP_OK;
+    b->wall_dirty = false;
+    const int64_t n_head = n_sel + n_pool;
+    return relax_set_fixed_dev_impl(ctx, n_head ? b->pool.p : nullptr, n_head, true); // (the pool is ours: no wait for the copy)
 }
 
 WTP_API int wtp_block_step(wtp_ctx* ctx, wtp_step_stats* stats, wtp_block_info* info) {
@@ -839,12 +981,6 @@ WTP_API int wtp_block_step(wtp_ctx* ctx, wtp_step_stats* stats, wtp_block_info* 
         b->info.redone = 1;
         b->plan_ready = false;
         if ((rc = blk_geometry(ctx, b))) return rc;
-    }
-    // the closest pair's indices: global ids (the rank that holds it looks them up; the others cannot, so the pair is
-    // reported as ids only where that is free: on the holder.  -1 elsewhere.)
-    if (g.argmin_i >= 0) {
-        g.argmin_i = -1;
-        g.argmin_j = -1;
     }
     b->info.host_syncs = (int32_t)(ctx->n_syncs - syncs0);
     b->info.overlapped = (int32_t)(ctx->preranked_builds - pre0);
