@@ -490,7 +490,7 @@ int FN(wtpo_relax_sweep)(const REAL* snap, int64_t n, int64_t n_fixed, int dim,
             REAL s = spacings[id + n_fixed];       /* :260 */
             int32_t self = (int32_t)(id + n_fixed);/* :266 */
             int32_t nid = -1;
-            REAL ndist = REAL_MAX;
+            REAL ndist = (REAL)INFINITY; /* typemax(T) :268 is Inf (not the largest finite value): a k = 1 list has no neighbour */
             REAL F[3] = {0, 0, 0};
             for (int j = 0; j < m; ++j) { /* :270-280 */
                 if (bi[j] == self) continue;
