@@ -133,7 +133,10 @@ int wtp_knn_dev(wtp_ctx* ctx, const void* d_xyz, int64_t n, int dim, int dtype, 
  * d2(i,j) <= r*r (inclusive).  Two-phase CSR so the caller allocates exactly:
  * count fills counts_out[n]; the caller builds offsets[n+1] (exclusive scan, int64)
  * and calls fill, which writes rows sorted by ascending (d2, index) into idx_out.
- * fill refers to the cloud passed to the preceding count on the same context. */
+ * fill refers to the cloud passed to the preceding count on the same context.  Every call that overwrites what the
+ * count phase left on the context (wtp_knn* and what runs through it, the sharded topology, wtp_relax_init*) ends the
+ * pair: a fill after it returns WTP_ERR_STATE; calls that keep buffers of their own (wtp_spacing_eval, wtp_isinside_*,
+ * wtp_mesh_*) may come between the two. */
 int wtp_radius_count(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype,
                      double r, int32_t* counts_out);
 int wtp_radius_fill(wtp_ctx* ctx, const int64_t* offsets, int32_t* idx_out);
@@ -142,6 +145,15 @@ int wtp_radius_fill(wtp_ctx* ctx, const int64_t* offsets, int32_t* idx_out);
  * that follows may pass offsets = NULL.  Saves the counts' trip to the host and the offsets' trip back.  */
 int wtp_radius_offsets(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype, double r,
                        int64_t* offsets_out);
+/* Diagnostic, read-only: how the count phase disposed of each query of the cloud it was given.  Valid where
+ * wtp_radius_fill is (after a count or offsets call on this context, WTP_ERR_STATE otherwise), before or after the fill.
+ * marks_out[cap], cap >= n (WTP_ERR_ARG otherwise; NULL: only info_out is filled), by original id: 0 = left to the fill phase (the wave-per-query kernel, the serial kernel for rows beyond
+ * 512), 1 = row of at most 32 ids parked by the lane-per-query brick kernel, 2 = row parked in the arena (by the
+ * brick-staged dense kernel if info_out[0], else by the wave-per-query kernel).
+ * info_out[13]: [0] the dense kernel ran, [1] the grid's rad_wave_only flag, [2] the dense kernel's LDS point area for
+ * this dtype, [3..5] cells per axis, [6] cell edge, [7..9] grid origin (edge and origin exactly as the kernels use them),
+ * [10] ids of the arena the dense kernel took (in pieces of 2048), [11] ids the arena holds (48 n), [12] n, the points of the cloud the count was given. */
+int wtp_radius_marks(wtp_ctx* ctx, uint8_t* marks_out, int64_t cap, double* info_out);
 
 /* ---- repel: _relax! ------------------------------------------------------------------ */
 

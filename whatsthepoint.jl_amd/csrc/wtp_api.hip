@@ -826,7 +826,7 @@ template <typename T> static int radius_count_t(wtp_ctx* ctx, int64_t n, int dim
     // shared out evenly among the waves; a row that does not fit any more is simply searched again by the fill phase.
     // (For the hand-backs of the fp32 brick kernel it buys nothing: measured 2.07 -> 2.14 ms per graded 1 M cloud —
     // ranking in the count phase costs what it saves in the fill phase; the kernel decides by the grid's flag.)
-    const int64_t arena_cap = 48 * n;
+    const int64_t arena_cap = (int64_t)kRadArenaPerPoint * n;
     if ((rc = ensure(ctx, ctx->rad_arena, sizeof(int32_t) * (size_t)arena_cap))) return rc;
     if ((rc = ensure(ctx, ctx->rad_arena_off, sizeof(int64_t) * (size_t)(n + 2)))) return rc;
     a.rad_arena = (int32_t*)ctx->rad_arena.p;
@@ -863,7 +863,7 @@ template <typename T> static int radius_fill_t(wtp_ctx* ctx, const int64_t* d_of
     a.rad_done = (uint8_t*)ctx->rad_done.p;
     a.rad_arena = (int32_t*)ctx->rad_arena.p;
     a.rad_arena_off = (int64_t*)ctx->rad_arena_off.p;
-    a.rad_arena_cap = 48 * ctx->rad_n;
+    a.rad_arena_cap = (int64_t)kRadArenaPerPoint * ctx->rad_n;
     a.rad_dense = ctx->rad_dense_used ? 1 : 0; // (the hand-back list of the count phase is what is left to search)
     int sp = span_begin(ctx, 1);
     int rc = launch_radius_fill<T>(ctx, a, (T)ctx->rad_r, d_off, d_idx);
@@ -954,6 +954,39 @@ WTP_API int wtp_radius_fill(wtp_ctx* ctx, const int64_t* offsets, int32_t* idx_o
         WTP_HIP(ctx, hipMemcpyAsync(idx_out, ctx->idx_out.p, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost,
                                     ctx->stream));
     return sync(ctx);
+}
+
+// Diagnostic of the pair above: the count phase's mark per query, which kernels stood in front, and the grid they ran on.
+// Copies only; no kernel is launched.
+WTP_API int wtp_radius_marks(wtp_ctx* ctx, uint8_t* marks_out, int64_t cap, double* info_out) {
+    if (!ctx) return WTP_ERR_ARG;
+    if (!ctx->rad_valid) return fail(ctx, WTP_ERR_STATE, "wtp_radius_marks needs a preceding wtp_radius_count");
+    if (!info_out) return fail(ctx, WTP_ERR_ARG, "info_out is NULL");
+    const int64_t n = ctx->rad_n;
+    if (marks_out && cap < n) return fail(ctx, WTP_ERR_ARG, "marks_out holds fewer than n marks (info_out[12] of a call with marks_out = NULL)");
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    if (marks_out && n > 0) WTP_HIP(ctx, hipMemcpyAsync(marks_out, ctx->rad_done.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    return by_dtype(ctx->rad_dtype, [&](auto t) {
+        using T = decltype(t);
+        Grid<T> g;
+        unsigned long long taken = 0;
+        WTP_HIP(ctx, hipMemcpyAsync(&g, ctx->grid.p, sizeof(g), hipMemcpyDeviceToHost, ctx->stream));
+        WTP_HIP(ctx, hipMemcpyAsync(&taken, ctx->rad_pos.p, sizeof(taken), hipMemcpyDeviceToHost, ctx->stream));
+        int rc = sync(ctx);
+        if (rc) return rc;
+        info_out[0] = ctx->rad_dense_used ? 1 : 0;
+        info_out[1] = g.rad_wave_only;
+        info_out[2] = radius_dense_hcap<T>();
+        for (int a = 0; a < 3; ++a) {
+            info_out[3 + a] = g.n[a];
+            info_out[7 + a] = (double)g.org[a];
+        }
+        info_out[6] = (double)g.c;
+        info_out[10] = (double)taken;
+        info_out[11] = (double)((int64_t)kRadArenaPerPoint * n);
+        info_out[12] = (double)n;
+        return (int)WTP_OK;
+    });
 }
 
 // ---- the sharded topology's local searches (wtp_block_topo.hip): the kernels of wtp_knn_dev / wtp_radius_* on the

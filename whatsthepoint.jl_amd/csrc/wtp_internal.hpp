@@ -66,6 +66,7 @@ constexpr int HCELLS = HX * HY * HZ;
 // kernel's 32 entries (a row is ~4.06 cells' worth of points): it belongs to the dense kernel, or to the wave kernel
 constexpr int kRadDenseMin = 1600;
 constexpr int kBrickThreads = 256;
+constexpr int kRadArenaPerPoint = 48; // RadiusTopology: ids of the count phase's arena per point of the cloud (wtp_api.hip)
 // partial-reduction slots: [0, brick_partials()) brick blocks, then kWavePartials, then kGenericPartials
 constexpr int kWavePartials = 4096;    // wave-per-query kernel blocks
 constexpr int kGenericPartials = 1024; // serial last-resort kernel blocks

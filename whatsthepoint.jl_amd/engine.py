@@ -113,6 +113,19 @@ class Context:
         L.check(self._h, rc)
         return offsets, idx[: int(offsets[-1])]
 
+    def radius_marks(self):
+        """Diagnostic of the last radius count on this context (wtp_radius_marks): (marks uint8[n], info dict).
+        marks: 0 = left to the fill phase, 1 = brick kernel row, 2 = row in the arena."""
+        info = (C.c_double * 13)()
+        L.check(self._h, self._lib.wtp_radius_marks(self._h, None, 0, info))  # n of the count, as the library holds it
+        n = int(info[12])
+        marks = np.empty(max(n, 1), dtype=np.uint8)
+        L.check(self._h, self._lib.wtp_radius_marks(self._h, _vp(marks), len(marks), info))
+        return marks[:n], dict(dense_used=bool(info[0]), rad_wave_only=int(info[1]), dense_hcap=int(info[2]),
+                                          cells=(int(info[3]), int(info[4]), int(info[5])), cell_edge=float(info[6]),
+                                          origin=(float(info[7]), float(info[8]), float(info[9])),
+                                          arena_taken=int(info[10]), arena_cap=int(info[11]))
+
     # ---- repel -------------------------------------------------------------------------------
     def relax(self, snap, n_fixed: int, spacing, force, k: int, alpha_lo: float, alpha_max: float, device_ptr=None):
         return RelaxSession(self, snap, n_fixed, spacing, force, k, alpha_lo, alpha_max, device_ptr=device_ptr)
