@@ -52,7 +52,7 @@ RD_CAP = 128          # wtp_radb.hip kRdCap (:365 park = m <= kRdCap)
 RD_CHUNK = 2048       # wtp_radb.hip kRdChunk (:366-374)
 WTP_ERR_STATE = 4     # include/wtp.h
 RAD_CAP = 512         # wtp_wave.hip kRadCap (:533 longer rows: the fb2 list, the serial kernel)
-ARENA_PER_POINT = 48  # wtp_api.hip:829
+ARENA_PER_POINT = 48  # wtp_internal.hpp kRadArenaPerPoint (wtp_topology.hip radius_count_t: arena_cap)
 WAVE_ONLY = 30.0      # wtp_hash.hip:178
 SHELL_MIN = 16        # wtp_radb.hip:112 (rows beyond 16 are grouped into shells)
 TWO_PER_LANE = 64     # wtp_radb.hip:65 (rows beyond 64: two entries per lane)

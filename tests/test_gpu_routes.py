@@ -33,18 +33,18 @@ pytestmark = pytest.mark.gpu
 
 FAST_KMAX = 32    # csrc/wtp_brick.hip kFastKMax: k >= 32 goes to the wave kernel
 KSEL_KMAX = 24    # csrc/wtp_ksel.hip kKsKMax (ksel_kmax()): largest k + self of the x-slowest k-selection
-KSEL_NMIN = 4096  # n >= 4096 for the k-selection layout (csrc/wtp_api.hip:434, :492, :1311, :1317)
-F64_KC_MAX = 31   # csrc/wtp_api.hip:527: candidate lists longer than 31 take the exact path
-F64K_KMAX = 22    # csrc/wtp_api.hip:1315: Float64 candidate sweeps for k <= 22 (k + 2 candidates <= 24)
+KSEL_NMIN = 4096  # n >= 4096 for the k-selection layout (csrc/wtp_topology.hip knn_dev_t, f64_candidates; wtp_relax.hip sweep_route<T>)
+F64_KC_MAX = 31   # csrc/wtp_topology.hip knn_dev_f64: candidate lists longer than 31 take the exact path
+F64K_KMAX = 22    # csrc/wtp_relax.hip sweep_route<T> (f64k): Float64 candidate sweeps for k <= 22 (k + 2 candidates <= 24)
 CLIPPED = 2       # WTP_FORCE_CLIPPED_SPACING
 
 
 def _topology32(dim, k, include_self, n):
     """The fp32 KNNTopology kernel of k rows (k + self searched) — knn_dev_t and launch_topology<float>."""
-    kq = k if include_self else k + 1                      # wtp_api.hip:431 (kq: neighbours sought, self included)
+    kq = k if include_self else k + 1                      # wtp_topology.hip knn_dev_t (kq: neighbours sought, self included)
     if k > FAST_KMAX - 1:                                  # wtp_brick.hip:893 (a.k > kFastKMax - 1: the wave kernel)
         return "exact"
-    if dim == 3 and kq <= KSEL_KMAX and n >= KSEL_NMIN:    # wtp_api.hip:434 (the x-slowest layout)
+    if dim == 3 and kq <= KSEL_KMAX and n >= KSEL_NMIN:    # wtp_topology.hip knn_dev_t: ksel (the x-slowest layout)
         if k == 24:                                        # wtp_ksel.hip:729
             return "ksel<0,24>"
         return "ksel<0,21>" if k == 21 else "ksel<0,0>"    # wtp_ksel.hip:730
@@ -55,31 +55,31 @@ def knn_route(dtype, dim, k, include_self, n):
     """Route of ctx.knn: fp32 through knn_dev_t, fp64 through knn_dev_f64 (fp32 candidates, fp64 re-ranking)."""
     if np.dtype(dtype) == np.float32:
         return _topology32(dim, k, include_self, n)
-    kq = k if include_self else k + 1                      # wtp_api.hip:520
-    kc = min(kq + 2, n)                                    # wtp_api.hip:524-525
-    if kc > F64_KC_MAX:                                    # wtp_api.hip:527 (launch_topology<double>: the wave kernel)
+    kq = k if include_self else k + 1                      # wtp_topology.hip knn_dev_f64: kq
+    kc = min(kq + 2, n)                                    # wtp_topology.hip knn_dev_f64: kc
+    if kc > F64_KC_MAX:                                    # wtp_topology.hip knn_dev_f64 (launch_topology<double>: the wave kernel)
         return "exact"
-    cand = _topology32(dim, kc, True, n)                   # wtp_api.hip:492 and f64_candidates: kc with self, fp32
-    refine = "slots" if kc == 24 else "refine"             # wtp_api.hip:541 (refine_f64_slots_kernel at kc == 24)
+    cand = _topology32(dim, kc, True, n)                   # wtp_topology.hip f64_candidates: kc with self, fp32
+    refine = "slots" if kc == 24 else "refine"             # wtp_topology.hip knn_dev_f64: slots (refine_f64_slots_kernel at kc == 24)
     return f"f64:{cand}+{refine}"
 
 
 def sweep_route(dtype, dim, k, kind, n, ball64=True):
-    """Route of a fresh sweep (sweep_route<T>, wtp_api.hip:1291-1319, then step_route :1347-1355 with a measured grid),
+    """Route of a fresh sweep (wtp_relax.hip: sweep_route<T>, then step_route with a measured grid),
     with the kernel instance it launches (launch_brick_sweep, wtp_brick.hip:910; launch_ksel_sweep, wtp_ksel.hip:735)."""
     clipped = kind == CLIPPED
     f64 = np.dtype(dtype) == np.float64
-    if clipped and 2 <= k < 32:                            # wtp_api.hip:1297 (compact support)
+    if clipped and 2 <= k < 32:                            # wtp_relax.hip sweep_route<T>: compact support
         if f64:
-            return "Cs64" if ball64 else "Cs64Wave"        # wtp_api.hip:1298
-        return "Cs2" if dim == 3 else "Cs<1,0,1>"          # wtp_api.hip:1299
-    if f64:                                                # wtp_api.hip:1305-1306 (k-nearest laws, 3-D, 2 <= k <= 22)
+            return "Cs64" if ball64 else "Cs64Wave"        # wtp_relax.hip sweep_route<T>: ctx->ball64
+        return "Cs2" if dim == 3 else "Cs<1,0,1>"          # wtp_relax.hip sweep_route<T>: r.dim
+    if f64:                                                # wtp_relax.hip sweep_route<T>: f64k (k-nearest laws, 3-D, 2 <= k <= 22)
         return "F64Ksel" if dim == 3 and not clipped and 2 <= k <= F64K_KMAX and n >= KSEL_NMIN else "Exact"
-    if k >= 32:                                            # wtp_api.hip:1308
+    if k >= 32:                                            # wtp_relax.hip sweep_route<T>: beyond the brick kernels' lists
         return "Exact"
-    if dim == 3 and 2 <= k <= KSEL_KMAX and n >= KSEL_NMIN:  # wtp_api.hip:1311
+    if dim == 3 and 2 <= k <= KSEL_KMAX and n >= KSEL_NMIN:  # wtp_relax.hip sweep_route<T>: ksel
         return "Ksel<1,21>" if k == 21 else "Ksel<1,0>"
-    return "Select<1,21,0>" if k == 21 else "Select<1,0,0>"  # wtp_api.hip:1312
+    return "Select<1,21,0>" if k == 21 else "Select<1,0,0>"  # wtp_relax.hip sweep_route<T>: Select
 
 
 FAST_SWEEP = {"Cs2", "Cs<1,0,1>", "Cs64", "Cs64Wave", "F64Ksel", "Ksel<1,21>", "Ksel<1,0>", "Select<1,21,0>",

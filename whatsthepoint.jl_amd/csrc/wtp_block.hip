@@ -366,7 +366,7 @@ __global__ void blk_gather_gid_kernel(const float4* __restrict__ P, int64_t n, i
 // ---- host side --------------------------------------------------------------------------------------------------------
 
 static int blk_sync(wtp_ctx* ctx, BlockState* b) {
-    ctx->ev_last_end = -1;
+    ctx->timers.ev_last_end = -1;
     WTP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->n_syncs += 1;
     (void)b;
@@ -874,7 +874,7 @@ static int blk_exchange_and_apply(wtp_ctx* ctx, BlockState* b) {
                 if ((rc = blk_streams(ctx))) return rc;
                 WTP_HIP(ctx, hipEventRecord(ctx->ev_comm_a, ctx->stream));
                 if ((rc = relax_prerank(ctx, n_sel + n_pool))) return rc;
-                ctx->ev_last_end = -1;
+                ctx->timers.ev_last_end = -1;
                 WTP_HIP(ctx, hipEventSynchronize(ctx->ev_comm_a));
                 ctx->n_syncs += 1;
             } else if ((rc = blk_sync(ctx, b)))

@@ -293,7 +293,7 @@ __global__ __launch_bounds__(256) void tp_radius_fill_kernel(int64_t n_own, cons
 // ---- host side --------------------------------------------------------------------------------------------------------
 
 static int tp_sync(wtp_ctx* ctx) {
-    ctx->ev_last_end = -1;
+    ctx->timers.ev_last_end = -1;
     WTP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->n_syncs += 1;
     return WTP_OK;

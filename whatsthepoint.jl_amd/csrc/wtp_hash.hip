@@ -934,7 +934,7 @@ int launch_reduce_partials(wtp_ctx* ctx, const Partial* parts, int n_parts, int 
                            wtp_step_stats* d_slot) {
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, parts, n_parts, used_brick,
                        brick_partials(), used_wave, used_generic, fb_count, uncovered, escaped, d_slot,
-                       (int32_t*)ctx->fb_count.p);
+                       &step_counters(ctx)->brick_handbacks); // (the block's first word: the kernel zeroes all 16)
     ctx->counters_clean = true;
     WTP_HIP(ctx, hipGetLastError());
     return WTP_OK;

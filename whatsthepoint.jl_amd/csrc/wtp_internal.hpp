@@ -8,7 +8,9 @@
 //   Points of one cell are contiguous, cells of one x-row are contiguous.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
+#include <functional>
 #include <map>
 #include <string>
 #include <utility>
@@ -66,7 +68,7 @@ constexpr int HCELLS = HX * HY * HZ;
 // kernel's 32 entries (a row is ~4.06 cells' worth of points): it belongs to the dense kernel, or to the wave kernel
 constexpr int kRadDenseMin = 1600;
 constexpr int kBrickThreads = 256;
-constexpr int kRadArenaPerPoint = 48; // RadiusTopology: ids of the count phase's arena per point of the cloud (wtp_api.hip)
+constexpr int kRadArenaPerPoint = 48; // RadiusTopology: ids of the count phase's arena per point of the cloud (radius_count_t, wtp_topology.hip)
 // partial-reduction slots: [0, brick_partials()) brick blocks, then kWavePartials, then kGenericPartials
 constexpr int kWavePartials = 4096;    // wave-per-query kernel blocks
 constexpr int kGenericPartials = 1024; // serial last-resort kernel blocks
@@ -92,6 +94,27 @@ struct Partial {
     int64_t argmin_j;
     int64_t n_move;
 };
+
+// The 64-byte counter block of a search (ctx->fb_count; the float copy's in F64Stage::cnt): cleared with one memset before
+// the kernels count in it, read and zeroed again, all 16 words, by a step's final reduction (reduce_partials_block).
+// SearchArgs hands the kernels the address of each word.
+struct StepCounters {
+    int32_t brick_handbacks, pad1_; // [0] queries the brick kernels hand to the wave kernel (SearchArgs::fb_count)
+    int32_t nn_count, pad3_;        // [2] wtp_cs2.hip: queries whose nearest neighbour the follow-up kernel still has to find
+    int32_t wave_handbacks, pad5_;  // [4] queries the wave kernel hands to the serial one (SearchArgs::fb2_count)
+    int32_t ball_count, pad7_;      // [6] what the ball kernel leaves for the exact path
+    int32_t uncovered, pad9_[3];    // [8] sharded sessions: queries whose neighbourhood reaches past the covered range
+    int32_t escaped, pad13_[3];     // [12] octree wall rule: movable points that left the mesh in this sweep
+};
+static_assert(sizeof(StepCounters) == 64 && offsetof(StepCounters, escaped) == 48, "16 words: the reduction zeroes exactly these");
+
+// RadiusTopology's counter block (RadiusState::pos), cleared by every count phase
+struct RadCursor {
+    unsigned long long arena_next; // [0, 8) next free id of the arena (wtp_radb.hip takes pieces of it)
+    int32_t bricks_listed;         // [8, 12) bricks listed for the dense kernel
+    int32_t dense_queries;         // [12, 16) diagnostics: queries the dense kernel served (WTP_DEBUG prints it)
+};
+static_assert(sizeof(RadCursor) == 16, "wtp_radb.hip addresses these words by offset");
 
 struct ForceParams {
     int32_t kind;
@@ -164,7 +187,7 @@ template <typename T> struct SearchArgs {
     const uint8_t* brick_dead; // wtp_cs2.hip, variable spacing: bricks whose points all went to the ball kernel's list already (cs2_dead_kernel), or nullptr
     int32_t brick_dead_cap;
     int32_t cs2_chunked;       // wtp_cs2.hip: runs longer than the hit masks are taken in chunks (variable spacing, several points per cell)
-    int32_t counters_cleared;  // topology calls: the caller cleared fb_count / fb2_count (one 64-byte block) itself
+    int32_t counters_cleared;  // topology calls: the caller cleared fb_count / fb2_count (one StepCounters block) itself
     int32_t fb_r0;             // first block radius (cells) of the exact path for hand-backs; 0: the default (2: the 27 cells failed already)
     int32_t ksel_bx;           // > 0: the grid was built for the k-selection kernels of wtp_ksel.hip; largest brick length along x
     unsigned long long* diag;  // -DWTP_DIAG builds: per-phase wave-cycle sums (8 slots), else unused
@@ -235,7 +258,7 @@ struct Prerank {
     const void *cnt = nullptr, *cr = nullptr, *dirty = nullptr;
 };
 
-// Measured tuning of a grid (build_hash_tuned, ksel_tune in wtp_api.hip): the key it was measured for and what was measured.
+// Measured tuning of a grid (build_hash_tuned, ksel_tune in wtp_tune.hip): the key it was measured for and what was measured.
 // The topology calls keep one per context; a relax session keeps one for its own grid (only `valid` of the key: measured
 // once per session) and one for the float copy of its Float64 sweeps.
 struct GridTune {
@@ -250,7 +273,7 @@ struct GridTune {
     int bx = 0, hcap = 0;    // wtp_ksel.hip: brick length along x and LDS point area (0: not measured)
 };
 
-// The kernels of a relax sweep on a fresh snapshot, chosen at every rebuild (sweep_route in wtp_api.hip).  A stale snapshot
+// The kernels of a relax sweep on a fresh snapshot, chosen at every rebuild (sweep_route in wtp_relax.hip).  A stale snapshot
 // (rebuild_every > 1) sends every query through the ball kernel on the routes that have one, else to the exact path.
 enum class SweepRoute {
     Exact,    // wave-per-query and serial kernels for every query
@@ -304,6 +327,65 @@ struct RelaxState {
     double cover_lo3[3] = {0, 0, 0}, cover_hi3[3] = {0, 0, 0}; // cover_axis == 3: a box (ends may be +-inf)
 };
 
+// ---- groups of wtp_ctx's fields ------------------------------------------------------------------------------------
+// radius two-phase state (wtp_radius_count / wtp_radius_offsets, then wtp_radius_fill)
+struct RadiusState {
+    int64_t n = 0;
+    int dim = 0, dtype = 0;
+    double r = 0;
+    int64_t nnz = 0;
+    bool valid = false;
+    bool offsets_dev = false; // wtp_radius_offsets left the CSR offsets in dist_out (device): fill may take them from there
+    DevBuf pos;               // counter block: one RadCursor
+    DevBuf bricks;            // the dense kernel's brick list
+    bool dense_attr[2] = {false, false}; // wtp_radb.hip: the kernel's LDS size has been declared (fp32, fp64)
+    bool dense_used = false;  // the count phase ran the dense kernel: the fill phase's wave kernel works from the hand-back list
+    DevBuf tmp, done;         // RadiusTopology: rows parked by the count phase (32 ids per query), one byte per query
+    DevBuf arena, arena_off;  // ... and the wave kernel's rows (any length), their starts; the bump counter sits behind the starts
+};
+
+// triangle mesh of the octree method (wtp_mesh.hip): bounding-volume tree nodes, pseudonormals
+struct MeshState {
+    DevBuf nodes, pn, io;
+    int64_t nt = 0;
+    int dtype = -1;
+    double bbox[6] = {0, 0, 0, 0, 0, 0};
+    double scale = 0;
+    std::vector<double> face_host; // unit face normals (the returned boundary's normals, src/repel.jl:614)
+    DevBuf wall_flags, wall_tri;   // per movable point: is_bnd | escaped (+ counter), landing triangle
+    DevBuf wall_hint;              // per movable point: tree node of its nearest triangle at the last sweep
+    DevBuf cls;                    // inside/outside class per cell of a uniform grid over the mesh bbox
+    bool cls_ready = false;
+    int cls_dim[3] = {0, 0, 0};
+    double cls_cell = 0;
+};
+
+struct KdTree {
+    DevBuf nodes;      // variable spacings: kd-tree over the boundary points (heap order)
+    int64_t m = 0;     // nodes in it; the key below identifies the boundary it was built from
+    uint64_t key = 0;
+    int dim = 0, dtype = -1;
+};
+
+struct Timers {
+    bool timing = false;      // per-phase event pairs around every step: off until wtp_timers_reset asks for them (6 event records per step are a third of a small cloud's step)
+    bool timing_forced = false; // WTP_TIMING in the environment decides, wtp_timers_reset does not
+    double t_hash = 0, t_sweep = 0, t_other = 0;
+    int64_t n_sweep_launches = 0;
+    std::vector<hipEvent_t> ev_pool;
+    struct Span { int a, b, kind; };
+    std::vector<Span> spans;
+    int ev_used = 0;
+    int ev_last_end = -1;     // the event that closed the latest span: the next span starts from it (no second record)
+};
+
+// fp64 sweeps through fp32 candidates (wtp_sweep64.hip): the session's grid, cell table and box parked while the float
+// copy's are built and searched; the fp64 points and their session slots in the float copy's order; the search's own
+// lists and their counter block (a StepCounters)
+struct F64Stage {
+    DevBuf grid_b, cell_start_b, box_b, s64, slot, lists, cnt;
+};
+
 } // namespace wtp
 
 struct wtp_ctx {
@@ -340,47 +422,25 @@ struct wtp_ctx {
     wtp::DevBuf box_dev;       // robust box {lo xyz, hi xyz} (doubles) + histogram scratch behind it
     wtp::DevBuf idx_out, dist_out, counts_out;
     wtp::DevBuf cand_idx, cand_dist, f32_pts; // fp64 topology: fp32 candidate lists and the float copy of the cloud
-    // fp64 sweeps through fp32 candidates (wtp_sweep64.hip): the session's grid, cell table and box parked while the float
-    // copy's are built and searched; the fp64 points and their session slots in the float copy's order; the search's own lists
-    wtp::DevBuf grid_b, cell_start_b, box_b, f64k_s64, f64k_slot, f64k_lists, f64k_cnt;
+    wtp::F64Stage f64k;
     wtp::DevBuf forces, nn_dist, nn_id, spacing_pp;
     wtp::DevBuf partials, stats, fb_list, fb_count, fb2_list, fb2_count, nn_list;
-    wtp::DevBuf rad_pos;           // counter block: [0, 8) next free id of the arena (wtp_radb.hip takes pieces of it), [8, 12) bricks listed
-    wtp::DevBuf rad_bricks;        // the dense kernel's brick list
-    bool rad_dense_attr[2] = {false, false}; // wtp_radb.hip: the kernel's LDS size has been declared (fp32, fp64)
-    bool rad_dense_used = false;   // the count phase ran the dense kernel: the fill phase's wave kernel works from the hand-back list
-    wtp::DevBuf rad_tmp, rad_done; // RadiusTopology: rows parked by the count phase (32 ids per query), one byte per query
-    wtp::DevBuf rad_arena, rad_arena_off; // ... and the wave kernel's rows (any length), their starts; the bump counter sits behind the starts
+    wtp::RadiusState rad;
     wtp::DevBuf brick_dead;    // wtp_cs2.hip, variable spacing: one byte per brick (cs2_dead_kernel)
     wtp::Prerank prerank;             // wtp_hash.hip: prerank_old_snapshot
     int64_t preranked_builds = 0;     // hash builds that took a first half over
     hipStream_t comm_stream = nullptr; // block driver: the grouped exchange runs here while the owned points are ranked
     hipEvent_t ev_comm_a = nullptr, ev_comm_b = nullptr;
     bool hash_scratch_clean = false;  // cell counts and dirty map are all-zero (every completed build leaves them so)
-    bool counters_clean = false;      // the 64-byte counter block is all-zero (the step's final reduction leaves it so)
+    bool counters_clean = false;      // the counter block (StepCounters in fb_count) is all-zero (the step's final reduction leaves it so)
     wtp::DevBuf stop_state;           // wtp_relax_run_until: {stopped, reason, n_done, last_impr, best_cv} on the device
     const int32_t* stop_dev = nullptr; // its first word while such a run is enqueued, else NULL (kernels then never look)
     wtp::DevBuf scratch;       // misc (relax_get staging, radius rows)
     wtp::DevBuf diag;          // diagnostic builds only
     wtp::DevBuf ins_in, ins_elems, ins_partial, ins_out; // isinside filter
-    // triangle mesh of the octree method (wtp_mesh.hip): bounding-volume tree nodes, pseudonormals
-    wtp::DevBuf mesh_nodes, mesh_pn, mesh_io;
-    int64_t mesh_nt = 0;
-    int mesh_dtype = -1;
-    double mesh_bbox[6] = {0, 0, 0, 0, 0, 0};
-    double mesh_scale = 0;
-    std::vector<double> mesh_face_host; // unit face normals (the returned boundary's normals, src/repel.jl:614)
-    wtp::DevBuf wall_flags, wall_tri;   // per movable point: is_bnd | escaped (+ counter), landing triangle
-    wtp::DevBuf wall_hint;              // per movable point: tree node of its nearest triangle at the last sweep
-    wtp::DevBuf mesh_cls;               // inside/outside class per cell of a uniform grid over the mesh bbox
-    bool mesh_cls_ready = false;
-    int mesh_cls_dim[3] = {0, 0, 0};
-    double mesh_cls_cell = 0;
+    wtp::MeshState mesh;
     wtp::DevBuf sp_hint;       // variable spacings: nearest tree node of each snapshot point at the last sweep
-    wtp::DevBuf kd_nodes;      // variable spacings: kd-tree over the boundary points (heap order)
-    int64_t kd_m = 0;          // nodes in it; the key below identifies the boundary it was built from
-    uint64_t kd_key = 0;
-    int kd_dim = 0, kd_dtype = -1;
+    wtp::KdTree kd;
     int64_t n_syncs = 0;       // host synchronisations of the context's stream so far (wtp_block_info.host_syncs counts with it)
     void* block = nullptr;     // wtp::BlockState (wtp_block.hip): this rank's share of a block-decomposed repel
     void* block_topo = nullptr; // wtp::TopoState (wtp_block_topo.hip): buffers of the sharded KNN / radius rows
@@ -390,30 +450,22 @@ struct wtp_ctx {
     wtp::DevBuf sp_cert;       // device-evaluated spacing laws: per point, where it stood at its last tree walk and the bound that walk left (wtp_spacing.hip)
     void* host_pinned = nullptr;
     size_t host_pinned_cap = 0;
-    // radius two-phase state
-    int64_t rad_n = 0;
-    int rad_dim = 0, rad_dtype = 0;
-    double rad_r = 0;
-    int64_t rad_nnz = 0;
-    bool rad_valid = false;
-    bool rad_offsets_dev = false; // wtp_radius_offsets left the CSR offsets in dist_out (device): fill may take them from there
     wtp::RelaxState relax;
-    // timers
-    bool timing = false;      // per-phase event pairs around every step: off until wtp_timers_reset asks for them (6 event records per step are a third of a small cloud's step)
-    bool timing_forced = false; // WTP_TIMING in the environment decides, wtp_timers_reset does not
-    double t_hash = 0, t_sweep = 0, t_other = 0;
-    int64_t n_sweep_launches = 0;
-    std::vector<hipEvent_t> ev_pool;
-    struct Span { int a, b, kind; };
-    std::vector<Span> spans;
-    int ev_used = 0;
-    int ev_last_end = -1;     // the event that closed the latest span: the next span starts from it (no second record)
+    wtp::Timers timers;
 };
 
 namespace wtp {
 
-// error plumbing
+inline StepCounters* step_counters(wtp_ctx* ctx) { return (StepCounters*)ctx->fb_count.p; } // the context's counter block
+
+// ---- wtp_context.hip: error plumbing, the buffer pool, timing spans, the entry points' argument checks ---------
 int fail(wtp_ctx* ctx, int code, const std::string& msg);
+int sync(wtp_ctx* ctx);        // the host waits for the context's stream (counted in n_syncs)
+size_t tsize(int dtype);       // bytes of a coordinate
+size_t pt_size(int dtype);     // bytes of a Pt record
+int check_cloud(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype);
+int check_idle(wtp_ctx* ctx);  // no relax session holds the context's buffers
+int check_k(wtp_ctx* ctx, int64_t n, int k, int include_self);
 int ensure_pinned(wtp_ctx* ctx, size_t bytes); // the context's page-locked staging block, at least this large
 #define WTP_HIP(ctx, call)                                                                    \
     do {                                                                                      \
@@ -433,6 +485,29 @@ int launch_occupancy_of(wtp_ctx* ctx, const void* fn, int threads, size_t smem);
 int span_begin(wtp_ctx* ctx, int kind);
 void span_end(wtp_ctx* ctx, int span);
 void spans_collect(wtp_ctx* ctx);
+
+// ---- wtp_tune.hip: measured grids (see GridTune) and the owner of the context's grid ----------------------------
+template <typename T> int build_hash_tuned(wtp_ctx* ctx, GridTune& t, HashBuild<T> b, Grid<T>* hg_out, double* rho_eff_out);
+template <typename T> int ksel_tune(wtp_ctx* ctx, GridTune& t, HashBuild<T> b, Grid<T>& hg, double& rho_eff);
+template <typename T> int build_grid_cached(wtp_ctx* ctx, GridTune& t, HashBuild<T> b, bool ksel);
+template <typename T>
+void init_search(SearchArgs<T>& a, const wtp_ctx* ctx, const Pt<T>* snap, const Pt<T>* query, int64_t n, int k, int include_self);
+double ksel_rho_for(int kq);
+double ksel_cap_count(int kq);
+int cs2_tune(wtp_ctx* ctx, RelaxState& r, const Grid<float>& hg, double rho_eff);
+void grid_taken(wtp_ctx* ctx); // a call is about to build, or has built, its hash on ctx->grid: what others left there is void
+
+// ---- wtp_topology.hip: the Float64 candidate stage, shared with the session's fp64 sweep ------------------------
+int f64_candidates(wtp_ctx* ctx, const double4* pts, int64_t n, int dim, int kc, GridTune& t, SearchArgs<float>& b, int& sp,
+                   const double** org4_out, const std::function<int(float4*)>& relabel);
+
+// ---- wtp_spacing.hip: the spacing laws' host side (wtp_relax_init, wtp_spacing_eval) -----------------------------
+bool spacing_on_device(int kind);
+int check_spacing_law(wtp_ctx* ctx, const wtp_spacing_desc* s);
+int ensure_kd(wtp_ctx* ctx, const wtp_spacing_desc* s, int dim, int dtype); // the kd-tree over the law's boundary, cached per context
+
+// ---- wtp_relax.hip -------------------------------------------------------------------------------------------------
+int flush_pending(wtp_ctx* ctx); // materialise a pending fixed head (every entry point that reads P calls it first)
 
 // ---- launch wrappers (implemented per translation unit) ----------------------------------------
 // hash build (HashBuild above) into ctx->grid, ctx->cell_start and b.out
@@ -561,7 +636,7 @@ int launch_layers(wtp_ctx* ctx, const Pt<T>* pts, int64_t n, int64_t n_fixed, in
                   double lo_out, double hi_out, Pt<T>* d_lo, Pt<T>* d_hi, int64_t cap, int2* d_blk, int32_t* d_totals,
                   bool slot_ordered, double reach);
 template <typename T> int launch_append_fixed(wtp_ctx* ctx, const Pt<T>* d_src, int64_t n, Pt<T>* d_dst);
-// block decomposition (wtp_block.hip) <-> session internals (wtp_api.hip)
+// block decomposition (wtp_block.hip) <-> session internals (wtp_relax.hip)
 int relax_step_enqueue(wtp_ctx* ctx, int rebuild, wtp_step_stats* d_slot); // one sweep, statistics into a device slot, no synchronisation
 int relax_swap_begin(wtp_ctx* ctx, int64_t n_move_new, void** d_buf_out);  // a free point buffer for a replaced movable set ...
 int relax_swap_commit(wtp_ctx* ctx, int64_t n_move_new);                   // ... which becomes the session's P (no fixed head, tuning kept)
@@ -572,9 +647,9 @@ template <typename T> int launch_radius_dense(wtp_ctx* ctx, SearchArgs<T>& a, T 
 template <typename T> int radius_dense_hcap();
 int launch_cs_all_slots(wtp_ctx* ctx, int32_t* list, int32_t n, int32_t* count); // wtp_cs2.hip: list = 0 .. n-1, *count = n
 int launch_cs_ball64(wtp_ctx* ctx, SearchArgs<double>& a, int32_t* rest_list, int32_t* rest_count); // wtp_ball64.hip
-int relax_prerank(wtp_ctx* ctx, int64_t n_fixed_new); // first half of the next rebuild's hash, ahead of wtp_relax_set_fixed_dev (see wtp_api.hip)
+int relax_prerank(wtp_ctx* ctx, int64_t n_fixed_new); // first half of the next rebuild's hash, ahead of wtp_relax_set_fixed_dev (see wtp_relax.hip)
 void block_destroy(wtp_ctx* ctx);                                          // frees ctx->block (wtp_destroy)
-// sharded topology (wtp_block_topo.hip) <-> block driver (wtp_block.hip) and the single-context searches (wtp_api.hip)
+// sharded topology (wtp_block_topo.hip) <-> block driver (wtp_block.hip) and the single-context searches (wtp_topology.hip)
 void block_topo_destroy(wtp_ctx* ctx);                                     // frees ctx->block_topo (wtp_destroy)
 bool block_session_open(wtp_ctx* ctx);                                     // a wtp_block_open session is active
 const wtp_transport* block_host_transport(wtp_ctx* ctx);                   // wtp_block_set_transport's callbacks, or NULL: RCCL

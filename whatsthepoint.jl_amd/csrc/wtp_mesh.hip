@@ -655,17 +655,17 @@ static int mesh_grid(int64_t n) {
 
 template <typename TM> static MeshView<TM> make_view(const wtp_ctx* ctx) {
     MeshView<TM> mv;
-    mv.nodes = (const MeshNode<TM>*)ctx->mesh_nodes.p;
-    mv.pn = (const TM*)ctx->mesh_pn.p;
-    mv.m = (int32_t)ctx->mesh_nt;
+    mv.nodes = (const MeshNode<TM>*)ctx->mesh.nodes.p;
+    mv.pn = (const TM*)ctx->mesh.pn.p;
+    mv.m = (int32_t)ctx->mesh.nt;
     for (int a = 0; a < 3; ++a) {
-        mv.lo[a] = (TM)ctx->mesh_bbox[a];
-        mv.hi[a] = (TM)ctx->mesh_bbox[3 + a];
+        mv.lo[a] = (TM)ctx->mesh.bbox[a];
+        mv.hi[a] = (TM)ctx->mesh.bbox[3 + a];
     }
-    mv.scale = (TM)ctx->mesh_scale;
-    mv.cls = ctx->mesh_cls_ready ? (const uint8_t*)ctx->mesh_cls.p : nullptr;
-    for (int a = 0; a < 3; ++a) mv.cdim[a] = ctx->mesh_cls_dim[a];
-    mv.cinv = (TM)(1.0 / (ctx->mesh_cls_cell > 0 ? ctx->mesh_cls_cell : 1.0));
+    mv.scale = (TM)ctx->mesh.scale;
+    mv.cls = ctx->mesh.cls_ready ? (const uint8_t*)ctx->mesh.cls.p : nullptr;
+    for (int a = 0; a < 3; ++a) mv.cdim[a] = ctx->mesh.cls_dim[a];
+    mv.cinv = (TM)(1.0 / (ctx->mesh.cls_cell > 0 ? ctx->mesh.cls_cell : 1.0));
     return mv;
 }
 
@@ -681,7 +681,7 @@ static int launch_mesh_query(wtp_ctx* ctx, const TP* d_xyz, int64_t n, double of
 template <typename TP>
 int launch_mesh_constrain(wtp_ctx* ctx, const Pt<TP>* old, Pt<TP>* cur, int64_t n, int64_t n_fixed, double offset,
                           const uint8_t* is_bnd, uint8_t* escaped, int32_t* tri_idx, int32_t* hint, int32_t* n_escaped) {
-    if (ctx->mesh_dtype == WTP_F32)
+    if (ctx->mesh.dtype == WTP_F32)
         hipLaunchKernelGGL((mesh_constrain_kernel<float, TP>), dim3(mesh_grid(n)), dim3(kMeshThreads), 0, ctx->stream, old,
                            cur, n, (int32_t)n_fixed, make_view<float>(ctx), (float)offset, is_bnd, escaped, tri_idx,
                            hint, n_escaped);
@@ -702,29 +702,29 @@ template int launch_mesh_constrain<double>(wtp_ctx*, const Pt<double>*, Pt<doubl
 template <typename TM> static int mesh_classes_t(wtp_ctx* ctx, double cell) {
     double ext[3], vol = 1;
     for (int a = 0; a < 3; ++a) {
-        ext[a] = ctx->mesh_bbox[3 + a] - ctx->mesh_bbox[a];
+        ext[a] = ctx->mesh.bbox[3 + a] - ctx->mesh.bbox[a];
         vol *= ext[a];
     }
     const double floor_cell = std::cbrt(vol / 67108864.0);
     if (!(cell > floor_cell)) cell = floor_cell;
-    if (ctx->mesh_cls_ready && ctx->mesh_cls_cell <= cell * 1.0001 && ctx->mesh_cls_cell >= cell * 0.5) return WTP_OK;
+    if (ctx->mesh.cls_ready && ctx->mesh.cls_cell <= cell * 1.0001 && ctx->mesh.cls_cell >= cell * 0.5) return WTP_OK;
     int64_t ncell = 1;
     for (int a = 0; a < 3; ++a) {
         int64_t d = (int64_t)std::ceil(ext[a] / cell);
         d = d < 1 ? 1 : d;
-        ctx->mesh_cls_dim[a] = (int)d;
+        ctx->mesh.cls_dim[a] = (int)d;
         ncell *= d;
     }
     if (ncell > 200000000LL) return fail(ctx, WTP_ERR_ARG, "mesh class grid too large");
     int rc;
-    ctx->mesh_cls_ready = false;
-    if ((rc = ensure(ctx, ctx->mesh_cls, (size_t)ncell))) return rc;
-    ctx->mesh_cls_cell = cell;
+    ctx->mesh.cls_ready = false;
+    if ((rc = ensure(ctx, ctx->mesh.cls, (size_t)ncell))) return rc;
+    ctx->mesh.cls_cell = cell;
     MeshView<TM> mv = make_view<TM>(ctx);
     hipLaunchKernelGGL((mesh_classify_kernel<TM>), dim3(mesh_grid(ncell)), dim3(kMeshThreads), 0, ctx->stream, mv,
-                       (TM)cell, ncell, (uint8_t*)ctx->mesh_cls.p);
+                       (TM)cell, ncell, (uint8_t*)ctx->mesh.cls.p);
     WTP_HIP(ctx, hipGetLastError());
-    ctx->mesh_cls_ready = true;
+    ctx->mesh.cls_ready = true;
     return WTP_OK;
 }
 
@@ -733,21 +733,21 @@ static size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 template <typename TM> static int mesh_set_t(wtp_ctx* ctx, const TM* verts, int64_t nv, const int32_t* tris, int64_t nt) {
     std::vector<MeshNode<TM>> nodes((size_t)nt);
     std::vector<TM> pn((size_t)nt * 21);
-    mesh_build_host<TM>(verts, tris, nt, nodes.data(), pn.data(), ctx->mesh_bbox, nv);
+    mesh_build_host<TM>(verts, tris, nt, nodes.data(), pn.data(), ctx->mesh.bbox, nv);
     double sc = 0;
-    for (int a = 0; a < 6; ++a) sc = std::max(sc, std::fabs(ctx->mesh_bbox[a]));
-    ctx->mesh_scale = sc;
+    for (int a = 0; a < 6; ++a) sc = std::max(sc, std::fabs(ctx->mesh.bbox[a]));
+    ctx->mesh.scale = sc;
     int rc;
-    if ((rc = ensure(ctx, ctx->mesh_nodes, sizeof(MeshNode<TM>) * (size_t)nt))) return rc;
-    if ((rc = ensure(ctx, ctx->mesh_pn, sizeof(TM) * 21 * (size_t)nt))) return rc;
-    WTP_HIP(ctx, hipMemcpyAsync(ctx->mesh_nodes.p, nodes.data(), sizeof(MeshNode<TM>) * (size_t)nt, hipMemcpyHostToDevice,
+    if ((rc = ensure(ctx, ctx->mesh.nodes, sizeof(MeshNode<TM>) * (size_t)nt))) return rc;
+    if ((rc = ensure(ctx, ctx->mesh.pn, sizeof(TM) * 21 * (size_t)nt))) return rc;
+    WTP_HIP(ctx, hipMemcpyAsync(ctx->mesh.nodes.p, nodes.data(), sizeof(MeshNode<TM>) * (size_t)nt, hipMemcpyHostToDevice,
                                 ctx->stream));
-    WTP_HIP(ctx, hipMemcpyAsync(ctx->mesh_pn.p, pn.data(), sizeof(TM) * 21 * (size_t)nt, hipMemcpyHostToDevice,
+    WTP_HIP(ctx, hipMemcpyAsync(ctx->mesh.pn.p, pn.data(), sizeof(TM) * 21 * (size_t)nt, hipMemcpyHostToDevice,
                                 ctx->stream));
     WTP_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the host vectors go out of scope
-    ctx->mesh_face_host.assign((size_t)nt * 3, 0.0);
+    ctx->mesh.face_host.assign((size_t)nt * 3, 0.0);
     for (int64_t t = 0; t < nt; ++t)
-        for (int a = 0; a < 3; ++a) ctx->mesh_face_host[3 * t + a] = (double)pn[21 * t + a];
+        for (int a = 0; a < 3; ++a) ctx->mesh.face_host[3 * t + a] = (double)pn[21 * t + a];
     return WTP_OK;
 }
 
@@ -769,13 +769,13 @@ WTP_API int wtp_mesh_set(wtp_ctx* ctx, const void* vertices, int64_t nv, const i
     if (ctx->relax.active && ctx->relax.wall_active)
         return fail(ctx, WTP_ERR_STATE, "the relax session uses the current mesh: call wtp_relax_end first");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->mesh_nt = 0;
-    ctx->mesh_cls_ready = false;
+    ctx->mesh.nt = 0;
+    ctx->mesh.cls_ready = false;
     const int rc = dtype == WTP_F32 ? mesh_set_t<float>(ctx, (const float*)vertices, nv, triangles, nt)
                                     : mesh_set_t<double>(ctx, (const double*)vertices, nv, triangles, nt);
     if (rc) return rc;
-    ctx->mesh_nt = nt;
-    ctx->mesh_dtype = dtype;
+    ctx->mesh.nt = nt;
+    ctx->mesh.dtype = dtype;
     return WTP_OK;
 }
 
@@ -783,25 +783,25 @@ WTP_API int wtp_mesh_clear(wtp_ctx* ctx) {
     if (!ctx) return WTP_ERR_ARG;
     if (ctx->relax.active && ctx->relax.wall_active)
         return fail(ctx, WTP_ERR_STATE, "the relax session uses the current mesh: call wtp_relax_end first");
-    ctx->mesh_nt = 0;
-    ctx->mesh_cls_ready = false;
-    ctx->mesh_face_host.clear();
+    ctx->mesh.nt = 0;
+    ctx->mesh.cls_ready = false;
+    ctx->mesh.face_host.clear();
     return WTP_OK;
 }
 
 WTP_API int wtp_mesh_face_normals(wtp_ctx* ctx, double* normals_out) {
     if (!ctx) return WTP_ERR_ARG;
-    if (ctx->mesh_nt < 1) return fail(ctx, WTP_ERR_STATE, "no mesh: call wtp_mesh_set first");
+    if (ctx->mesh.nt < 1) return fail(ctx, WTP_ERR_STATE, "no mesh: call wtp_mesh_set first");
     if (!normals_out) return fail(ctx, WTP_ERR_ARG, "NULL array");
-    memcpy(normals_out, ctx->mesh_face_host.data(), sizeof(double) * ctx->mesh_face_host.size());
+    memcpy(normals_out, ctx->mesh.face_host.data(), sizeof(double) * ctx->mesh.face_host.size());
     return WTP_OK;
 }
 
 WTP_API int wtp_mesh_bounds(wtp_ctx* ctx, double bbox_out[6]) {
     if (!ctx) return WTP_ERR_ARG;
-    if (ctx->mesh_nt < 1) return fail(ctx, WTP_ERR_STATE, "no mesh: call wtp_mesh_set first");
+    if (ctx->mesh.nt < 1) return fail(ctx, WTP_ERR_STATE, "no mesh: call wtp_mesh_set first");
     if (!bbox_out) return fail(ctx, WTP_ERR_ARG, "NULL array");
-    memcpy(bbox_out, ctx->mesh_bbox, sizeof(double) * 6);
+    memcpy(bbox_out, ctx->mesh.bbox, sizeof(double) * 6);
     return WTP_OK;
 }
 
@@ -809,18 +809,18 @@ WTP_API int wtp_mesh_query(wtp_ctx* ctx, const void* xyz, int64_t n, int dtype, 
                            int32_t* tri_out, void* closest_out, uint8_t* inside_out, void* projected_out) {
     if (!ctx) return WTP_ERR_ARG;
     if (dtype != WTP_F32 && dtype != WTP_F64) return fail(ctx, WTP_ERR_ARG, "dtype must be WTP_F32 or WTP_F64");
-    if (ctx->mesh_nt < 1) return fail(ctx, WTP_ERR_STATE, "no mesh: call wtp_mesh_set first");
+    if (ctx->mesh.nt < 1) return fail(ctx, WTP_ERR_STATE, "no mesh: call wtp_mesh_set first");
     if (n < 0 || n > 2000000000LL) return fail(ctx, WTP_ERR_ARG, "bad n");
     if (n == 0) return WTP_OK;
     if (!xyz) return fail(ctx, WTP_ERR_ARG, "NULL array");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t ts = dtype == WTP_F64 ? 8 : 4;
-    // mesh_io: [xyz n*3 | sd n | cp n*3 | proj n*3 | tri n (int32) | inside n (u8)]
+    // mesh.io: [xyz n*3 | sd n | cp n*3 | proj n*3 | tri n (int32) | inside n (u8)]
     const size_t o_sd = al256(ts * n * 3), o_cp = o_sd + al256(ts * n), o_pr = o_cp + al256(ts * n * 3),
                  o_tr = o_pr + al256(ts * n * 3), o_in = o_tr + al256(4 * (size_t)n);
     int rc;
-    if ((rc = ensure(ctx, ctx->mesh_io, o_in + (size_t)n))) return rc;
-    char* b = (char*)ctx->mesh_io.p;
+    if ((rc = ensure(ctx, ctx->mesh.io, o_in + (size_t)n))) return rc;
+    char* b = (char*)ctx->mesh.io.p;
     WTP_HIP(ctx, hipMemcpyAsync(b, xyz, ts * n * 3, hipMemcpyHostToDevice, ctx->stream));
     int32_t* tri = tri_out ? (int32_t*)(b + o_tr) : nullptr;
     uint8_t* inside = inside_out ? (uint8_t*)(b + o_in) : nullptr;
@@ -829,7 +829,7 @@ WTP_API int wtp_mesh_query(wtp_ctx* ctx, const void* xyz, int64_t n, int dtype, 
         using TP = decltype(tp);
         TP *sd = sd_out ? (TP*)(b + o_sd) : nullptr, *cp = closest_out ? (TP*)(b + o_cp) : nullptr,
            *pr = projected_out ? (TP*)(b + o_pr) : nullptr;
-        return by_dtype(ctx->mesh_dtype, [&](auto tm) {
+        return by_dtype(ctx->mesh.dtype, [&](auto tm) {
             return launch_mesh_query<decltype(tm), TP>(ctx, (const TP*)b, n, offset, sd, tri, cp, inside, pr);
         });
     });
@@ -852,24 +852,24 @@ WTP_API int wtp_relax_set_wall(wtp_ctx* ctx, int64_t n_boundary, double offset_d
     int rc = need_session(ctx, __func__);
     if (rc) return rc;
     RelaxState& r = ctx->relax;
-    if (ctx->mesh_nt < 1) return fail(ctx, WTP_ERR_STATE, "no mesh: call wtp_mesh_set first");
+    if (ctx->mesh.nt < 1) return fail(ctx, WTP_ERR_STATE, "no mesh: call wtp_mesh_set first");
     if (r.dim != 3) return fail(ctx, WTP_ERR_ARG, "the wall rule is 3-D only (src/repel.jl:122)");
     const int64_t nm = r.n - r.n_fixed;
     if (n_boundary < 0 || n_boundary > nm) return fail(ctx, WTP_ERR_ARG, "n_boundary out of range");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    // wall_flags: [is_bnd nm | escaped nm | counter (int32, 256-aligned)]; wall_tri: int32 nm, -1 = none
+    // mesh.wall_flags: [is_bnd nm | escaped nm | counter (int32, 256-aligned)]; mesh.wall_tri: int32 nm, -1 = none
     const size_t o_cnt = al256(2 * (size_t)nm);
-    if ((rc = ensure(ctx, ctx->wall_flags, o_cnt + 256))) return rc;
-    if ((rc = ensure(ctx, ctx->wall_tri, 4 * (size_t)nm))) return rc;
-    if ((rc = ensure(ctx, ctx->wall_hint, 4 * (size_t)nm))) return rc;
+    if ((rc = ensure(ctx, ctx->mesh.wall_flags, o_cnt + 256))) return rc;
+    if ((rc = ensure(ctx, ctx->mesh.wall_tri, 4 * (size_t)nm))) return rc;
+    if ((rc = ensure(ctx, ctx->mesh.wall_hint, 4 * (size_t)nm))) return rc;
     // cells of about one spacing: only the points within a spacing or two of the wall take the exact test
     const double cell = r.spacing_kind == WTP_SPACING_CONSTANT ? r.spacing_const
                         : (r.spacing_kind == WTP_SPACING_BOUNDARY_LAYER ? r.sp_p0 : r.spacing_max / 2);
-    if ((rc = ctx->mesh_dtype == WTP_F32 ? mesh_classes_t<float>(ctx, cell) : mesh_classes_t<double>(ctx, cell))) return rc;
-    WTP_HIP(ctx, hipMemsetAsync(ctx->wall_hint.p, 0xff, 4 * (size_t)nm, ctx->stream));
-    WTP_HIP(ctx, hipMemsetAsync(ctx->wall_flags.p, 0, o_cnt + 256, ctx->stream));
-    if (n_boundary > 0) WTP_HIP(ctx, hipMemsetAsync(ctx->wall_flags.p, 1, (size_t)n_boundary, ctx->stream));
-    WTP_HIP(ctx, hipMemsetAsync(ctx->wall_tri.p, 0xff, 4 * (size_t)nm, ctx->stream));
+    if ((rc = ctx->mesh.dtype == WTP_F32 ? mesh_classes_t<float>(ctx, cell) : mesh_classes_t<double>(ctx, cell))) return rc;
+    WTP_HIP(ctx, hipMemsetAsync(ctx->mesh.wall_hint.p, 0xff, 4 * (size_t)nm, ctx->stream));
+    WTP_HIP(ctx, hipMemsetAsync(ctx->mesh.wall_flags.p, 0, o_cnt + 256, ctx->stream));
+    if (n_boundary > 0) WTP_HIP(ctx, hipMemsetAsync(ctx->mesh.wall_flags.p, 1, (size_t)n_boundary, ctx->stream));
+    WTP_HIP(ctx, hipMemsetAsync(ctx->mesh.wall_tri.p, 0xff, 4 * (size_t)nm, ctx->stream));
     r.wall_active = true;
     r.wall_offset = offset_dist;
     r.wall_nm = nm;
@@ -886,8 +886,8 @@ WTP_API int wtp_relax_get_wall(wtp_ctx* ctx, int32_t* tri_out, uint8_t* is_bnd_o
     if (!r.active || !r.wall_active) return fail(ctx, WTP_ERR_STATE, "no wall rule installed");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nm = (size_t)r.wall_nm;
-    char* f = (char*)ctx->wall_flags.p;
-    if (tri_out) WTP_HIP(ctx, hipMemcpyAsync(tri_out, ctx->wall_tri.p, 4 * nm, hipMemcpyDeviceToHost, ctx->stream));
+    char* f = (char*)ctx->mesh.wall_flags.p;
+    if (tri_out) WTP_HIP(ctx, hipMemcpyAsync(tri_out, ctx->mesh.wall_tri.p, 4 * nm, hipMemcpyDeviceToHost, ctx->stream));
     if (is_bnd_out) WTP_HIP(ctx, hipMemcpyAsync(is_bnd_out, f, nm, hipMemcpyDeviceToHost, ctx->stream));
     if (escaped_out) WTP_HIP(ctx, hipMemcpyAsync(escaped_out, f + nm, nm, hipMemcpyDeviceToHost, ctx->stream));
     if (clear_escaped) WTP_HIP(ctx, hipMemsetAsync(f + nm, 0, nm, ctx->stream));
@@ -904,8 +904,8 @@ WTP_API int wtp_relax_set_wall_flags(wtp_ctx* ctx, const uint8_t* is_bnd, const 
     if (!is_bnd || !tri) return fail(ctx, WTP_ERR_ARG, "NULL array");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nm = (size_t)r.wall_nm;
-    WTP_HIP(ctx, hipMemcpyAsync(ctx->wall_flags.p, is_bnd, nm, hipMemcpyHostToDevice, ctx->stream));
-    WTP_HIP(ctx, hipMemcpyAsync(ctx->wall_tri.p, tri, 4 * nm, hipMemcpyHostToDevice, ctx->stream));
+    WTP_HIP(ctx, hipMemcpyAsync(ctx->mesh.wall_flags.p, is_bnd, nm, hipMemcpyHostToDevice, ctx->stream));
+    WTP_HIP(ctx, hipMemcpyAsync(ctx->mesh.wall_tri.p, tri, 4 * nm, hipMemcpyHostToDevice, ctx->stream));
     WTP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return WTP_OK;
 }

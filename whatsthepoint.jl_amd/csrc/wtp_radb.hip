@@ -448,9 +448,9 @@ template <typename T> static int rd_hcap() {
 template <typename T> int launch_radius_dense(wtp_ctx* ctx, SearchArgs<T>& a, T r, int32_t* d_counts) {
     const int hcap = rd_hcap<T>();
     const size_t smem = rd_smem_bytes<T>(hcap);
-    if (!ctx->rad_dense_attr[sizeof(T) == 8]) { // (once per context: the call is not free, and the uniform clouds' rows never reach this kernel)
+    if (!ctx->rad.dense_attr[sizeof(T) == 8]) { // (once per context: the call is not free, and the uniform clouds' rows never reach this kernel)
         WTP_HIP(ctx, hipFuncSetAttribute((const void*)rad_dense_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        ctx->rad_dense_attr[sizeof(T) == 8] = true;
+        ctx->rad.dense_attr[sizeof(T) == 8] = true;
     }
     a.rad_dense = hcap;
     int32_t* n_bricks = (int32_t*)a.rad_arena_pos + 2; // (the counter block the caller cleared: [0, 8) the arena's next free id)

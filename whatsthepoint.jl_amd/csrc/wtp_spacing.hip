@@ -497,4 +497,68 @@ INST(float)
 INST(double)
 #undef INST
 
+// ---- variable spacings: kd-tree over the law's boundary points, cached per context -----------------
+bool spacing_on_device(int kind) { return kind == WTP_SPACING_LOGLIKE || kind == WTP_SPACING_BOUNDARY_LAYER; }
+
+int check_spacing_law(wtp_ctx* ctx, const wtp_spacing_desc* s) {
+    if (!s->boundary_xyz || s->n_boundary < 1)
+        return fail(ctx, WTP_ERR_ARG, "boundary_points must be non-empty"); // spacings.jl:61-62,106-107
+    if (s->n_boundary > 2000000000LL) return fail(ctx, WTP_ERR_ARG, "n_boundary exceeds the int32 index space");
+    if (s->kind == WTP_SPACING_BOUNDARY_LAYER && !(s->p2 > 0))
+        return fail(ctx, WTP_ERR_ARG, "layer_thickness must be positive"); // spacings.jl:108-109
+    return WTP_OK;
+}
+
+int ensure_kd(wtp_ctx* ctx, const wtp_spacing_desc* s, int dim, int dtype) {
+    const size_t ts = tsize(dtype);
+    const size_t bytes = ts * (size_t)s->n_boundary * dim;
+    uint64_t h = 1469598103934665603ull; // FNV-1a over the coordinates: same boundary -> same tree
+    const unsigned char* b = (const unsigned char*)s->boundary_xyz;
+    for (size_t i = 0; i < bytes; ++i) h = (h ^ b[i]) * 1099511628211ull;
+    if (ctx->kd.m == s->n_boundary && ctx->kd.key == h && ctx->kd.dim == dim && ctx->kd.dtype == dtype) return WTP_OK;
+    const size_t kdsz = by_dtype(dtype, [&](auto t) { return kd_bytes<decltype(t)>(s->n_boundary); });
+    int rc;
+    if ((rc = ensure(ctx, ctx->kd.nodes, kdsz))) return rc;
+    std::vector<char> host(kdsz);
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        kd_build_host<T>((const T*)s->boundary_xyz, s->n_boundary, dim, host.data());
+    });
+    WTP_HIP(ctx, hipMemcpyAsync(ctx->kd.nodes.p, host.data(), host.size(), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = sync(ctx))) return rc; // `host` dies with this scope
+    ctx->kd.m = s->n_boundary;
+    ctx->kd.key = h;
+    ctx->kd.dim = dim;
+    ctx->kd.dtype = dtype;
+    return WTP_OK;
+}
+
 } // namespace wtp
+
+using namespace wtp;
+
+#define WTP_API extern "C"
+
+WTP_API int wtp_spacing_eval(wtp_ctx* ctx, const wtp_spacing_desc* spacing, const void* xyz, int64_t n, int dim,
+                             int dtype, void* out) {
+    int rc = check_cloud(ctx, xyz, n, dim, dtype);
+    if (rc) return rc;
+    if (!spacing || !out) return fail(ctx, WTP_ERR_ARG, "spacing/out is NULL");
+    if (!spacing_on_device(spacing->kind))
+        return fail(ctx, WTP_ERR_ARG, "wtp_spacing_eval evaluates LOGLIKE / BOUNDARY_LAYER descriptors");
+    if ((rc = check_spacing_law(ctx, spacing))) return rc;
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t ts = tsize(dtype);
+    if ((rc = ensure_kd(ctx, spacing, dim, dtype))) return rc;
+    if ((rc = ensure(ctx, ctx->ins_in, ts * (size_t)n * dim))) return rc;
+    if ((rc = ensure(ctx, ctx->ins_out, ts * (size_t)n))) return rc;
+    WTP_HIP(ctx, hipMemcpyAsync(ctx->ins_in.p, xyz, ts * (size_t)n * dim, hipMemcpyHostToDevice, ctx->stream));
+    rc = by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_spacing_eval<T>(ctx, (const T*)ctx->ins_in.p, n, dim, ctx->kd.nodes.p, ctx->kd.m, spacing->kind,
+                                      spacing->p0, spacing->p1, spacing->p2, (T*)ctx->ins_out.p);
+    });
+    if (rc) return rc;
+    WTP_HIP(ctx, hipMemcpyAsync(out, ctx->ins_out.p, ts * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
+}

@@ -2,7 +2,7 @@
 // float (origin_kernel, to_local_f32_kernel), the fp32 k-selection kernels (wtp_ksel.hip) find the kc nearest CANDIDATES per
 // query on that copy, and one lane per query re-ranks them exactly in fp64 and certifies the first k: the fp32 search
 // excluded nothing nearer than its last candidate minus the rounding bound (f64_certified).  Queries the certificate turns
-// down take the exact path.  Two users (wtp_api.hip, through f64_candidates):
+// down take the exact path.  Two users (through f64_candidates, wtp_topology.hip):
 //  - Float64 KNNTopology (knn_dev_f64): refine_f64_kernel for any kc, refine_f64_slots_kernel for k = 21 without self;
 //  - Float64 sweeps of the laws that need the explicit k nearest neighbours (relax_f64_ksel_sweep; src/repel.jl:256-292
 //    with InverseDistance, Spacing, LennardJones forces: everything but ClippedSpacingForce, which has its compact-support
