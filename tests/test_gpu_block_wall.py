@@ -8,7 +8,8 @@ session itself does not reproduce); (b) 2 x 2 x 2 and 4 ranks as threads on the 
 carried by a loopback transport, reproduce the single-domain run with the same wall, also when the ghost layer is
 widened (the wall is selected again); (c) the closest pair is reported in the numbering of the assembled snapshot on
 every rank, across a face and against a wall point; (d) a graded cloud with BoundaryLayerSpacing of the wall; (e) the
-stop rules; (f) the entry point's argument and state checks."""
+stop rules, every exit of wtp_block_run_until against the plain session's; (f) the entry point's argument and state
+checks."""
 import ctypes as C
 
 import numpy as np
@@ -260,6 +261,136 @@ def test_stop_rules_with_a_wall(wtp):
             assert np.allclose(conv, conv0, rtol=1e-5)
         assert np.abs(p - p0).max() / s <= 2e-5
     assert why0 == "cv_target" and len(conv0) == i + 2
+
+
+def _stall_walk(cvs, stall_after):
+    """The stall rule (src/repel.jl:318-329) restated on a list of CVs: (the sweep, from 1, at which it fires or None,
+    the improvements it saw before, the smallest |cv / (best (1 - 1e-3)) - 1| it met)."""
+    best, last_impr, n_impr, margin = np.inf, 0, 0, np.inf
+    for i, cv in enumerate(cvs, 1):
+        margin = min(margin, abs(cv / (best * (1 - 1e-3)) - 1.0))
+        if cv < best * (1 - 1e-3):
+            best, last_impr, n_impr = cv, i, n_impr + 1
+        elif i - last_impr >= stall_after:
+            return i, n_impr, margin
+    return None, n_impr, margin
+
+
+_STOP_SWEEPS = 40
+_STALL_AFTER = 2
+
+
+def _plain_steps(wtp, x, s, alpha):
+    with wtp.Context(0) as c, c.relax(x, 0, s, FORCE, K, alpha / 100, alpha) as sess:
+        return [sess.step(True) for _ in range(_STOP_SWEEPS)]
+
+
+def _stalling_step_limit(wtp, x, s):
+    """A step limit at which the plain session's own trajectory improves several times and then stalls before sweep 40.
+
+    This selects the INPUT, from the plain session's sweeps alone.  At the file's usual limit (s / 20), and at every
+    limit from s down to s / 200, the CV of a uniform cloud of these sizes still falls by about 1 % per sweep at sweep
+    40, ten times the 0.1 % the stall rule asks for: the rule cannot fire within 40 sweeps.  Below s / 400 the gain per
+    sweep is proportional to the limit and decays slowly (0.147 % per sweep at s / 1200 for 30 000 points).  Where it
+    starts just above 0.05 %, every second sweep is an improvement until the gain of two sweeps drops below 0.1 %:
+    then two sweeps in a row bring none and stall_after = 2 fires.  Larger limits never stall, smaller ones stall at
+    sweep 3 after the one improvement from +inf, so the limit is bisected for a stall between sweeps 12 and 36."""
+    lo, hi = 1500.0, 6000.0
+    for _ in range(14):
+        div = 0.5 * (lo + hi)
+        ref = _plain_steps(wtp, x, s, s / div)
+        at, n_impr, margin = _stall_walk([_cv(st) for st in ref], _STALL_AFTER)
+        if at is None or at > 36:
+            lo = div
+        elif at < 12:
+            hi = div
+        elif margin < 1e-7:  # too close to the threshold for a fair input (see _assert_clear_of_the_stall_threshold)
+            hi = div * (1 - 1e-4)
+        else:
+            assert n_impr >= 4, (div, at, n_impr)
+            return s / div, ref
+    raise AssertionError(f"no step limit between s / {hi:.0f} and s / {lo:.0f} stalls between sweeps 12 and 36: choose another input")
+
+
+def _assert_clear_of_the_stall_threshold(cvs):
+    """Guards the INPUT, not the code: sum_u / sum_u2 are reproducible only to their last bits from run to run, so a
+    trajectory is a fair one for the stall rule only if no sweep's CV sits within 1e-9 (relative) of the improvement
+    threshold best * (1 - 1e-3), where a last-bit difference could flip the rule's verdict."""
+    at, _, margin = _stall_walk(cvs, _STOP_SWEEPS + 1)  # (never fires: the whole list is walked)
+    assert at is None and margin > 1e-9, margin
+
+
+@pytest.fixture(scope="module")
+def one_rank_trajectory(wtp):
+    """30 000 uniform points, no wall: (x, s, step limit, per-sweep conv, per-sweep cv) of 40 plain-session sweeps."""
+    n = 30_000
+    x = wtp.synth.uniform(n, 3, np.float32)
+    s = float(n) ** (-1.0 / 3.0)
+    alpha, ref = _stalling_step_limit(wtp, x, s)
+    return x, s, alpha, [st["max_force"] for st in ref], [_cv(st) for st in ref]
+
+
+def _plain_and_one_rank_block(wtp, x, s, alpha, tol, stall_after):
+    """The same run_until on the plain session and on a one-rank block session (which IS the plain session)."""
+    from whatsthepoint_jl_amd import blockc
+
+    with wtp.Context(0) as c, c.relax(x, 0, s, FORCE, K, alpha / 100, alpha) as sess:
+        conv0, why0, _ = sess.run_until(_STOP_SWEEPS, 1, tol, stall_after, 0.0)
+    boxes = blockc.orthtree_boxes(None, 1, equal_count=False)
+    with wtp.Context(0) as ctx:
+        drv = blockc.BlockRelax(ctx, 0, 1, boxes, x, None, 2.0 * s, s, FORCE, K, alpha / 100, alpha)
+        conv, why, _ = drv.run_until(_STOP_SWEEPS, tol, stall_after, 0.0)
+        drv.close()
+    return np.asarray(conv0), ("max_iters", "tol", "cv_target", "stall")[why0], np.asarray(conv), why
+
+
+def test_block_run_until_tol_exit_is_the_plain_sessions(wtp, one_rank_trajectory):
+    x, s, alpha, conv_ref, _ = one_rank_trajectory
+    # a tolerance crossed between two consecutive sweeps after the fifth, with room on both sides
+    j = next(j for j in range(5, _STOP_SWEEPS - 1) if conv_ref[j + 1] < conv_ref[j] == min(conv_ref[: j + 1]))
+    tol = float(np.sqrt(conv_ref[j] * conv_ref[j + 1]))
+    conv0, why0, conv, why = _plain_and_one_rank_block(wtp, x, s, alpha, tol, 0)
+    print(f"tol exit: tol = {tol:.6e} between sweeps {j + 1} and {j + 2}; plain {why0} after {len(conv0)}, block {why} after {len(conv)}")
+    assert why0 == "tol" and why == "tol", (why0, why)
+    assert len(conv0) == len(conv) == j + 2, (len(conv0), len(conv), j + 2)
+    assert np.array_equal(conv0, conv), "a one-rank block session is the plain session bit for bit in max |F|"
+
+
+def test_block_run_until_stall_exit_is_the_plain_sessions(wtp, one_rank_trajectory):
+    x, s, alpha, _, cvs = one_rank_trajectory
+    _assert_clear_of_the_stall_threshold(cvs)
+    at, n_impr, margin = _stall_walk(cvs, _STALL_AFTER)
+    conv0, why0, conv, why = _plain_and_one_rank_block(wtp, x, s, alpha, 0.0, _STALL_AFTER)
+    print(f"stall exit: step limit s / {s / alpha:.1f}, restated rule fires at sweep {at} after {n_impr} improvements "
+          f"(margin {margin:.2e}); plain {why0} after {len(conv0)}, block {why} after {len(conv)}")
+    assert why0 == "stall" and why == "stall", (why0, why)
+    assert len(conv0) == len(conv) == at, (len(conv0), len(conv), at)
+    assert np.array_equal(conv0, conv), "a one-rank block session is the plain session bit for bit in max |F|"
+
+
+def test_block_run_until_stall_exit_on_four_ranks(wtp):
+    """2 x 2 ranks as threads over the loopback transport: every rank stops at the sweep the restated rule names on the
+    four-rank run's own (gathered, rank-ordered) CVs."""
+    from whatsthepoint_jl_amd import blockc
+
+    n = 60_000
+    x = wtp.synth.uniform(n, 3, np.float32)
+    s = float(n) ** (-1.0 / 3.0)
+    alpha, ref = _stalling_step_limit(wtp, x, s)
+    boxes = blockc.orthtree_boxes(None, 4, equal_count=False)
+    _, hists = _run_blocks(wtp, x, boxes, s, _STOP_SWEEPS, alpha, w=2.2 * s, margin=0.1 * s, wall=None)
+    _same_on_every_rank(hists)
+    cvs = [_cv(st) for st in hists[0]]
+    _assert_clear_of_the_stall_threshold(cvs)
+    at, n_impr, margin = _stall_walk(cvs, _STALL_AFTER)
+    assert at is not None and at < _STOP_SWEEPS and n_impr >= 4, ("the four-rank trajectory does not stall: choose another input", at, n_impr)
+    _, res = _run_blocks(wtp, x, boxes, s, 0, alpha, w=2.2 * s, margin=0.1 * s, wall=None,
+                         body=lambda drv: drv.run_until(_STOP_SWEEPS, 0.0, _STALL_AFTER, 0.0))
+    print(f"four ranks: step limit s / {s / alpha:.1f}, restated rule fires at sweep {at} after {n_impr} improvements "
+          f"(margin {margin:.2e}); ranks stop {[(why, len(conv)) for conv, why, _ in res]}")
+    for conv, why, _ in res:
+        assert why == "stall" and len(conv) == at, (why, len(conv), at)
+        assert np.allclose(conv, [st["max_force"] for st in ref[:at]], rtol=1e-5)
 
 
 def test_set_wall_arguments_and_state(wtp):

@@ -21,6 +21,9 @@
 //      synchronisation; every rank reduces the statistics in rank order (fixed order: reproducible sums).
 //   7. if any rank counted a query whose support reaches past its covered box: undo, widen, repeat.
 //
+// How the rows and the gathered words travel (the context's RCCL communicator or the caller's host callbacks, and the
+// overlap of step 1 with the first half of step 4) is the context's Transport: wtp_comm.hip.
+//
 // Order of the rows a peer receives = slot order of the sender's sorted state = a pure function of the sender's
 // points, so the ghost ids on the receiving side (and with them every sum) do not depend on scheduling.
 //
@@ -64,17 +67,13 @@ struct BlockState {
     BlkGeom geom{};
     int widened = 0;
     // device
-    DevBuf flags, span_counts, totals, send, send_mig, gid[2], pool, recv_mig, gsend, grecv, lost;
+    DevBuf flags, span_counts, totals, send, send_mig, gid[2], pool, recv_mig, gsend, lost;
     int gid_cur = 0;
     int64_t n_owned = 0, n_ghost = 0;
     int64_t send_cap = 0, mig_cap = 0;
     // the plan of the next exchange (host): rows to / from each peer
     bool plan_ready = false;
     std::vector<int64_t> send_cnt, mig_cnt, recv_cnt, rmig_cnt;
-    // transport
-    bool host_transport = false;
-    wtp_transport tr{};
-    std::vector<unsigned char> hbuf_a, hbuf_b;
     // the boundary wall (wtp_block_set_wall): all of it on the host, the part inside the coverage box as 16-byte rows
     // {x, y, z, bits(wall index)} in ascending wall index on both sides; the rows lead the fixed head
     std::vector<float> wall;             // n_wall x 3
@@ -85,7 +84,6 @@ struct BlockState {
     bool pool_wall_ok = false;           // the pool's prefix holds the current selection (false after any regrowth)
     // last info
     wtp_block_info info{};
-    // stop rules (wtp_block_run_until)
 };
 
 static BlockState* bs_of(wtp_ctx* ctx) { return (BlockState*)ctx->block; }
@@ -365,14 +363,6 @@ __global__ void blk_gather_gid_kernel(const float4* __restrict__ P, int64_t n, i
 
 // ---- host side --------------------------------------------------------------------------------------------------------
 
-static int blk_sync(wtp_ctx* ctx, BlockState* b) {
-    ctx->timers.ev_last_end = -1;
-    WTP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->n_syncs += 1;
-    (void)b;
-    return WTP_OK;
-}
-
 static bool boxes_near(const double* a, const double* c, double reach) {
     for (int ax = 0; ax < 3; ++ax)
         if (a[ax] - reach >= c[3 + ax] || c[ax] - reach >= a[3 + ax]) return false;
@@ -413,7 +403,7 @@ static int blk_select_wall(wtp_ctx* ctx, BlockState* b, const double lo[3], cons
         return WTP_OK;
     // (the previous rows may still be the source of a copy in flight: the stream drains before they are replaced)
     int rc;
-    if ((rc = blk_sync(ctx, b))) return rc;
+    if ((rc = sync(ctx))) return rc;
     b->wall_sel.swap(sel);
     b->n_sel = (int64_t)(b->wall_sel.size() / 4);
     b->wall_dirty = true;
@@ -507,7 +497,6 @@ static int blk_classify(wtp_ctx* ctx, BlockState* b, const wtp_step_stats* d_sta
     }
     const size_t gwords = (size_t)kBlkStatWords + 2 * (size_t)b->nranks + 2;
     if ((rc = ensure(ctx, b->gsend, 8 * gwords))) return rc;
-    if ((rc = ensure(ctx, b->grecv, 8 * gwords * (size_t)b->nranks))) return rc;
     const float4* P = (const float4*)ctx->pts[r.bufP].p;
     int32_t* totals = (int32_t*)b->totals.p;
     int* d_peer_rank = (int*)(totals + ncol + 4);
@@ -534,24 +523,10 @@ static int blk_classify(wtp_ctx* ctx, BlockState* b, const wtp_step_stats* d_sta
 // statistics in *g (if d_stats was given to blk_classify) and whether a send buffer overflowed anywhere.
 static int blk_gather(wtp_ctx* ctx, BlockState* b, wtp_step_stats* g, bool* overflow, int64_t* lost_total) {
     const size_t gwords = (size_t)kBlkStatWords + 2 * (size_t)b->nranks + 2;
-    const size_t bytes = 8 * gwords;
     int rc;
-    if ((rc = ensure_pinned(ctx, bytes * (size_t)b->nranks + 64))) return rc;
+    if ((rc = ensure_pinned(ctx, 8 * gwords * (size_t)b->nranks + 64))) return rc;
     int64_t* h = (int64_t*)ctx->host_pinned;
-    if (b->host_transport) {
-        b->hbuf_a.resize(bytes);
-        WTP_HIP(ctx, hipMemcpyAsync(b->hbuf_a.data(), b->gsend.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        if ((rc = blk_sync(ctx, b))) return rc;
-        if (b->tr.allgather(b->tr.user, b->hbuf_a.data(), h, (int64_t)bytes) != 0)
-            return fail(ctx, WTP_ERR_STATE, "wtp_block: the caller's allgather callback failed");
-    } else if (b->nranks == 1) {
-        WTP_HIP(ctx, hipMemcpyAsync(h, b->gsend.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        if ((rc = blk_sync(ctx, b))) return rc;
-    } else {
-        if ((rc = wtp_comm_allgather_dev(ctx, b->gsend.p, b->grecv.p, (int64_t)bytes))) return rc;
-        WTP_HIP(ctx, hipMemcpyAsync(h, b->grecv.p, bytes * (size_t)b->nranks, hipMemcpyDeviceToHost, ctx->stream));
-        if ((rc = blk_sync(ctx, b))) return rc;
-    }
+    if ((rc = transport_allgather(ctx, b->nranks, b->gsend.p, true, h, (int64_t)gwords, "wtp_block"))) return rc;
     // the plan: what I send (my own row) and what every peer sends me
     const int np = b->geom.np;
     const int64_t* mine = h + (size_t)b->rank * gwords;
@@ -635,11 +610,6 @@ static int blk_plan(wtp_ctx* ctx, BlockState* b, const wtp_step_stats* d_stats, 
 // ---- what the sharded topology (wtp_block_topo.hip) takes from the driver -------------------------------------------
 bool block_session_open(wtp_ctx* ctx) { return bs_of(ctx) && bs_of(ctx)->active; }
 
-const wtp_transport* block_host_transport(wtp_ctx* ctx) {
-    BlockState* b = bs_of(ctx);
-    return b && b->host_transport ? &b->tr : nullptr;
-}
-
 int launch_blk_scan(wtp_ctx* ctx, int32_t* span_counts, int64_t nspans, int ncol, int32_t* totals) {
     hipLaunchKernelGGL(blk_scan_kernel, dim3(ncol), dim3(256), 0, ctx->stream, span_counts, nspans, ncol, totals);
     WTP_HIP(ctx, hipGetLastError());
@@ -692,21 +662,6 @@ WTP_API int wtp_block_morton_rank(int ix, int iy, int iz, const int p[3]) {
     return out;
 }
 
-WTP_API int wtp_block_set_transport(wtp_ctx* ctx, const wtp_transport* t) {
-    if (!ctx) return WTP_ERR_ARG;
-    if (!ctx->block) ctx->block = new BlockState();
-    BlockState* b = bs_of(ctx);
-    if (b->active) return fail(ctx, WTP_ERR_STATE, "wtp_block_set_transport while a block session is open");
-    if (t) {
-        if (!t->allgather || !t->exchange) return fail(ctx, WTP_ERR_ARG, "wtp_block_set_transport: both callbacks are needed");
-        b->tr = *t;
-        b->host_transport = true;
-    } else {
-        b->host_transport = false;
-    }
-    return WTP_OK;
-}
-
 WTP_API int wtp_block_set_wall(wtp_ctx* ctx, const void* d_wall_xyz, int64_t n_wall) {
     if (!ctx) return WTP_ERR_ARG;
     if (n_wall < 0 || (n_wall > 0 && !d_wall_xyz)) return fail(ctx, WTP_ERR_ARG, "wtp_block_set_wall: n_wall >= 0, and an array when n_wall > 0");
@@ -748,8 +703,7 @@ WTP_API int wtp_block_open(wtp_ctx* ctx, const wtp_block_desc* desc, const void*
     if (!ctx->block) ctx->block = new BlockState();
     BlockState* b = bs_of(ctx);
     if (b->active) return fail(ctx, WTP_ERR_STATE, "wtp_block_open: a block session is open already");
-    if (!b->host_transport && desc->nranks > 1 && (!ctx->comm || ctx->comm_size != desc->nranks || ctx->comm_rank != desc->rank))
-        return fail(ctx, WTP_ERR_STATE, "wtp_block_open: wtp_comm_init (same rank / nranks) or wtp_block_set_transport first");
+    if (int rc = transport_ready(ctx, desc->rank, desc->nranks, "wtp_block_open: ")) return rc;
     for (int r = 0; r < desc->nranks; ++r)
         for (int ax = 0; ax < 3; ++ax)
             if (!(desc->boxes[(size_t)r * 6 + ax] < desc->boxes[(size_t)r * 6 + 3 + ax]))
@@ -802,14 +756,6 @@ WTP_API int wtp_block_open(wtp_ctx* ctx, const wtp_block_desc* desc, const void*
     return WTP_OK;
 }
 
-// second stream and the two events that tie it to the first (created on first use)
-static int blk_streams(wtp_ctx* ctx) {
-    if (!ctx->comm_stream) WTP_HIP(ctx, hipStreamCreateWithFlags(&ctx->comm_stream, hipStreamNonBlocking));
-    if (!ctx->ev_comm_a) WTP_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_comm_a, hipEventDisableTiming));
-    if (!ctx->ev_comm_b) WTP_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_comm_b, hipEventDisableTiming));
-    return WTP_OK;
-}
-
 // the exchange the plan describes: ghost rows into the pool, migrants into recv_mig; then the owned set and the ghosts
 static int blk_exchange_and_apply(wtp_ctx* ctx, BlockState* b) {
     RelaxState& r = ctx->relax;
@@ -859,59 +805,16 @@ static int blk_exchange_and_apply(wtp_ctx* ctx, BlockState* b) {
         ro += b->recv_cnt[q];
         rmo += b->rmig_cnt[q];
     }
-    if (np > 0) {
-        if (b->host_transport) {
-            // stage through the host: rows out, callback, rows in
-            const size_t out_bytes = 16 * (size_t)n_send + 32 * (size_t)n_mig, in_bytes = 16 * (size_t)n_recv + 32 * (size_t)n_rmig;
-            b->hbuf_a.resize(out_bytes + 16);
-            b->hbuf_b.resize(in_bytes + 16);
-            unsigned char* ha = b->hbuf_a.data();
-            unsigned char* hb = b->hbuf_b.data();
-            if (n_send) WTP_HIP(ctx, hipMemcpyAsync(ha, b->send.p, 16 * (size_t)n_send, hipMemcpyDeviceToHost, ctx->stream));
-            if (n_mig) WTP_HIP(ctx, hipMemcpyAsync(ha + 16 * (size_t)n_send, b->send_mig.p, 32 * (size_t)n_mig, hipMemcpyDeviceToHost, ctx->stream));
-            if (early) {
-                // the host waits for the rows only; the stream goes on ranking the owned points under the callback
-                if ((rc = blk_streams(ctx))) return rc;
-                WTP_HIP(ctx, hipEventRecord(ctx->ev_comm_a, ctx->stream));
-                if ((rc = relax_prerank(ctx, n_sel + n_pool))) return rc;
-                ctx->timers.ev_last_end = -1;
-                WTP_HIP(ctx, hipEventSynchronize(ctx->ev_comm_a));
-                ctx->n_syncs += 1;
-            } else if ((rc = blk_sync(ctx, b)))
-                return rc;
-            std::vector<const void*> hs(sp.size());
-            std::vector<void*> hr(rp.size());
-            std::vector<int64_t> sb(sp.size()), rb(rp.size());
-            for (size_t j = 0; j < sp.size(); ++j) {
-                const bool mig = j & 1;
-                hs[j] = mig ? ha + 16 * (size_t)n_send + ((const char*)sp[j] - (const char*)b->send_mig.p)
-                            : ha + ((const char*)sp[j] - (const char*)b->send.p);
-                hr[j] = mig ? hb + 16 * (size_t)n_recv + ((char*)rp[j] - (char*)b->recv_mig.p) : hb + ((char*)rp[j] - ghost_base);
-                sb[j] = 16 * sn[j];
-                rb[j] = 16 * rn[j];
-            }
-            if (b->tr.exchange(b->tr.user, (int)peers.size(), peers.data(), hs.data(), sb.data(), hr.data(), rb.data()) != 0)
-                return fail(ctx, WTP_ERR_STATE, "wtp_block: the caller's exchange callback failed");
-            if (n_recv) WTP_HIP(ctx, hipMemcpyAsync(ghost_base, hb, 16 * (size_t)n_recv, hipMemcpyHostToDevice, ctx->stream));
-            if (n_rmig) WTP_HIP(ctx, hipMemcpyAsync(b->recv_mig.p, hb + 16 * (size_t)n_recv, 32 * (size_t)n_rmig, hipMemcpyHostToDevice, ctx->stream));
-            if ((rc = blk_sync(ctx, b))) return rc; // (the host buffers are reused)
-        } else if (early) {
-            // Exchange and compute overlap: the grouped round runs on the context's second stream, every peer on
-            // its own link; the first stream ranks the owned points into the cells meanwhile (the first pass of the rebuild,
-            // which does not need the ghosts) and waits for the rows only before it appends them.
-            if ((rc = blk_streams(ctx))) return rc;
-            WTP_HIP(ctx, hipEventRecord(ctx->ev_comm_a, ctx->stream)); // (send rows and the pool's last readers are in stream order before it)
-            WTP_HIP(ctx, hipStreamWaitEvent(ctx->comm_stream, ctx->ev_comm_a, 0));
-            if ((rc = comm_exchange_peers_on(ctx, ctx->comm_stream, (int)peers.size(), peers.data(), sp.data(), sn.data(), rp.data(),
-                                             rn.data())))
-                return rc;
-            WTP_HIP(ctx, hipEventRecord(ctx->ev_comm_b, ctx->comm_stream));
-            rc = relax_prerank(ctx, n_sel + n_pool);
-            WTP_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_comm_b, 0)); // (also when the ranking failed: the streams join again)
-            if (rc) return rc;
-        } else {
-            if ((rc = wtp_comm_exchange_peers(ctx, (int)peers.size(), peers.data(), sp.data(), sn.data(), rp.data(), rn.data()))) return rc;
-        }
+    if (np > 0) { // (a rank without neighbours posts no round)
+        const RowRegion out[2] = {{b->send.p, n_send}, {b->send_mig.p, 2 * n_mig}};
+        const RowRegion in[2] = {{ghost_base, n_recv}, {b->recv_mig.p, 2 * n_rmig}};
+        // while the rows travel, the stream ranks the owned points into the cells (the first pass of the rebuild, which
+        // does not need the ghosts)
+        int64_t n_head = n_sel + n_pool;
+        auto prerank = [](wtp_ctx* c, void* n_fixed_new) { return relax_prerank(c, *(const int64_t*)n_fixed_new); };
+        if ((rc = transport_exchange(ctx, (int)peers.size(), peers.data(), sp.data(), sn.data(), rp.data(), rn.data(), 2, out, in,
+                                     early ? +prerank : nullptr, &n_head, "wtp_block")))
+            return rc;
     }
     // my emigrants: ghosts for this iteration
     if (n_mig)
@@ -1013,8 +916,8 @@ WTP_API int wtp_block_run(wtp_ctx* ctx, int n_iters, double* conv_out, wtp_step_
     return WTP_OK;
 }
 
-// The stop rules of `_relax!` (src/repel.jl:305-334) on the global statistics, in the reference's order: cv_target
-// (positions reverted), stall_after on the CV of d_NN / s, tol on max |F| s.  Every rank evaluates the same numbers.
+// The stop rules of `_relax!` (src/repel.jl:305-334; stop_rules_apply, wtp_internal.hpp) on the global statistics, with
+// the positions reverted on cv_target.  Every rank evaluates the same numbers.
 WTP_API int wtp_block_run_until(wtp_ctx* ctx, int max_iters, double tol, int stall_after, double cv_target, double* conv_out,
                                 int* n_done, int* reason, wtp_step_stats* last) {
     if (!ctx) return WTP_ERR_ARG;
@@ -1022,43 +925,21 @@ WTP_API int wtp_block_run_until(wtp_ctx* ctx, int max_iters, double tol, int sta
     BlockState* b = bs_of(ctx);
     if (!b || !b->active) return fail(ctx, WTP_ERR_STATE, "wtp_block_run_until before wtp_block_open");
     wtp_step_stats st{};
-    int done = 0, why = 0, last_impr = 0;
-    double best = std::numeric_limits<double>::infinity();
-    for (int i = 1; i <= max_iters; ++i) {
+    StopState ss{};
+    ss.best_cv = std::numeric_limits<double>::infinity();
+    for (int i = 1; i <= max_iters && !ss.stopped; ++i) {
         int rc = wtp_block_step(ctx, &st, nullptr);
         if (rc) return rc;
-        done = i;
         if (conv_out) conv_out[i - 1] = st.max_force;
-        const double nm = (double)st.n_move;
-        if ((cv_target > 0 || stall_after > 0) && st.n_move > 0) {
-            const double mu = st.sum_u / nm;
-            double var = st.sum_u2 / nm - mu * mu;
-            var = var > 0 ? var : 0;
-            const double cv = std::sqrt(var) / mu;
-            if (cv_target > 0 && cv <= cv_target) {
-                // p .= p_old (src/repel.jl:314): the sweep is undone; the plan made from its positions is void
-                if ((rc = wtp_relax_revert(ctx))) return rc;
-                b->plan_ready = false;
-                why = 2;
-                break;
-            }
-            if (stall_after > 0) {
-                if (cv < best * (1.0 - 1.0e-3)) {
-                    best = cv;
-                    last_impr = i;
-                } else if (i - last_impr >= stall_after) {
-                    why = 3;
-                    break;
-                }
-            }
-        }
-        if (st.max_force < tol) {
-            why = 1;
-            break;
+        stop_rules_apply(ss, st, i, tol, stall_after, cv_target);
+        if (ss.reason == 2) {
+            // p .= p_old (src/repel.jl:314): the sweep is undone; the plan made from its positions is void
+            if ((rc = wtp_relax_revert(ctx))) return rc;
+            b->plan_ready = false;
         }
     }
-    if (n_done) *n_done = done;
-    if (reason) *reason = why;
+    if (n_done) *n_done = ss.n_done;
+    if (reason) *reason = ss.reason;
     if (last) *last = st;
     return WTP_OK;
 }

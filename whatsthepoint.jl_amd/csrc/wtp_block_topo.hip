@@ -1,7 +1,8 @@
 // wtp_block_topo.hip — sharded set_topology: KNN and radius rows of a cloud that stays split across ranks
 // (include/wtp.h: wtp_block_knn, wtp_block_radius_*).
 //
-// Same decomposition as the block driver (wtp_block.hip), no iteration.  Per call and rank:
+// Same decomposition as the block driver (wtp_block.hip) and the same Transport (wtp_comm.hip), no iteration.  Per call
+// and rank:
 //
 //   1. one all-gather of a header {status, owned count, bounding box of the owned points, gid range and fingerprint,
 //      arguments}; every check that needs global knowledge runs on the gathered words, so every rank returns the same
@@ -71,8 +72,7 @@ __host__ __device__ inline unsigned long long tp_mix(unsigned long long z) {
 
 struct TopoState {
     DevBuf own4, recv, send, span_counts, totals, stats, bm, pc, off, scan_tmp;
-    DevBuf lxyz, lgid, opos, lidx, ldist, gbuf, lcnt, loff, ridx, cnt_own, own_off;
-    std::vector<unsigned char> hbuf_a, hbuf_b;
+    DevBuf lxyz, lgid, opos, lidx, ldist, lcnt, loff, ridx, cnt_own, own_off;
     bool rad_ready = false; // a wtp_block_radius_offsets call left its rows here for wtp_block_radius_fill
     int64_t rad_n_owned = 0, rad_nnz = 0;
 };
@@ -292,84 +292,6 @@ __global__ __launch_bounds__(256) void tp_radius_fill_kernel(int64_t n_own, cons
 
 // ---- host side --------------------------------------------------------------------------------------------------------
 
-static int tp_sync(wtp_ctx* ctx) {
-    ctx->timers.ev_last_end = -1;
-    WTP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->n_syncs += 1;
-    return WTP_OK;
-}
-
-struct TpComm {
-    wtp_ctx* ctx;
-    TopoState* s;
-    int rank, nranks;
-    const wtp_transport* tr; // NULL: the context's RCCL communicator
-};
-
-// every rank's `nwords` words into all[nranks * nwords], rank-major
-static int tp_allgather(TpComm& c, const int64_t* mine, int64_t* all, int nwords) {
-    wtp_ctx* ctx = c.ctx;
-    const size_t bytes = 8 * (size_t)nwords;
-    if (c.nranks == 1) {
-        memcpy(all, mine, bytes);
-        return WTP_OK;
-    }
-    if (c.tr) {
-        if (c.tr->allgather(c.tr->user, mine, all, (int64_t)bytes) != 0)
-            return fail(ctx, WTP_ERR_STATE, "wtp_block topology: the caller's allgather callback failed");
-        return WTP_OK;
-    }
-    int rc;
-    if ((rc = ensure(ctx, c.s->gbuf, bytes * (size_t)(c.nranks + 1)))) return rc;
-    char* d = (char*)c.s->gbuf.p;
-    WTP_HIP(ctx, hipMemcpyAsync(d, mine, bytes, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = wtp_comm_allgather_dev(ctx, d, d + bytes, (int64_t)bytes))) return rc;
-    WTP_HIP(ctx, hipMemcpyAsync(all, d + bytes, bytes * (size_t)c.nranks, hipMemcpyDeviceToHost, ctx->stream));
-    return tp_sync(ctx);
-}
-
-// one grouped round: rows to / from every peer (ascending rank), counts agreed on beforehand
-static int tp_exchange(TpComm& c, const std::vector<int>& peers, const std::vector<int64_t>& sn, const std::vector<int64_t>& rn,
-                       const float4* send, float4* recv) {
-    wtp_ctx* ctx = c.ctx;
-    // (a caller's transport is a collective of all ranks: it is called by every rank of a round, with or without peers)
-    if (c.nranks == 1 || (peers.empty() && !c.tr)) return WTP_OK;
-    const size_t np = peers.size();
-    std::vector<const void*> sp(np);
-    std::vector<void*> rp(np);
-    int64_t so = 0, ro = 0;
-    for (size_t j = 0; j < np; ++j) {
-        sp[j] = send + so;
-        rp[j] = recv + ro;
-        so += sn[j];
-        ro += rn[j];
-    }
-    if (!c.tr) return wtp_comm_exchange_peers(ctx, (int)np, peers.data(), sp.data(), sn.data(), rp.data(), rn.data());
-    // host transport: rows out, callback, rows in
-    TopoState* s = c.s;
-    s->hbuf_a.resize(16 * (size_t)so + 16);
-    s->hbuf_b.resize(16 * (size_t)ro + 16);
-    int rc;
-    if (so) {
-        WTP_HIP(ctx, hipMemcpyAsync(s->hbuf_a.data(), send, 16 * (size_t)so, hipMemcpyDeviceToHost, ctx->stream));
-        if ((rc = tp_sync(ctx))) return rc;
-    }
-    std::vector<const void*> hs(np);
-    std::vector<void*> hr(np);
-    std::vector<int64_t> sb(np), rb(np);
-    for (size_t j = 0; j < np; ++j) {
-        hs[j] = s->hbuf_a.data() + ((const char*)sp[j] - (const char*)send);
-        hr[j] = s->hbuf_b.data() + ((char*)rp[j] - (char*)recv);
-        sb[j] = 16 * sn[j];
-        rb[j] = 16 * rn[j];
-    }
-    if (c.tr->exchange(c.tr->user, (int)np, peers.data(), hs.data(), sb.data(), hr.data(), rb.data()) != 0)
-        return fail(ctx, WTP_ERR_STATE, "wtp_block topology: the caller's exchange callback failed");
-    if (!ro) return WTP_OK;
-    WTP_HIP(ctx, hipMemcpyAsync(recv, s->hbuf_b.data(), 16 * (size_t)ro, hipMemcpyHostToDevice, ctx->stream));
-    return tp_sync(ctx); // (the host buffers are reused)
-}
-
 struct TpCall {
     int rank, nranks;
     const float* xyz;
@@ -413,13 +335,14 @@ static int tp_run(wtp_ctx* ctx, const TpCall& c, wtp_block_topo_info* info) {
     const bool knn = c.k != 0;
     const char* who = knn ? "wtp_block_knn: " : "wtp_block_radius_offsets: ";
     if (c.nranks < 1 || c.rank < 0 || c.rank >= c.nranks) return fail(ctx, WTP_ERR_ARG, std::string(who) + "0 <= rank < nranks");
-    const wtp_transport* tr = block_host_transport(ctx);
-    if (!tr && c.nranks > 1 && (!ctx->comm || ctx->comm_size != c.nranks || ctx->comm_rank != c.rank))
-        return fail(ctx, WTP_ERR_STATE, std::string(who) + "wtp_comm_init (same rank / nranks) or wtp_block_set_transport first");
+    if (int rcr = transport_ready(ctx, c.rank, c.nranks, who)) return rcr;
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     TopoState* s = ts_of(ctx);
     s->rad_ready = false;
-    TpComm cm{ctx, s, c.rank, c.nranks, tr};
+    // every rank's words into all[nranks * nwords], rank-major
+    auto allgather = [&](const int64_t* mine, int64_t* all, int nwords) {
+        return transport_allgather(ctx, c.nranks, mine, false, all, nwords, "wtp_block topology");
+    };
     const int64_t syncs0 = ctx->n_syncs;
     const int R = c.nranks, me = c.rank;
     const int64_t n = c.n;
@@ -443,7 +366,7 @@ static int tp_run(wtp_ctx* ctx, const TpCall& c, wtp_block_topo_info* info) {
                            (float4*)s->own4.p, (TpStats*)s->stats.p);
         WTP_HIP(ctx, hipGetLastError());
         WTP_HIP(ctx, hipMemcpyAsync(&hs, s->stats.p, sizeof(TpStats), hipMemcpyDeviceToHost, ctx->stream));
-        if ((rc = tp_sync(ctx))) return rc;
+        if ((rc = sync(ctx))) return rc;
     }
     int64_t hdr[kTpHdr] = {status, reason, status ? 0 : n, (int64_t)hs.gmax, (int64_t)hs.fp, c.k, c.include_self ? 1 : 0,
                            hdr_w(c.r), hdr_w(c.width)};
@@ -452,7 +375,7 @@ static int tp_run(wtp_ctx* ctx, const TpCall& c, wtp_block_topo_info* info) {
         hdr[12 + a] = hdr_w((double)tp_unkey(hs.key_hi[a]));
     }
     std::vector<int64_t> all((size_t)R * kTpHdr);
-    if ((rc = tp_allgather(cm, hdr, all.data(), kTpHdr))) return rc;
+    if ((rc = allgather(hdr, all.data(), kTpHdr))) return rc;
     auto H = [&](int q, int w) { return all[(size_t)q * kTpHdr + w]; };
 
     // ---- global checks on the gathered words: the same verdict on every rank ----
@@ -489,14 +412,14 @@ static int tp_run(wtp_ctx* ctx, const TpCall& c, wtp_block_topo_info* info) {
         WTP_HIP(ctx, hipGetLastError());
         unsigned long long want = 0;
         WTP_HIP(ctx, hipMemcpyAsync(&want, d_fp, 8, hipMemcpyDeviceToHost, ctx->stream));
-        if ((rc = tp_sync(ctx))) return rc;
+        if ((rc = sync(ctx))) return rc;
         if (want != fp)
             return fail(ctx, WTP_ERR_ARG, std::string(who) + "a gid is owned by more than one rank (the gids must be 0 .. N_total - 1, each once)");
     }
     if (N == 0) {
         if (!knn && c.off_out) WTP_HIP(ctx, hipMemsetAsync(c.off_out, 0, 8, ctx->stream));
         if (info) *info = wtp_block_topo_info{};
-        return tp_sync(ctx);
+        return sync(ctx);
     }
 
     // ---- boxes and widths (identical on every rank) ----
@@ -577,7 +500,7 @@ static int tp_run(wtp_ctx* ctx, const TpCall& c, wtp_block_topo_info* info) {
             if ((rc = launch_blk_scan(ctx, (int32_t*)s->span_counts.p, nsp, geo.nd, (int32_t*)s->totals.p))) return rc;
             int32_t tot[kTpMaxDest];
             WTP_HIP(ctx, hipMemcpyAsync(tot, s->totals.p, sizeof(int32_t) * geo.nd, hipMemcpyDeviceToHost, ctx->stream));
-            if ((rc = tp_sync(ctx))) return rc;
+            if ((rc = sync(ctx))) return rc;
             for (int d = 0; d < geo.nd; ++d) {
                 send_to[dest[d]] = tot[d];
                 n_send += tot[d];
@@ -591,7 +514,7 @@ static int tp_run(wtp_ctx* ctx, const TpCall& c, wtp_block_topo_info* info) {
         }
         span_end(ctx, sp);
         // row counts of every rank to every rank, then one grouped exchange with exact sizes
-        if ((rc = tp_allgather(cm, send_to.data(), cnt_all.data(), R))) return rc;
+        if ((rc = allgather(send_to.data(), cnt_all.data(), R))) return rc;
         std::vector<int> peers;
         std::vector<int64_t> sn, rn;
         n_recv = 0;
@@ -608,7 +531,23 @@ static int tp_run(wtp_ctx* ctx, const TpCall& c, wtp_block_topo_info* info) {
             n_from += in > 0;
         }
         if ((rc = ensure(ctx, s->recv, 16 * (size_t)n_recv))) return rc;
-        if ((rc = tp_exchange(cm, peers, sn, rn, (const float4*)s->send.p, (float4*)s->recv.p))) return rc;
+        // one grouped round: rows to / from every peer (ascending rank), counts agreed on beforehand
+        // (a caller's transport is a collective of all ranks: it is called by every rank of a round, with or without peers)
+        if (R > 1 && (!peers.empty() || ctx->transport.host)) {
+            std::vector<const void*> sp(peers.size());
+            std::vector<void*> rp(peers.size());
+            int64_t so = 0, ro = 0;
+            for (size_t j = 0; j < peers.size(); ++j) {
+                sp[j] = (const float4*)s->send.p + so;
+                rp[j] = (float4*)s->recv.p + ro;
+                so += sn[j];
+                ro += rn[j];
+            }
+            const RowRegion out{s->send.p, so}, in{s->recv.p, ro};
+            if ((rc = transport_exchange(ctx, (int)peers.size(), peers.data(), sp.data(), sn.data(), rp.data(), rn.data(), 1, &out, &in,
+                                         nullptr, nullptr, "wtp_block topology")))
+                return rc;
+        }
         n_all = n + n_recv;
 
         // the local set in gid order
@@ -639,7 +578,7 @@ static int tp_run(wtp_ctx* ctx, const TpCall& c, wtp_block_topo_info* info) {
             span_end(ctx, sp);
             unsigned long long dup = 0;
             WTP_HIP(ctx, hipMemcpyAsync(&dup, &dst->dup, 8, hipMemcpyDeviceToHost, ctx->stream));
-            if ((rc = tp_sync(ctx))) return rc;
+            if ((rc = sync(ctx))) return rc;
             // (a gid seen twice leaves holes in the local set: it is not searched)
             if (dup) my_status = WTP_ERR_ARG;
             TpBox cb;
@@ -679,14 +618,14 @@ static int tp_run(wtp_ctx* ctx, const TpCall& c, wtp_block_topo_info* info) {
                 span_end(ctx, sp);
                 unsigned long long nu = 0;
                 WTP_HIP(ctx, hipMemcpyAsync(&nu, &dst->n_uncert, 8, hipMemcpyDeviceToHost, ctx->stream));
-                if ((rc = tp_sync(ctx))) return rc;
+                if ((rc = sync(ctx))) return rc;
                 uncert = (int64_t)nu;
             }
         }
         // {status, incomplete rows} of every rank
         w2[0] = my_status;
         w2[1] = uncert;
-        if ((rc = tp_allgather(cm, w2.data(), g2.data(), 2))) return rc;
+        if ((rc = allgather(w2.data(), g2.data(), 2))) return rc;
         int64_t total = 0;
         for (int q = 0; q < R; ++q)
             if (g2[2 * q])
@@ -713,11 +652,11 @@ static int tp_run(wtp_ctx* ctx, const TpCall& c, wtp_block_topo_info* info) {
             WTP_HIP(ctx, hipMemcpyAsync(c.off_out, s->own_off.p, 8 * (size_t)(n + 1), hipMemcpyDeviceToDevice, ctx->stream));
         int64_t nnz = 0;
         WTP_HIP(ctx, hipMemcpyAsync(&nnz, (int64_t*)s->own_off.p + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-        if ((rc = tp_sync(ctx))) return rc;
+        if ((rc = sync(ctx))) return rc;
         s->rad_ready = true;
         s->rad_n_owned = n;
         s->rad_nnz = nnz;
-    } else if ((rc = tp_sync(ctx))) {
+    } else if ((rc = sync(ctx))) {
         return rc;
     }
     if (info) {
@@ -764,5 +703,5 @@ WTP_API int wtp_block_radius_fill(wtp_ctx* ctx, int64_t* d_idx_out) {
                            (const int32_t*)s->lgid.p, (const int64_t*)s->own_off.p, d_idx_out);
         WTP_HIP(ctx, hipGetLastError());
     }
-    return tp_sync(ctx);
+    return sync(ctx);
 }

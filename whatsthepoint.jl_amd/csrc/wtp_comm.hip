@@ -9,6 +9,10 @@
 // (WTP_COMM=abi), which is how the entry points are exercised.
 //
 // librccl is opened at the first wtp_comm_* call (dlopen), not linked: a single-GPU user of libwtp never loads it.
+//
+// The block driver (wtp_block.hip) and the sharded topology (wtp_block_topo.hip) reach the other ranks
+// through the context's Transport (wtp_internal.hpp), at the end of this file: the caller's host callbacks
+// (wtp_block_set_transport) or this communicator, behind one readiness check, one all-gather and one grouped exchange.
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
@@ -214,20 +218,13 @@ WTP_API int wtp_comm_allreduce_stats(wtp_ctx* ctx, wtp_step_stats* st) {
     return WTP_OK;
 }
 
-// ---- primitives of the block iteration (wtp_block.hip; also exported) --------------------------------------------------
+// ---- primitives of the block iteration (also exported) -------------------------------------------------------------
 // One grouped round: every message is a send to and a receive from peers[j].  Both sides walk their peer lists in
 // ascending rank order and post (send, recv) per peer inside ONE group, so the pairs match without any ordering between
 // different peers; the counts were agreed on beforehand (they ride with the previous iteration's all-gather).
-WTP_API int wtp_comm_exchange_peers(wtp_ctx* ctx, int n_msgs, const int* peers, const void* const* d_send,
-                                    const int64_t* n_send, void* const* d_recv, const int64_t* n_recv) {
-    if (!ctx) return WTP_ERR_ARG;
-    return wtp::comm_exchange_peers_on(ctx, ctx->stream, n_msgs, peers, d_send, n_send, d_recv, n_recv);
-}
-
-// (the same round on a stream of the caller's choosing: the block driver posts it on the context's second stream and lets
-// the first one rank the owned points meanwhile)
-int wtp::comm_exchange_peers_on(wtp_ctx* ctx, hipStream_t stream, int n_msgs, const int* peers, const void* const* d_send,
-                                const int64_t* n_send, void* const* d_recv, const int64_t* n_recv) {
+// (on a stream of the caller's choosing: transport_exchange posts it on the context's second stream when it overlaps)
+static int exchange_peers_on(wtp_ctx* ctx, hipStream_t stream, int n_msgs, const int* peers, const void* const* d_send,
+                             const int64_t* n_send, void* const* d_recv, const int64_t* n_recv) {
     if (!ctx->comm) return fail(ctx, WTP_ERR_STATE, "wtp_comm_exchange_peers before wtp_comm_init");
     if (n_msgs < 0 || (n_msgs > 0 && (!peers || !d_send || !n_send || !d_recv || !n_recv)))
         return fail(ctx, WTP_ERR_ARG, "wtp_comm_exchange_peers: NULL argument");
@@ -251,6 +248,12 @@ int wtp::comm_exchange_peers_on(wtp_ctx* ctx, hipStream_t stream, int n_msgs, co
     return WTP_OK;
 }
 
+WTP_API int wtp_comm_exchange_peers(wtp_ctx* ctx, int n_msgs, const int* peers, const void* const* d_send,
+                                    const int64_t* n_send, void* const* d_recv, const int64_t* n_recv) {
+    if (!ctx) return WTP_ERR_ARG;
+    return exchange_peers_on(ctx, ctx->stream, n_msgs, peers, d_send, n_send, d_recv, n_recv);
+}
+
 WTP_API int wtp_comm_allgather_dev(wtp_ctx* ctx, const void* d_send, void* d_recv, int64_t bytes) {
     if (!ctx || !d_send || !d_recv) return WTP_ERR_ARG;
     if (!ctx->comm) return fail(ctx, WTP_ERR_STATE, "wtp_comm_allgather_dev before wtp_comm_init");
@@ -258,4 +261,128 @@ WTP_API int wtp_comm_allgather_dev(wtp_ctx* ctx, const void* d_send, void* d_rec
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     WTP_NCCL(ctx, g_rccl.AllGather(d_send, d_recv, (size_t)bytes / 8, ncclUint64, (ncclComm_t)ctx->comm, ctx->stream));
     return WTP_OK;
+}
+
+// ---- the transport of the block driver and the sharded topology (Transport, wtp_internal.hpp) ------------------------
+WTP_API int wtp_block_set_transport(wtp_ctx* ctx, const wtp_transport* t) {
+    if (!ctx) return WTP_ERR_ARG;
+    if (block_session_open(ctx)) return fail(ctx, WTP_ERR_STATE, "wtp_block_set_transport while a block session is open");
+    if (t) {
+        if (!t->allgather || !t->exchange) return fail(ctx, WTP_ERR_ARG, "wtp_block_set_transport: both callbacks are needed");
+        ctx->transport.tr = *t;
+    }
+    ctx->transport.host = t != nullptr;
+    return WTP_OK;
+}
+
+int wtp::transport_ready(wtp_ctx* ctx, int rank, int nranks, const std::string& who) {
+    if (ctx->transport.host || nranks <= 1 || (ctx->comm && ctx->comm_size == nranks && ctx->comm_rank == rank)) return WTP_OK;
+    return fail(ctx, WTP_ERR_STATE, who + "wtp_comm_init (same rank / nranks) or wtp_block_set_transport first");
+}
+
+int wtp::transport_allgather(wtp_ctx* ctx, int nranks, const void* mine, bool on_device, int64_t* all, int64_t nwords,
+                             const char* who) {
+    Transport& t = ctx->transport;
+    const size_t bytes = 8 * (size_t)nwords;
+    int rc;
+    if (nranks == 1 && !on_device) { // nothing to gather and nothing to fetch: no transport is asked
+        memcpy(all, mine, bytes);
+        return WTP_OK;
+    }
+    if (t.host) {
+        if (on_device) {
+            t.hbuf_a.resize(bytes);
+            WTP_HIP(ctx, hipMemcpyAsync(t.hbuf_a.data(), mine, bytes, hipMemcpyDeviceToHost, ctx->stream));
+            if ((rc = sync(ctx))) return rc;
+            mine = t.hbuf_a.data();
+        }
+        if (t.tr.allgather(t.tr.user, mine, all, (int64_t)bytes) != 0)
+            return fail(ctx, WTP_ERR_STATE, std::string(who) + ": the caller's allgather callback failed");
+        return WTP_OK;
+    }
+    if (nranks == 1) { // no communicator needed: the words themselves
+        WTP_HIP(ctx, hipMemcpyAsync(all, mine, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return sync(ctx);
+    }
+    if ((rc = ensure(ctx, t.gbuf, bytes * (size_t)(nranks + 1)))) return rc;
+    char* d = (char*)t.gbuf.p;
+    if (!on_device) {
+        WTP_HIP(ctx, hipMemcpyAsync(d, mine, bytes, hipMemcpyHostToDevice, ctx->stream));
+        mine = d;
+    }
+    if ((rc = wtp_comm_allgather_dev(ctx, mine, d + bytes, (int64_t)bytes))) return rc;
+    WTP_HIP(ctx, hipMemcpyAsync(all, d + bytes, bytes * (size_t)nranks, hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
+}
+
+int wtp::transport_exchange(wtp_ctx* ctx, int n_msgs, const int* peers, const void* const* d_send, const int64_t* n_send,
+                            void* const* d_recv, const int64_t* n_recv, int n_regions, const RowRegion* send, const RowRegion* recv,
+                            int (*meanwhile)(wtp_ctx*, void*), void* arg, const char* who) {
+    Transport& t = ctx->transport;
+    int rc;
+    if (meanwhile) { // the second stream and the two events that tie it to the first (created on first use)
+        if (!ctx->comm_stream) WTP_HIP(ctx, hipStreamCreateWithFlags(&ctx->comm_stream, hipStreamNonBlocking));
+        if (!ctx->ev_comm_a) WTP_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_comm_a, hipEventDisableTiming));
+        if (!ctx->ev_comm_b) WTP_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_comm_b, hipEventDisableTiming));
+    }
+    if (!t.host) {
+        if (!meanwhile) return wtp_comm_exchange_peers(ctx, n_msgs, peers, d_send, n_send, d_recv, n_recv);
+        // Exchange and compute overlap: the grouped round runs on the context's second stream, every peer on
+        // its own link; the first stream does the caller's work meanwhile and waits for the rows only behind it.
+        WTP_HIP(ctx, hipEventRecord(ctx->ev_comm_a, ctx->stream)); // (the send rows and the receive regions' last readers are in stream order before it)
+        WTP_HIP(ctx, hipStreamWaitEvent(ctx->comm_stream, ctx->ev_comm_a, 0));
+        if ((rc = exchange_peers_on(ctx, ctx->comm_stream, n_msgs, peers, d_send, n_send, d_recv, n_recv))) return rc;
+        WTP_HIP(ctx, hipEventRecord(ctx->ev_comm_b, ctx->comm_stream));
+        rc = meanwhile(ctx, arg);
+        WTP_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_comm_b, 0)); // (also when the work failed: the streams join again)
+        return rc;
+    }
+    // host transport: regions out, callback, regions in; the host layout is the regions one behind the other
+    std::vector<size_t> so(n_regions + 1, 0), ro(n_regions + 1, 0); // byte offset of every region in hbuf_a / hbuf_b
+    for (int r = 0; r < n_regions; ++r) {
+        so[r + 1] = so[r] + 16 * (size_t)send[r].rows;
+        ro[r + 1] = ro[r] + 16 * (size_t)recv[r].rows;
+    }
+    const size_t out_bytes = so[n_regions], in_bytes = ro[n_regions];
+    t.hbuf_a.resize(out_bytes + 16);
+    t.hbuf_b.resize(in_bytes + 16);
+    for (int r = 0; r < n_regions; ++r)
+        if (send[r].rows)
+            WTP_HIP(ctx, hipMemcpyAsync(t.hbuf_a.data() + so[r], send[r].d, so[r + 1] - so[r], hipMemcpyDeviceToHost, ctx->stream));
+    if (meanwhile) {
+        // the host waits for the rows only; the stream goes on with the caller's work under the callback
+        WTP_HIP(ctx, hipEventRecord(ctx->ev_comm_a, ctx->stream));
+        if ((rc = meanwhile(ctx, arg))) return rc;
+        ctx->timers.ev_last_end = -1;
+        WTP_HIP(ctx, hipEventSynchronize(ctx->ev_comm_a));
+        ctx->n_syncs += 1;
+    } else if (out_bytes && (rc = sync(ctx))) {
+        return rc;
+    }
+    // a message's host address: where its region was staged plus its offset in the region; NULL if the message does
+    // not lie inside one region (an empty message may lie anywhere: it gets the buffer's start)
+    auto staged = [&](const RowRegion* reg, const std::vector<size_t>& at, unsigned char* h, const void* p, size_t bytes) {
+        for (int r = 0; r < n_regions; ++r) {
+            const uintptr_t a = (uintptr_t)p, base = (uintptr_t)reg[r].d;
+            if (a >= base && a - base + bytes <= at[r + 1] - at[r]) return h + at[r] + (a - base);
+        }
+        return bytes ? nullptr : h;
+    };
+    std::vector<const void*> hs(n_msgs);
+    std::vector<void*> hr(n_msgs);
+    std::vector<int64_t> sb(n_msgs), rb(n_msgs);
+    for (int j = 0; j < n_msgs; ++j) {
+        sb[j] = 16 * n_send[j];
+        rb[j] = 16 * n_recv[j];
+        hs[j] = staged(send, so, t.hbuf_a.data(), d_send[j], (size_t)sb[j]);
+        hr[j] = staged(recv, ro, t.hbuf_b.data(), d_recv[j], (size_t)rb[j]);
+        if (!hs[j] || !hr[j]) return fail(ctx, WTP_ERR_ARG, std::string(who) + ": a message of the exchange lies outside its regions");
+    }
+    if (t.tr.exchange(t.tr.user, n_msgs, peers, hs.data(), sb.data(), hr.data(), rb.data()) != 0)
+        return fail(ctx, WTP_ERR_STATE, std::string(who) + ": the caller's exchange callback failed");
+    if (!in_bytes) return WTP_OK;
+    for (int r = 0; r < n_regions; ++r)
+        if (recv[r].rows)
+            WTP_HIP(ctx, hipMemcpyAsync(recv[r].d, t.hbuf_b.data() + ro[r], ro[r + 1] - ro[r], hipMemcpyHostToDevice, ctx->stream));
+    return sync(ctx); // (the host buffers are reused)
 }

@@ -386,6 +386,63 @@ struct F64Stage {
     DevBuf grid_b, cell_start_b, box_b, s64, slot, lists, cnt;
 };
 
+// How this rank reaches the others (wtp_comm.hip): the caller's host callbacks (wtp_block_set_transport) or, without them,
+// the context's RCCL communicator.  The block driver and the sharded topology both go through transport_ready,
+// transport_allgather and transport_exchange below.
+struct Transport {
+    bool host = false;                         // wtp_block_set_transport gave callbacks
+    wtp_transport tr{};
+    std::vector<unsigned char> hbuf_a, hbuf_b; // host staging around the callbacks: rows out, rows in
+    DevBuf gbuf;                               // an all-gather through RCCL: [this rank's words ; every rank's]
+};
+
+// a device region of 16-byte rows that messages of a grouped exchange lie in
+struct RowRegion {
+    void* d;
+    int64_t rows;
+};
+
+// The reference's stop rules (`_relax!`, src/repel.jl:305-334) for one run: on the device for wtp_relax_run_until
+// (ctx->stop_state), on the host for wtp_block_run_until.  best_cv starts at +inf (typemax(U), src/repel.jl:238).
+struct StopState {
+    int32_t stopped, reason, n_done, last_impr;
+    double best_cv;
+};
+
+// One sweep's statistics (sweep number iter1, from 1) under the rules, in the reference's order: cv_target (the caller
+// then reverts p to p_old), the stall counter on the CV of d_NN / s, the tolerance on max |F| s.  reason: 1 tol,
+// 2 cv_target, 3 stall.
+__host__ __device__ inline void stop_rules_apply(StopState& s, const wtp_step_stats& st, int iter1, double tol, int stall_after,
+                                                 double cv_target) {
+    if (s.stopped) return;
+    s.n_done = iter1;
+    const double conv = st.max_force;
+    if ((stall_after > 0 || cv_target > 0) && st.n_move > 0) {
+        const double n = (double)st.n_move, mu = st.sum_u / n;
+        const double var = st.sum_u2 / n - mu * mu;
+        const double cv = sqrt(var > 0.0 ? var : 0.0) / mu; // _dnn_cv, src/repel.jl:374-386
+        if (cv_target > 0 && cv <= cv_target) {
+            s.stopped = 1;
+            s.reason = 2;
+            return;
+        }
+        if (stall_after > 0) {
+            if (cv < s.best_cv * (1 - 1.0e-3)) {
+                s.best_cv = cv;
+                s.last_impr = iter1;
+            } else if (iter1 - s.last_impr >= stall_after) {
+                s.stopped = 1;
+                s.reason = 3;
+                return;
+            }
+        }
+    }
+    if (conv < tol) {
+        s.stopped = 1;
+        s.reason = 1;
+    }
+}
+
 } // namespace wtp
 
 struct wtp_ctx {
@@ -429,7 +486,7 @@ struct wtp_ctx {
     wtp::DevBuf brick_dead;    // wtp_cs2.hip, variable spacing: one byte per brick (cs2_dead_kernel)
     wtp::Prerank prerank;             // wtp_hash.hip: prerank_old_snapshot
     int64_t preranked_builds = 0;     // hash builds that took a first half over
-    hipStream_t comm_stream = nullptr; // block driver: the grouped exchange runs here while the owned points are ranked
+    hipStream_t comm_stream = nullptr; // transport_exchange: the grouped round runs here while the caller's work runs on `stream`
     hipEvent_t ev_comm_a = nullptr, ev_comm_b = nullptr;
     bool hash_scratch_clean = false;  // cell counts and dirty map are all-zero (every completed build leaves them so)
     bool counters_clean = false;      // the counter block (StepCounters in fb_count) is all-zero (the step's final reduction leaves it so)
@@ -446,6 +503,7 @@ struct wtp_ctx {
     void* block_topo = nullptr; // wtp::TopoState (wtp_block_topo.hip): buffers of the sharded KNN / radius rows
     void* comm = nullptr;      // ncclComm_t (wtp_comm.hip); rank and size of the communicator
     int comm_rank = 0, comm_size = 0;
+    wtp::Transport transport;  // callbacks in place of the communicator, and the staging either one needs (wtp_comm.hip)
     wtp::DevBuf comm_scratch;
     wtp::DevBuf sp_cert;       // device-evaluated spacing laws: per point, where it stood at its last tree walk and the bound that walk left (wtp_spacing.hip)
     void* host_pinned = nullptr;
@@ -641,8 +699,17 @@ int relax_step_enqueue(wtp_ctx* ctx, int rebuild, wtp_step_stats* d_slot); // on
 int relax_swap_begin(wtp_ctx* ctx, int64_t n_move_new, void** d_buf_out);  // a free point buffer for a replaced movable set ...
 int relax_swap_commit(wtp_ctx* ctx, int64_t n_move_new);                   // ... which becomes the session's P (no fixed head, tuning kept)
 int relax_set_fixed_dev_impl(wtp_ctx* ctx, const void* d_fixed4, int64_t n_fixed_new, bool keep_alive);
-int comm_exchange_peers_on(wtp_ctx* ctx, hipStream_t stream, int n_msgs, const int* peers, const void* const* d_send,
-                           const int64_t* n_send, void* const* d_recv, const int64_t* n_recv); // wtp_comm.hip
+// wtp_comm.hip: the transport of the block driver and the sharded topology (see Transport); `who` leads the error texts.
+// A caller's transport, or a communicator of this rank and size (one rank needs neither)
+int transport_ready(wtp_ctx* ctx, int rank, int nranks, const std::string& who);
+// every rank's `nwords` 8-byte words (device or host memory) into the host array all[nranks * nwords], rank-major
+int transport_allgather(wtp_ctx* ctx, int nranks, const void* mine, bool on_device, int64_t* all, int64_t nwords, const char* who);
+// One grouped round, messages as wtp_comm_exchange_peers takes them; a host transport stages whole regions (send[r] /
+// recv[r], r < n_regions) through the host.  meanwhile(ctx, arg), if given, enqueues work on the context's stream that
+// runs while the rows travel.
+int transport_exchange(wtp_ctx* ctx, int n_msgs, const int* peers, const void* const* d_send, const int64_t* n_send,
+                       void* const* d_recv, const int64_t* n_recv, int n_regions, const RowRegion* send, const RowRegion* recv,
+                       int (*meanwhile)(wtp_ctx*, void*), void* arg, const char* who);
 template <typename T> int launch_radius_dense(wtp_ctx* ctx, SearchArgs<T>& a, T r, int32_t* d_counts); // wtp_radb.hip
 template <typename T> int radius_dense_hcap();
 int launch_cs_all_slots(wtp_ctx* ctx, int32_t* list, int32_t n, int32_t* count); // wtp_cs2.hip: list = 0 .. n-1, *count = n
@@ -652,7 +719,6 @@ void block_destroy(wtp_ctx* ctx);                                          // fr
 // sharded topology (wtp_block_topo.hip) <-> block driver (wtp_block.hip) and the single-context searches (wtp_topology.hip)
 void block_topo_destroy(wtp_ctx* ctx);                                     // frees ctx->block_topo (wtp_destroy)
 bool block_session_open(wtp_ctx* ctx);                                     // a wtp_block_open session is active
-const wtp_transport* block_host_transport(wtp_ctx* ctx);                   // wtp_block_set_transport's callbacks, or NULL: RCCL
 int launch_blk_scan(wtp_ctx* ctx, int32_t* span_counts, int64_t nspans, int ncol, int32_t* totals); // column scan of per-span counts
 int topo_knn_local(wtp_ctx* ctx, const float* d_xyz, int64_t n, int k, int include_self, int32_t* d_idx, float* d_dist);
 // radius rows of a device fp32 3-D cloud: counts -> d_off (n + 1, exclusive scan) -> rows into *d_idx (grown to fit); *nnz

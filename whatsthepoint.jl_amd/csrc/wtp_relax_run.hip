@@ -64,43 +64,12 @@ WTP_API int wtp_relax_run(wtp_ctx* ctx, int n_iters, int rebuild_every, double* 
 }
 
 // ---- stop rules on the device (src/repel.jl:305-334) -----------------------------------------------------------
-// After every sweep of a batch one thread applies the reference's rules, in the reference's order, to that sweep's
-// statistics: cv_target (the caller then reverts p to p_old), the stall counter on the CV of d_NN / s, the tolerance
-// on max |F| s.  Once a rule fires, every kernel of the later iterations of the batch that would touch the session's
+// After every sweep of a batch one thread applies the reference's rules (stop_rules_apply, wtp_internal.hpp) to that
+// sweep's statistics.  Once a rule fires, every kernel of the later iterations of the batch that would touch the session's
 // state returns at once (SearchArgs::stop / ctx->stop_dev), so the state is that of the stopping iteration.
-struct StopState {
-    int32_t stopped, reason, n_done, last_impr;
-    double best_cv;
-};
 __global__ void stop_rules_kernel(const wtp_step_stats* __restrict__ st, StopState* __restrict__ s, int iter1, double tol,
                                   int stall_after, double cv_target) {
-    if (s->stopped) return;
-    s->n_done = iter1;
-    const double conv = st->max_force;
-    if ((stall_after > 0 || cv_target > 0) && st->n_move > 0) {
-        const double n = (double)st->n_move, mu = st->sum_u / n;
-        const double var = st->sum_u2 / n - mu * mu;
-        const double cv = sqrt(var > 0.0 ? var : 0.0) / mu; // _dnn_cv, src/repel.jl:374-386
-        if (cv_target > 0 && cv <= cv_target) {
-            s->stopped = 1;
-            s->reason = 2;
-            return;
-        }
-        if (stall_after > 0) {
-            if (cv < s->best_cv * (1 - 1.0e-3)) {
-                s->best_cv = cv;
-                s->last_impr = iter1;
-            } else if (iter1 - s->last_impr >= stall_after) {
-                s->stopped = 1;
-                s->reason = 3;
-                return;
-            }
-        }
-    }
-    if (conv < tol) {
-        s->stopped = 1;
-        s->reason = 1;
-    }
+    stop_rules_apply(*s, *st, iter1, tol, stall_after, cv_target);
 }
 
 WTP_API int wtp_relax_run_until(wtp_ctx* ctx, int max_iters, int rebuild_every, double tol, int stall_after,
