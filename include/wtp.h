@@ -223,9 +223,21 @@ int wtp_relax_end(wtp_ctx* ctx);
  * (`spacings` of src/repel.jl:209,251 — the kick and the trace read it).  Host array of n values. */
 int wtp_relax_get_spacing(wtp_ctx* ctx, void* spacing_out);
 
+/* Diagnostic, read-only: what a session with a LOGLIKE / BOUNDARY_LAYER law keeps per movable point between sweeps so
+ * that a point may skip its boundary search (WTP_ERR_STATE without a session or with any other spacing kind).  Host
+ * arrays over the n - n_fixed movable points in movable order, any of them NULL:
+ * hint_out[i]: index of the boundary-tree node that won the point's last search, -1 before the first;
+ * cert_out[4 i ..]: x_ref (three coordinates, z = 0 in 2-D: where the point stood at its last search) and lb, a lower
+ *   bound on the canonical d2 from x_ref to every boundary point other than the winner, in the session's dtype;
+ * winner_xyz_out[3 i ..]: the coordinates of node hint_out[i] (left untouched where the hint is -1).
+ * A search rewrites x_ref with the point's position at that sweep; a point whose certificate answered keeps its x_ref. */
+int wtp_relax_get_spacing_certs(wtp_ctx* ctx, int32_t* hint_out, void* cert_out, void* winner_xyz_out);
+
 /* A variable spacing law evaluated at arbitrary points (spacing.(points), e.g. the default
  * alpha = minimum(spacing.(to(cloud)))/20 of src/repel.jl:61, or the metrics): LOGLIKE /
- * BOUNDARY_LAYER descriptors only.  xyz: host n x dim of dtype, out: host n values.  */
+ * BOUNDARY_LAYER descriptors only.  xyz: host n x dim of dtype, out: host n values.  The context caches one boundary
+ * tree: while a relax session with a LOGLIKE / BOUNDARY_LAYER law is open, only that law's boundary (same points, dim and
+ * dtype) may be evaluated here; any other returns WTP_ERR_STATE instead of replacing the tree under the session.  */
 int wtp_spacing_eval(wtp_ctx* ctx, const wtp_spacing_desc* spacing, const void* xyz, int64_t n, int dim,
                      int dtype, void* out);
 

@@ -516,6 +516,10 @@ int ensure_kd(wtp_ctx* ctx, const wtp_spacing_desc* s, int dim, int dtype) {
     const unsigned char* b = (const unsigned char*)s->boundary_xyz;
     for (size_t i = 0; i < bytes; ++i) h = (h ^ b[i]) * 1099511628211ull;
     if (ctx->kd.m == s->n_boundary && ctx->kd.key == h && ctx->kd.dim == dim && ctx->kd.dtype == dtype) return WTP_OK;
+    // an open session with a device-evaluated law walks ctx->kd before every sweep: another boundary must not replace it
+    // (wtp_relax_init* itself comes here with the session not yet active)
+    if (ctx->relax.active && spacing_on_device(ctx->relax.spacing_kind))
+        return fail(ctx, WTP_ERR_STATE, "another boundary's spacing law while a relax session evaluates its own: end the session first");
     const size_t kdsz = by_dtype(dtype, [&](auto t) { return kd_bytes<decltype(t)>(s->n_boundary); });
     int rc;
     if ((rc = ensure(ctx, ctx->kd.nodes, kdsz))) return rc;
@@ -561,4 +565,47 @@ WTP_API int wtp_spacing_eval(wtp_ctx* ctx, const wtp_spacing_desc* spacing, cons
     if (rc) return rc;
     WTP_HIP(ctx, hipMemcpyAsync(out, ctx->ins_out.p, ts * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     return sync(ctx);
+}
+
+// Diagnostic read-out of what spacing_session_kernel keeps per movable point (copies only, no kernel): the entries of
+// movable point i sit at [n_fixed + i - aux_off], as the session kernel addresses them by id.
+WTP_API int wtp_relax_get_spacing_certs(wtp_ctx* ctx, int32_t* hint_out, void* cert_out, void* winner_xyz_out) {
+    int rc = need_session(ctx, __func__);
+    if (rc) return rc;
+    RelaxState& r = ctx->relax;
+    if (!spacing_on_device(r.spacing_kind))
+        return fail(ctx, WTP_ERR_STATE, "wtp_relax_get_spacing_certs: the session's spacing law is not evaluated on the device");
+    const int64_t n_move = r.n - r.n_fixed, first = r.n_fixed - r.aux_off;
+    if (n_move == 0 || (!hint_out && !cert_out && !winner_xyz_out)) return WTP_OK;
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t ts = tsize(r.dtype);
+    const int64_t m = ctx->kd.m;
+    std::vector<int32_t> hint(hint_out || winner_xyz_out ? (size_t)n_move : 0); // (the winners are looked up through it)
+    if (!hint.empty())
+        WTP_HIP(ctx, hipMemcpyAsync(hint.data(), (const int32_t*)ctx->sp_hint.p + first, sizeof(int32_t) * (size_t)n_move,
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    if (cert_out)
+        WTP_HIP(ctx, hipMemcpyAsync(cert_out, (const char*)ctx->sp_cert.p + 4 * ts * (size_t)first, 4 * ts * (size_t)n_move,
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    const size_t node_sz = by_dtype(r.dtype, [](auto t) { return sizeof(KdNode<decltype(t)>); });
+    std::vector<char> nodes(winner_xyz_out ? node_sz * (size_t)m : 0);
+    if (winner_xyz_out)
+        WTP_HIP(ctx, hipMemcpyAsync(nodes.data(), ctx->kd.nodes.p, nodes.size(), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = sync(ctx))) return rc;
+    if (hint_out) memcpy(hint_out, hint.data(), sizeof(int32_t) * (size_t)n_move);
+    if (winner_xyz_out)
+        by_dtype(r.dtype, [&](auto t) {
+            using T = decltype(t);
+            const KdNode<T>* nd = (const KdNode<T>*)nodes.data();
+            T* out = (T*)winner_xyz_out;
+            for (int64_t i = 0; i < n_move; ++i) {
+                const int32_t h = hint[(size_t)i];
+                if (h < 0 || h >= m) continue; // no winner yet: the caller's values stay
+                out[3 * i] = nd[h].p.x;
+                out[3 * i + 1] = nd[h].p.y;
+                out[3 * i + 2] = nd[h].p.z;
+            }
+            return 0;
+        });
+    return WTP_OK;
 }

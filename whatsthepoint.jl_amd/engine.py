@@ -430,6 +430,17 @@ class RelaxSession:
         L.check(self.ctx._h, self._lib.wtp_relax_get_spacing(self.ctx._h, _vp(out)))
         return out
 
+    def spacing_certs(self):
+        """Diagnostic (wtp_relax_get_spacing_certs), device-evaluated laws only: per movable point the winning tree node
+        of its last boundary search (-1: none yet), where it stood then and the bound that search left, and the winner's
+        coordinates: dict(hint int32[m], x_ref (m, 3), lb [m], winner (m, 3)); winner rows are NaN where hint < 0."""
+        m = self.n - self.n_fixed
+        hint = np.empty(m, dtype=np.int32)
+        cert = np.empty((m, 4), dtype=self.dtype)
+        winner = np.full((m, 3), np.nan, dtype=self.dtype)
+        L.check(self.ctx._h, self._lib.wtp_relax_get_spacing_certs(self.ctx._h, _vp(hint), _vp(cert), _vp(winner)))
+        return dict(hint=hint, x_ref=cert[:, :3].copy(), lb=cert[:, 3].copy(), winner=winner)
+
     def set_spacing(self, spacing):
         sp = np.ascontiguousarray(spacing, dtype=self.dtype)
         if sp.shape != (self.n,):
