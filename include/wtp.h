@@ -319,6 +319,38 @@ int wtp_pca_normals(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype
 int wtp_gradient_limit(wtp_ctx* ctx, const void* centers, int64_t n, int dim, int dtype, int k, const void* h0,
                        double g, double tol, int max_sweeps, void* h_out, int* sweeps_out);
 
+/* The reductions of metrics / spacing_metrics / spacing_fidelity_metrics (src/metrics.jl:19-129) over the k-NN distance
+ * rows, on the device: the search of KNearestSearch(cloud, k) (k counts the point itself, 2 <= k <= n), then one pass
+ * over the n x k distances where the search left them.  Slot 0 of a row (the point itself, or a coincident twin at
+ * distance 0) is dropped as x[2][2:end] does; the statistics cover the k_eff = k - 1 slots behind it.  Per point, in
+ * double and in slot order: mean_i, the two-pass sample deviation std_i (NaN for k_eff = 1, as Julia's std of one
+ * value), max_i and min_i = nn_i (slot 1); with a spacing h_i also e_i = |mean_i - h_i| / h_i, u_i = nn_i / h_i and
+ * c_i = #{slots with d <= coord_radius h_i}.  The struct holds their sums over the cloud (divide by n), the extremes
+ * of nn_i with the smallest index that attains each, and the sums of squared deviations of e and u from their means
+ * (sample variance = ssd / (n - 1)), merged from per-block (count, sum, M2) triples.  The reduction order is fixed and
+ * uses no floating-point atomics: two calls on the same cloud return the same bits; no sum chains more than 4096
+ * additions.  Without a spacing has_spacing = 0 and the fields from sum_err on are zero.  (The struct shares its name
+ * with the call, as stat does: it has a tag and no typedef, so write `struct wtp_knn_stats`.)  */
+struct wtp_knn_stats {
+    int64_t n; int32_t k_eff; int32_t has_spacing;
+    double sum_mean, sum_std, sum_max, sum_min;   /* divide by n for metrics()' avg/std/max/min */
+    double nn_min, nn_max; int64_t nn_min_i, nn_max_i; /* separation, fill */
+    double sum_err, ssd_err, max_err;             /* e_i; ssd = sum of squared deviations from the mean */
+    double sum_u, ssd_u;                          /* u_i = nn_i / h_i */
+    int64_t sum_coord;
+};
+/* xyz: host n x dim of dtype.  h: n host doubles, each finite and > 0 (checked on the device: WTP_ERR_ARG names the
+ * first offending index), or NULL; with h == NULL a h_const > 0 is the spacing of every point and h_const <= 0 means no
+ * spacing.  out: host.  nn_out (n of dtype) and mean_out (n doubles): host arrays or NULL.  The call copies back the
+ * struct and those two arrays, never the n x k matrices.  Like every call that runs the k-NN search (wtp_knn,
+ * wtp_pca_normals, ...) it ends a pending wtp_radius_count / wtp_radius_fill pair; WTP_ERR_STATE while a relax session
+ * is open.  */
+int wtp_knn_stats(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype, int k, const double* h, double h_const,
+                  double coord_radius, struct wtp_knn_stats* out, void* nn_out, double* mean_out);
+/* The same with d_xyz, d_h, d_nn_out and d_mean_out in device memory; out stays a host struct.  */
+int wtp_knn_stats_dev(wtp_ctx* ctx, const void* d_xyz, int64_t n, int dim, int dtype, int k, const double* d_h,
+                      double h_const, double coord_radius, struct wtp_knn_stats* out, void* d_nn_out, double* d_mean_out);
+
 /* ---- sharded sessions (no counterpart in the reference) --------------
  * One rank sweeps one spatial slab.  Its session's fixed head is the ghost layer received
  * from the neighbouring ranks, its movable tail the points it owns.  The two calls below
@@ -517,6 +549,17 @@ int wtp_block_radius_offsets(wtp_ctx* ctx, int rank, int nranks, const void* d_x
  * (d², gid): equal to wtp_radius_fill's rows of the assembled cloud.  WTP_ERR_STATE without a preceding
  * wtp_block_radius_offsets on this context.  */
 int wtp_block_radius_fill(wtp_ctx* ctx, int64_t* d_idx_out);
+/* Collective.  wtp_knn_stats of the assembled cloud without assembling it: every rank searches its rows as
+ * wtp_block_knn does (include_self = 1, distances into an internal buffer), reduces its owned rows on the device, and one
+ * more all-gather carries each rank's partial struct; every rank merges the partials in rank order ((count, sum, M2)
+ * triples for the variances), so `out` is the global view, the same bytes on every rank.  nn_min_i / nn_max_i are
+ * global ids, ties to the smaller gid.  A rank with n_owned = 0 contributes the neutral element.  2 <= k <= N_total
+ * (k counts the point itself).  d_h: n_owned device doubles in the caller's order or NULL (then h_const as in
+ * wtp_knn_stats); the ranks that own points must agree on whether there is a spacing.  d_nn_out: n_owned fp32 (device)
+ * or NULL.  A bad argument on any rank, a bad spacing value included, is WTP_ERR_ARG on all of them.  */
+int wtp_block_knn_stats(wtp_ctx* ctx, int rank, int nranks, const void* d_xyz, const int64_t* d_gid, int64_t n_owned, int k,
+                        const double* d_h, double h_const, double coord_radius, double width, struct wtp_knn_stats* out,
+                        float* d_nn_out, wtp_block_topo_info* info);
 /* Grouped point-to-point primitive of the exchange, exposed for callers that drive their own iteration: message j is
  * sent to and received from rank peers[j], rows of 16 bytes, device buffers, stream-ordered on the context's stream.
  * Counts must agree on both sides (ncclSend/ncclRecv semantics).  peers[j] may equal the caller's own rank. */

@@ -62,6 +62,40 @@ function search_with_dists(points, k::Int)
     return [Int.(view(idx, :, i)) .+ 1 for i in 1:n], [collect(view(dist, :, i)) for i in 1:n]
 end
 
+# ---- src/metrics.jl:19-129: the reductions over the distance rows, on the device (include/wtp.h: wtp_knn_stats) ------
+mutable struct KnnStats
+    n::Int64; k_eff::Int32; has_spacing::Int32
+    sum_mean::Float64; sum_std::Float64; sum_max::Float64; sum_min::Float64
+    nn_min::Float64; nn_max::Float64; nn_min_i::Int64; nn_max_i::Int64
+    sum_err::Float64; ssd_err::Float64; max_err::Float64
+    sum_u::Float64; ssd_u::Float64; sum_coord::Int64
+    KnnStats() = new()
+end
+
+# k counts the point itself, as KNearestSearch(cloud, k) does.  h: nothing, one positive number, or one value per point.
+# Returns (stats, nn) with nn the n nearest-neighbour distances when want_nn (the quantiles of spacing_fidelity_metrics).
+function knn_stats(points, k::Int; h = nothing, coord_radius = 1.4, want_nn = false)
+    xs = raw(points); D = length(first(xs)); T = eltype(first(xs)); n = length(xs)
+    st = KnnStats()
+    hv = h isa AbstractVector ? Vector{Float64}(ustrip.(h)) : nothing
+    hc = h isa Number ? Float64(ustrip(h)) : 0.0
+    nn = want_nn ? Vector{T}(undef, n) : nothing
+    check(context(), ccall((:wtp_knn_stats, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cint, Cint, Cint, Ptr{Float64}, Float64, Float64, Ref{KnnStats}, Ptr{Cvoid}, Ptr{Float64}),
+        context(), xs, n, D, dtype(T), k, hv === nothing ? C_NULL : hv, hc, Float64(coord_radius), st,
+        nn === nothing ? C_NULL : nn, C_NULL))
+    return st, nn
+end
+
+# body of metrics(cloud; k) (src/metrics.jl:19-41) without the printing
+function metrics(cloud; k::Int = 20)
+    pts = WhatsThePoint.points(cloud); k = min(length(pts), k)
+    st, _ = knn_stats(pts, k)
+    n = st.n
+    return (avg = st.sum_mean / n, std = st.sum_std / n, max = st.sum_max / n, min = st.sum_min / n, k = k,
+            separation = st.nn_min, fill = st.nn_max, mesh_ratio = st.nn_min > 0 ? st.nn_max / st.nn_min : Inf)
+end
+
 # ---- src/topology.jl:91-97 -------------------------------------------------------------------------
 function build_radius_neighbors(points, radius)
     r = ustrip(WhatsThePoint._get_radius(radius, points))

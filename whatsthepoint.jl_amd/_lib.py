@@ -63,6 +63,15 @@ class BlockTopoInfo(C.Structure):
                 ("widened", C.c_int32), ("host_syncs", C.c_int32), ("reserved", C.c_int32)]
 
 
+class KnnStats(C.Structure):
+    """struct wtp_knn_stats: the sums behind metrics / spacing_metrics / spacing_fidelity_metrics."""
+    _fields_ = [("n", C.c_int64), ("k_eff", C.c_int32), ("has_spacing", C.c_int32),
+                ("sum_mean", C.c_double), ("sum_std", C.c_double), ("sum_max", C.c_double), ("sum_min", C.c_double),
+                ("nn_min", C.c_double), ("nn_max", C.c_double), ("nn_min_i", C.c_int64), ("nn_max_i", C.c_int64),
+                ("sum_err", C.c_double), ("ssd_err", C.c_double), ("max_err", C.c_double),
+                ("sum_u", C.c_double), ("ssd_u", C.c_double), ("sum_coord", C.c_int64)]
+
+
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                           C.POINTER(C.c_void_p), C.POINTER(C.c_int64))
@@ -102,6 +111,8 @@ SIGNATURES = {
     "wtp_relax_get_spacing_certs": (_i, [_vp, _vp, _vp, _vp]),
     "wtp_spacing_eval": (_i, [_vp, C.POINTER(SpacingDesc), _vp, _i64, _i, _i, _vp]),
     "wtp_pca_normals": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp]),
+    "wtp_knn_stats": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _d, _d, C.POINTER(KnnStats), _vp, _vp]),
+    "wtp_knn_stats_dev": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _d, _d, C.POINTER(KnnStats), _vp, _vp]),
     "wtp_gradient_limit": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _d, _d, _i, _vp, C.POINTER(_i)]),
     "wtp_mesh_set": (_i, [_vp, _vp, _i64, _vp, _i64, _i]),
     "wtp_mesh_clear": (_i, [_vp]),
@@ -139,6 +150,8 @@ SIGNATURES = {
     "wtp_block_grid": (_i, [_i, C.POINTER(_i)]),
     "wtp_block_morton_rank": (_i, [_i, _i, _i, C.POINTER(_i)]),
     "wtp_block_knn": (_i, [_vp, _i, _i, _vp, _vp, _i64, _i, _i, _d, _vp, _vp, C.POINTER(BlockTopoInfo)]),
+    "wtp_block_knn_stats": (_i, [_vp, _i, _i, _vp, _vp, _i64, _i, _vp, _d, _d, _d, C.POINTER(KnnStats), _vp,
+                                C.POINTER(BlockTopoInfo)]),
     "wtp_block_radius_offsets": (_i, [_vp, _i, _i, _vp, _vp, _i64, _d, _vp, C.POINTER(BlockTopoInfo)]),
     "wtp_block_radius_fill": (_i, [_vp, _vp]),
     "wtp_comm_exchange_peers": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_vp), C.POINTER(_i64)]),

@@ -319,6 +319,36 @@ def block_knn(ctx, rank: int, nranks: int, owned_xyz, gid, k: int, include_self:
     return idx, dist, _topo_info(info)
 
 
+def block_knn_stats(ctx, rank: int, nranks: int, owned_xyz, gid, k: int, h=None, coord_radius: float = 1.4, return_nn: bool = False,
+                    width: float = 0.0, transport=None):
+    """Context.knn_stats of the assembled cloud from its shards (collective: every rank calls it; wtp_block_knn_stats).
+    k counts the point itself.  h: None, one positive number, or this rank's n values in the order of owned_xyz (numpy or a
+    float64 torch tensor).  Returns (stats dict, the same on every rank, with global ids in nn_min_i / nn_max_i; nn: this
+    rank's nearest-neighbour distances as a float32 torch tensor, or None; info)."""
+    n = _topo_inputs(owned_xyz, gid)
+    import torch
+
+    dev = torch.device("cuda", ctx.device)
+    x, g = _on_device(owned_xyz, dev), _on_device(gid, dev)
+    hv, hc = None, 0.0
+    if h is not None:
+        if np.ndim(h) == 0 and not torch.is_tensor(h):
+            hc = float(h)
+        else:
+            hv = _on_device(h, dev).to(torch.float64).reshape(-1).contiguous()
+            if hv.shape[0] != n:
+                raise L.WtpArgumentError("h needs one value per owned point")
+    nn = torch.empty(n, dtype=torch.float32, device=dev) if return_nn else None
+    st, info = L.KnnStats(), L.BlockTopoInfo()
+    torch.cuda.synchronize(dev)
+    with _TransportFor(ctx, transport):
+        rc = ctx._lib.wtp_block_knn_stats(ctx._h, int(rank), int(nranks), _ptr(x), _ptr(g), n, int(k),
+                                          C.c_void_p(hv.data_ptr()) if hv is not None else None, hc, float(coord_radius),
+                                          float(width), C.byref(st), _ptr(nn), C.byref(info))
+    L.check(ctx._h, rc)
+    return {name: getattr(st, name) for name, _ in L.KnnStats._fields_}, nn, _topo_info(info)
+
+
 def block_radius(ctx, rank: int, nranks: int, owned_xyz, gid, r: float, transport=None):
     """RadiusTopology rows of this rank's owned points, in global ids (collective: every rank calls it).  Returns
     (offsets int64 (n + 1), idx int64 (nnz), info) as torch tensors on the context's device; row i equals ctx.radius's

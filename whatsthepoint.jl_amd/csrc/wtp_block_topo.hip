@@ -73,6 +73,7 @@ __host__ __device__ inline unsigned long long tp_mix(unsigned long long z) {
 struct TopoState {
     DevBuf own4, recv, send, span_counts, totals, stats, bm, pc, off, scan_tmp;
     DevBuf lxyz, lgid, opos, lidx, ldist, lcnt, loff, ridx, cnt_own, own_off;
+    DevBuf sdist;           // wtp_block_knn_stats: the owned rows' distances
     bool rad_ready = false; // a wtp_block_radius_offsets call left its rows here for wtp_block_radius_fill
     int64_t rad_n_owned = 0, rad_nnz = 0;
 };
@@ -258,7 +259,7 @@ __global__ __launch_bounds__(256) void tp_knn_rows_kernel(const float4* __restri
         const int64_t i = e / k;
         const int j = (int)(e - i * k);
         const int64_t src = (int64_t)opos[i] * k + j;
-        out_idx[e] = lgid[lidx[src]];
+        if (out_idx) out_idx[e] = lgid[lidx[src]];
         const float d = ldist[src];
         if (out_dist) out_dist[e] = d;
         if (j == k - 1) {
@@ -302,6 +303,8 @@ struct TpCall {
     int64_t* idx_out;
     float* dist_out;
     int64_t* off_out;
+    bool stats = false;   // wtp_block_knn_stats: k >= 2, the rows' ids are not wanted
+    int local_reason = 0; // a check the entry point made on its own arguments failed (tp_reason)
 };
 
 static double hdr_d(int64_t w) { return __builtin_bit_cast(double, w); }
@@ -316,6 +319,9 @@ static const char* tp_reason(int64_t code) {
     case 4: return "k must be >= 1";
     case 5: return "radius must be finite and > 0";
     case 6: return "width must not be NaN";
+    case 7: return "k must be >= 2 (k counts the point itself)";
+    case 8: return "out is NULL";
+    case 9: return "h_const must be finite, coord_radius finite and >= 0";
     default: return "failed its checks";
     }
 }
@@ -333,7 +339,7 @@ static float tp_up(double v) {
 
 static int tp_run(wtp_ctx* ctx, const TpCall& c, wtp_block_topo_info* info) {
     const bool knn = c.k != 0;
-    const char* who = knn ? "wtp_block_knn: " : "wtp_block_radius_offsets: ";
+    const char* who = c.stats ? "wtp_block_knn_stats: " : knn ? "wtp_block_knn: " : "wtp_block_radius_offsets: ";
     if (c.nranks < 1 || c.rank < 0 || c.rank >= c.nranks) return fail(ctx, WTP_ERR_ARG, std::string(who) + "0 <= rank < nranks");
     if (int rcr = transport_ready(ctx, c.rank, c.nranks, who)) return rcr;
     WTP_HIP(ctx, hipSetDevice(ctx->device));
@@ -352,10 +358,11 @@ static int tp_run(wtp_ctx* ctx, const TpCall& c, wtp_block_topo_info* info) {
     int64_t status = 0, reason = 0;
     if (ctx->relax.active || block_session_open(ctx)) status = WTP_ERR_STATE, reason = 1;
     else if (n < 0) status = WTP_ERR_ARG, reason = 3;
-    else if (knn && c.k < 1) status = WTP_ERR_ARG, reason = 4;
+    else if (c.local_reason) status = WTP_ERR_ARG, reason = c.local_reason;
+    else if (knn && c.k < (c.stats ? 2 : 1)) status = WTP_ERR_ARG, reason = c.stats ? 7 : 4;
     else if (!knn && !(c.r > 0 && std::isfinite(c.r))) status = WTP_ERR_ARG, reason = 5;
     else if (std::isnan(c.width)) status = WTP_ERR_ARG, reason = 6;
-    else if (n > 0 && (!c.xyz || !c.gid || !(knn ? (const void*)c.idx_out : (const void*)c.off_out))) status = WTP_ERR_ARG, reason = 2;
+    else if (n > 0 && (!c.xyz || !c.gid || !(c.stats ? (const void*)c.dist_out : knn ? (const void*)c.idx_out : (const void*)c.off_out))) status = WTP_ERR_ARG, reason = 2;
     TpStats hs{};
     if ((rc = ensure(ctx, s->stats, sizeof(TpStats) + 64))) return rc; // (the fingerprint sum sits behind the statistics)
     if (!status && n > 0) {
@@ -681,6 +688,62 @@ WTP_API int wtp_block_knn(wtp_ctx* ctx, int rank, int nranks, const void* d_xyz,
     if (!ctx) return WTP_ERR_ARG;
     TpCall c{rank, nranks, (const float*)d_xyz, d_gid, n_owned, k < 1 ? -1 : k, include_self, 0.0, width, d_idx_out, d_dist_out, nullptr};
     return tp_run(ctx, c, info);
+}
+
+// The sharded metrics: rows as wtp_block_knn's (self included) into an internal buffer, the reductions of wtp_stats.hip on
+// the owned rows, one all-gather of {status, first bad spacing index, partial struct}, merged in rank order on every rank.
+WTP_API int wtp_block_knn_stats(wtp_ctx* ctx, int rank, int nranks, const void* d_xyz, const int64_t* d_gid, int64_t n_owned, int k,
+                                const double* d_h, double h_const, double coord_radius, double width, KnnStats* out,
+                                float* d_nn_out, wtp_block_topo_info* info) {
+    if (!ctx) return WTP_ERR_ARG;
+    const char* who = "wtp_block_knn_stats: ";
+    if (nranks < 1 || rank < 0 || rank >= nranks) return fail(ctx, WTP_ERR_ARG, std::string(who) + "0 <= rank < nranks");
+    const char* why = nullptr;
+    const int has = knn_stats_spacing(d_h, h_const, coord_radius, &why);
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    TopoState* s = ts_of(ctx);
+    const int kk = k < 2 ? -1 : k;
+    int rc;
+    if (n_owned > 0 && kk > 0 && (rc = ensure(ctx, s->sdist, sizeof(float) * (size_t)n_owned * kk))) return rc;
+    TpCall c{rank, nranks, (const float*)d_xyz, d_gid, n_owned, kk, 1, 0.0, width, nullptr, (float*)s->sdist.p, nullptr};
+    c.stats = true;
+    c.local_reason = !out ? 8 : has < 0 ? 9 : 0;
+    if ((rc = tp_run(ctx, c, info))) return rc; // (the same status on every rank)
+    constexpr int kWords = 2 + (int)(sizeof(KnnStats) / 8);
+    static_assert(sizeof(KnnStats) % 8 == 0, "gathered as 8-byte words");
+    int64_t mine[kWords] = {0, -1};
+    KnnStats part = knn_stats_neutral();
+    if (n_owned > 0) {
+        int64_t bad = -1;
+        const int lrc = knn_stats_rows(ctx, s->sdist.p, n_owned, k, WTP_F32, d_h, h_const, has, coord_radius, d_gid, d_nn_out, nullptr,
+                                       &part, &bad);
+        mine[0] = lrc ? lrc : bad >= 0 ? WTP_ERR_ARG : 0;
+        mine[1] = bad;
+    }
+    memcpy(mine + 2, &part, sizeof(part));
+    std::vector<int64_t> all((size_t)nranks * kWords);
+    if ((rc = transport_allgather(ctx, nranks, mine, false, all.data(), kWords, "wtp_block_knn_stats"))) return rc;
+    if (info) info->host_syncs += n_owned > 0 ? 1 : 0;
+    KnnStats g = knn_stats_neutral();
+    int spacing_seen = -1;
+    for (int q = 0; q < nranks; ++q) {
+        const int64_t* w = all.data() + (size_t)q * kWords;
+        if (w[0]) {
+            if (q == rank && w[1] < 0) return (int)w[0]; // (this rank's own failure: its message stands)
+            return fail(ctx, (int)w[0], std::string(who) + "rank " + std::to_string(q) +
+                                           (w[1] >= 0 ? ": h[" + std::to_string(w[1]) + "] is not finite and > 0" : " failed in its reduction"));
+        }
+        KnnStats pq;
+        memcpy(&pq, w + 2, sizeof(pq));
+        if (pq.n > 0) {
+            if (spacing_seen >= 0 && spacing_seen != pq.has_spacing)
+                return fail(ctx, WTP_ERR_ARG, std::string(who) + "ranks disagree on whether there is a spacing");
+            spacing_seen = pq.has_spacing;
+        }
+        knn_stats_merge(g, pq);
+    }
+    *out = g;
+    return WTP_OK;
 }
 
 WTP_API int wtp_block_radius_offsets(wtp_ctx* ctx, int rank, int nranks, const void* d_xyz, const int64_t* d_gid, int64_t n_owned,

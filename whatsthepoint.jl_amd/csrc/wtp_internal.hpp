@@ -26,6 +26,8 @@ template <> struct PtOf<float> { using type = float4; };
 template <> struct PtOf<double> { using type = double4; };
 template <typename T> using Pt = typename PtOf<T>::type;
 
+using KnnStats = struct ::wtp_knn_stats; // (the C name is also the call's: see include/wtp.h)
+
 // One call for both dtypes: f(float{}) for WTP_F32, f(double{}) for WTP_F64; f takes `auto t` and works on T = decltype(t).
 template <typename F> inline auto by_dtype(int dtype, F&& f) { return dtype == WTP_F32 ? f(float{}) : f(double{}); }
 
@@ -493,6 +495,7 @@ struct wtp_ctx {
     wtp::DevBuf stop_state;           // wtp_relax_run_until: {stopped, reason, n_done, last_impr, best_cv} on the device
     const int32_t* stop_dev = nullptr; // its first word while such a run is enqueued, else NULL (kernels then never look)
     wtp::DevBuf scratch;       // misc (relax_get staging, radius rows)
+    wtp::DevBuf kstats;        // wtp_knn_stats: block partials, the result, the first bad spacing index
     wtp::DevBuf diag;          // diagnostic builds only
     wtp::DevBuf ins_in, ins_elems, ins_partial, ins_out; // isinside filter
     wtp::MeshState mesh;
@@ -636,6 +639,19 @@ int launch_pca_normals(wtp_ctx* ctx, const T* d_xyz, int64_t n, int dim, const i
 template <typename T>
 int launch_minplus_batch(wtp_ctx* ctx, const int32_t* d_rows, const T* d_dist, int64_t n, int k, double g, double tol,
                          T* d_h0, T* d_h1, int first, int sweeps, unsigned long long* d_state);
+// the metrics' reductions over the distance rows (wtp_stats.hip): result and first bad spacing index land in d_tmp
+size_t knn_stats_tmp_bytes(int64_t n);
+template <typename T>
+int launch_knn_stats(wtp_ctx* ctx, const T* d_dist, int64_t n, int k, const double* d_h, double h_const, int has_spacing,
+                     double coord_radius, const int64_t* d_gid, T* d_nn_out, double* d_mean_out, void* d_tmp,
+                     const KnnStats** d_result_out, const unsigned long long** d_bad_out);
+// wtp_topology.hip: the reduction of device rows into a host struct, shared with the sharded call (wtp_block_topo.hip)
+int knn_stats_spacing(const void* h, double h_const, double coord_radius, const char** why);
+int knn_stats_rows(wtp_ctx* ctx, const void* d_dist, int64_t n, int k, int dtype, const double* d_h, double h_const,
+                   int has_spacing, double coord_radius, const int64_t* d_gid, void* d_nn_out, double* d_mean_out,
+                   KnnStats* out, int64_t* bad_out);
+void knn_stats_merge(KnnStats& a, const KnnStats& b); // a <- a merged with b (host; the kernels' own rule)
+KnnStats knn_stats_neutral();
 // wall rule of the octree method (wtp_mesh.hip)
 template <typename TP>
 int launch_mesh_constrain(wtp_ctx* ctx, const Pt<TP>* old, Pt<TP>* cur, int64_t n, int64_t n_fixed, double offset,

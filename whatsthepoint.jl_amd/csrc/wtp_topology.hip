@@ -1,6 +1,7 @@
 // wtp_topology.hip — the topology calls of include/wtp.h: the call sequences that replace _build_knn_neighbors /
 // _build_radius_neighbors (src/topology.jl:79-97) in fp32 and fp64, and the consumers of their rows.
 #include <cmath>
+#include <cstring>
 
 #include "wtp_internal.hpp"
 
@@ -301,6 +302,104 @@ WTP_API int wtp_gradient_limit(wtp_ctx* ctx, const void* centers, int64_t n, int
     if (sweeps_out) *sweeps_out = applied;
     WTP_HIP(ctx, hipMemcpyAsync(h_out, b + ((applied & 1) ? o1 : 0), ts * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     return sync(ctx);
+}
+
+// ---- the metrics' reductions (wtp_stats.hip) ----------------------------------------------------
+// has_spacing of a call's (h, h_const, coord_radius), or -1 with *why set
+int wtp::knn_stats_spacing(const void* h, double h_const, double coord_radius, const char** why) {
+    if (!h && (std::isnan(h_const) || (h_const > 0 && !std::isfinite(h_const)))) {
+        *why = "h_const must be finite";
+        return -1;
+    }
+    const int has = h || h_const > 0 ? 1 : 0;
+    if (has && !(std::isfinite(coord_radius) && coord_radius >= 0)) {
+        *why = "coord_radius must be finite and >= 0";
+        return -1;
+    }
+    return has;
+}
+
+// n x k distance rows in device memory -> *out on the host; *bad_out: the first index whose spacing is not finite and > 0,
+// or -1 (then *out is not meaningful: the caller reports it)
+int wtp::knn_stats_rows(wtp_ctx* ctx, const void* d_dist, int64_t n, int k, int dtype, const double* d_h, double h_const,
+                        int has_spacing, double coord_radius, const int64_t* d_gid, void* d_nn_out, double* d_mean_out,
+                        KnnStats* out, int64_t* bad_out) {
+    int rc;
+    if ((rc = ensure(ctx, ctx->kstats, knn_stats_tmp_bytes(n)))) return rc;
+    if ((rc = ensure_pinned(ctx, 256))) return rc;
+    const KnnStats* d_res = nullptr;
+    const unsigned long long* d_bad = nullptr;
+    int sp = span_begin(ctx, 2);
+    rc = by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_knn_stats<T>(ctx, (const T*)d_dist, n, k, d_h, h_const, has_spacing, coord_radius, d_gid, (T*)d_nn_out,
+                                   d_mean_out, ctx->kstats.p, &d_res, &d_bad);
+    });
+    span_end(ctx, sp);
+    if (rc) return rc;
+    // (the result and the index behind it are adjacent: one copy)
+    WTP_HIP(ctx, hipMemcpyAsync(ctx->host_pinned, d_res, sizeof(KnnStats) + 8, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = sync(ctx))) return rc;
+    memcpy(out, ctx->host_pinned, sizeof(KnnStats));
+    unsigned long long bad;
+    memcpy(&bad, (const char*)ctx->host_pinned + sizeof(KnnStats), 8);
+    *bad_out = bad == ~0ull ? -1 : (int64_t)bad;
+    return WTP_OK;
+}
+
+static int knn_stats_call(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype, int k, const double* h, double h_const,
+                          double coord_radius, KnnStats* out, void* nn_out, double* mean_out, bool dev) {
+    int rc = check_cloud(ctx, xyz, n, dim, dtype);
+    if (rc) return rc;
+    if (k < 2) return fail(ctx, WTP_ERR_ARG, "k must be >= 2 (k counts the point itself: a row needs one neighbour)");
+    if ((rc = check_k(ctx, n, k, 1))) return rc;
+    if ((rc = check_idle(ctx))) return rc;
+    if (!out) return fail(ctx, WTP_ERR_ARG, "out is NULL");
+    const char* why = nullptr;
+    const int has = knn_stats_spacing(h, h_const, coord_radius, &why);
+    if (has < 0) return fail(ctx, WTP_ERR_ARG, why);
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t ts = tsize(dtype);
+    if (dev) {
+        if ((rc = ensure(ctx, ctx->idx_out, sizeof(int32_t) * (size_t)n * k))) return rc;
+        if ((rc = ensure(ctx, ctx->dist_out, ts * (size_t)n * k))) return rc;
+        rc = knn_on_device(ctx, xyz, n, dim, dtype, k, 1, (int32_t*)ctx->idx_out.p, ctx->dist_out.p);
+    } else {
+        rc = knn_rows_on_device(ctx, xyz, n, dim, dtype, k, 1, true);
+    }
+    if (rc) return rc;
+    const double* d_h = h;
+    void* d_nn = nn_out;
+    double* d_mean = mean_out;
+    if (!dev) { // staging of the host arrays: [h | mean | nn]
+        const size_t o1 = sizeof(double) * (size_t)n;
+        if ((rc = ensure(ctx, ctx->scratch, 2 * o1 + ts * (size_t)n))) return rc;
+        char* b = (char*)ctx->scratch.p;
+        if (h) WTP_HIP(ctx, hipMemcpyAsync(b, h, o1, hipMemcpyHostToDevice, ctx->stream));
+        d_h = h ? (const double*)b : nullptr;
+        d_mean = mean_out ? (double*)(b + o1) : nullptr;
+        d_nn = nn_out ? b + 2 * o1 : nullptr;
+    }
+    int64_t bad = -1;
+    if ((rc = knn_stats_rows(ctx, ctx->dist_out.p, n, k, dtype, d_h, h_const, has, coord_radius, nullptr, d_nn, d_mean, out, &bad)))
+        return rc;
+    if (bad >= 0) return fail(ctx, WTP_ERR_ARG, "h[" + std::to_string(bad) + "] is not finite and > 0");
+    if (!dev && (nn_out || mean_out)) {
+        if (nn_out) WTP_HIP(ctx, hipMemcpyAsync(nn_out, d_nn, ts * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        if (mean_out) WTP_HIP(ctx, hipMemcpyAsync(mean_out, d_mean, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        return sync(ctx);
+    }
+    return WTP_OK;
+}
+
+WTP_API int wtp_knn_stats(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype, int k, const double* h, double h_const,
+                          double coord_radius, KnnStats* out, void* nn_out, double* mean_out) {
+    return knn_stats_call(ctx, xyz, n, dim, dtype, k, h, h_const, coord_radius, out, nn_out, mean_out, false);
+}
+
+WTP_API int wtp_knn_stats_dev(wtp_ctx* ctx, const void* d_xyz, int64_t n, int dim, int dtype, int k, const double* d_h,
+                              double h_const, double coord_radius, KnnStats* out, void* d_nn_out, double* d_mean_out) {
+    return knn_stats_call(ctx, d_xyz, n, dim, dtype, k, d_h, h_const, coord_radius, out, d_nn_out, d_mean_out, true);
 }
 
 // ---- RadiusTopology ------------------------------------------------------------------------------

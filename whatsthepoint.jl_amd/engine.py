@@ -198,6 +198,47 @@ class Context:
         L.check(self._h, rc)
         return out, sw.value
 
+    def knn_stats(self, xyz, k: int, h=None, coord_radius: float = 1.4, return_nn: bool = False, return_mean: bool = False):
+        """The sums behind metrics / spacing_metrics / spacing_fidelity_metrics (src/metrics.jl:19-129), reduced on the
+        device from the k-NN distance rows (wtp_knn_stats): a dict of the struct's fields.  k counts the point itself
+        (KnearestSearch(cloud, k)), 2 <= k <= n.  h: None, one positive number, or n values (converted to float64).
+        return_nn / return_mean add "nn" (n values of the cloud's dtype: the nearest-neighbour distances) and "mean"
+        (n float64: the per-point mean distances); nothing else of size n, and never the (n, k) matrices, is copied."""
+        xyz = _cloud(xyz)
+        n, dim = xyz.shape
+        hv, hc = None, 0.0
+        if h is not None:
+            if np.ndim(h) == 0:
+                hc = float(h)
+                if not hc > 0:
+                    raise L.WtpArgumentError("a constant spacing must be > 0")
+            else:
+                hv = np.ascontiguousarray(h, dtype=np.float64).reshape(-1)
+                if hv.shape != (n,):
+                    raise L.WtpArgumentError("h needs one value per point")
+        st = L.KnnStats()
+        nn = np.empty(n, dtype=xyz.dtype) if return_nn else None
+        mean = np.empty(n, dtype=np.float64) if return_mean else None
+        rc = self._lib.wtp_knn_stats(self._h, _vp(xyz), n, dim, _dtype_code(xyz.dtype), int(k), _vp(hv), hc, float(coord_radius),
+                                     C.byref(st), _vp(nn), _vp(mean))
+        L.check(self._h, rc)
+        out = {name: getattr(st, name) for name, _ in L.KnnStats._fields_}
+        if return_nn:
+            out["nn"] = nn
+        if return_mean:
+            out["mean"] = mean
+        return out
+
+    def knn_stats_dev(self, d_xyz_ptr: int, n: int, dim: int, dtype, k: int, d_h_ptr: int = 0, h_const: float = 0.0,
+                      coord_radius: float = 1.4, d_nn_ptr: int = 0, d_mean_ptr: int = 0):
+        """wtp_knn_stats_dev: the same over device arrays given as addresses (0 = absent); returns the struct's dict."""
+        st = L.KnnStats()
+        p = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        rc = self._lib.wtp_knn_stats_dev(self._h, C.c_void_p(d_xyz_ptr), n, dim, _dtype_code(dtype), int(k), p(d_h_ptr),
+                                         float(h_const), float(coord_radius), C.byref(st), p(d_nn_ptr), p(d_mean_ptr))
+        L.check(self._h, rc)
+        return {name: getattr(st, name) for name, _ in L.KnnStats._fields_}
+
     # ---- triangle-mesh geometry index (octree method of repel; src/octree/triangle_octree.jl) -----
     def mesh_set(self, vertices, triangles):
         """vertices (nv, 3) float32/float64 = the index's machine type; triangles (nt, 3) 0-based."""
