@@ -351,6 +351,51 @@ int wtp_knn_stats(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype, 
 int wtp_knn_stats_dev(wtp_ctx* ctx, const void* d_xyz, int64_t n, int dim, int dtype, int k, const double* d_h,
                       double h_const, double coord_radius, struct wtp_knn_stats* out, void* d_nn_out, double* d_mean_out);
 
+/* The graph part of orient_normals! (src/normals.jl:75-161) and split_surface! (src/surface_operations.jl:58-94), on the
+ * device: the search of KNearestSearch(points, k) (k counts the point itself, 1 <= k <= n), whose rows stay where the
+ * search left them, then rounds of component merging over those rows.
+ *   Edge set.  As the reference builds it: for every row, src = slot 0 and dst = slots 1..k-1.  Slot 0 is the point
+ * itself or the coincident twin that sorts first; the row is followed, the row's own index is not substituted.  The
+ * graph is undirected and simple: an edge exists if either row names it (both directions give the same weight bits).
+ *   wtp_orient_normals.  Weight w = (1 - |((nx nx' + ny ny') + nz nz')|) + 100 eps(T) in the cloud's type T, term by
+ * term; weights compare as IEEE values (w < 0 is legal: normals may be a little longer than 1).  The forest is the
+ * unique minimum spanning forest under the total order (w, a, b), a < b the endpoint ids, which is what Kruskal over the
+ * edges sorted stably by w after de-duplication by a n + b gives.  The start is the first index that attains the largest
+ * last coordinate; it is flipped if its normal's last component is < 0.  Every other vertex of the start's component is
+ * flipped iff the number of tree edges (u, v) with n_u . n_v < 0 (input normals; a dot of exactly 0 is not negative) on
+ * its path to the start is odd, XOR the start's own flip: what the reference's walk does, in any walk order.  Vertices
+ * of other components come back untouched, bit for bit.  k = 1 or n = 1: no edges, only the start rule.  The result is
+ * unique, uses no floating-point atomics and does not depend on arrival order: two calls return the same bits.
+ *   mst_out (or NULL): room for n - 1 pairs {a, b}, a < b; the first n - n_components pairs are the forest's edges, in
+ * any order (sort them to compare); the rest is not written.
+ *   wtp_normal_components.  Keeps an edge iff |_angle(n_src, n_dst)| < angle, _angle as in src/utils.jl:18-23 evaluated
+ * in double from the normals converted to double (2-D: atan2(cross, dot), signed; 3-D: atan2(|cross|, dot)).
+ * label_out[i] is the smallest id in i's component of the kept edges.  The device's atan2 may differ from a host's in the
+ * last ulps: only edges whose angle is within 1e-12 rad of the threshold can be decided differently.
+ *   A normal with a non-finite component is WTP_ERR_ARG naming the first such index (checked on the device; nothing has
+ * been written then).  Like every call that runs the k-NN search these calls end a pending wtp_radius_count /
+ * wtp_radius_fill pair; WTP_ERR_STATE while a relax or block session is open.  Termination is a device flag read back
+ * once per batch of 4 rounds, the last of which only finds nothing left to merge: the graph part synchronises
+ * ceil((rounds + 1) / 4) + 1 times (twice for k = 1), which info (or NULL) reports with the rounds.  */
+typedef struct wtp_normal_graph_info {
+    int64_t n_edges;       /* distinct undirected edges of the row graph                                        */
+    int64_t n_components;  /* connected components of that graph (orient) / of the kept edges (components)      */
+    int64_t n_reached;     /* orient: vertices in the start's component                                         */
+    int64_t n_flipped;     /* orient: normals whose sign changed                                                */
+    int64_t start;         /* orient: argmax of the last coordinate, smallest index among equals (else -1)      */
+    int32_t rounds;        /* Boruvka / hooking rounds that merged something                                    */
+    int32_t host_syncs;    /* host synchronisations of the graph part (the search's own are not counted)        */
+} wtp_normal_graph_info;
+/* xyz: host n x dim of dtype; normals_inout: host n x dim of dtype, oriented in place; mst_out: host or NULL.  */
+int wtp_orient_normals(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype, int k, void* normals_inout,
+                       int32_t* mst_out, wtp_normal_graph_info* info);
+/* The same with d_xyz, d_normals_inout and d_mst_out in device memory; info stays a host struct.  */
+int wtp_orient_normals_dev(wtp_ctx* ctx, const void* d_xyz, int64_t n, int dim, int dtype, int k, void* d_normals_inout,
+                           int32_t* d_mst_out, wtp_normal_graph_info* info);
+/* xyz, normals: host n x dim of dtype (normals are not changed); label_out: n host int32.  */
+int wtp_normal_components(wtp_ctx* ctx, const void* xyz, const void* normals, int64_t n, int dim, int dtype, int k,
+                          double angle, int32_t* label_out, wtp_normal_graph_info* info);
+
 /* ---- sharded sessions (no counterpart in the reference) --------------
  * One rank sweeps one spatial slab.  Its session's fixed head is the ghost layer received
  * from the neighbouring ranks, its movable tail the points it owns.  The two calls below

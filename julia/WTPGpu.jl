@@ -96,6 +96,36 @@ function metrics(cloud; k::Int = 20)
             separation = st.nn_min, fill = st.nn_max, mesh_ratio = st.nn_min > 0 ? st.nn_max / st.nn_min : Inf)
 end
 
+# ---- src/normals.jl:75-161 and src/surface_operations.jl:58-94: the graph part on the device ------------------------
+# (include/wtp.h: wtp_orient_normals, wtp_normal_components)
+mutable struct NormalGraphInfo
+    n_edges::Int64; n_components::Int64; n_reached::Int64; n_flipped::Int64; start::Int64
+    rounds::Int32; host_syncs::Int32
+    NormalGraphInfo() = new()
+end
+
+# body of orient_normals!(normals, points; k): normals is a Vector{SVector{D,T}} of the points' eltype, oriented in place
+function orient_normals!(normals, points; k::Int = 5)
+    xs = raw(points); D = length(first(xs)); T = eltype(first(xs)); n = length(xs)
+    info = NormalGraphInfo()
+    check(context(), ccall((:wtp_orient_normals, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cint, Cint, Cint, Ptr{Cvoid}, Ptr{Int32}, Ref{NormalGraphInfo}),
+        context(), xs, n, D, dtype(T), min(k, n), normals, C_NULL, info))
+    info.start += 1
+    return info
+end
+
+# the graph part of split_surface!: 1-based labels (the smallest vertex of each component of the edges kept by `angle`)
+function normal_components(points, normals, k::Int, angle)
+    xs = raw(points); D = length(first(xs)); T = eltype(first(xs)); n = length(xs)
+    labels = Vector{Int32}(undef, n)
+    info = NormalGraphInfo()
+    check(context(), ccall((:wtp_normal_components, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cint, Cint, Cint, Float64, Ptr{Int32}, Ref{NormalGraphInfo}),
+        context(), xs, normals, n, D, dtype(T), min(k, n), Float64(ustrip(angle)), labels, info))
+    return Int.(labels) .+ 1, info
+end
+
 # ---- src/topology.jl:91-97 -------------------------------------------------------------------------
 function build_radius_neighbors(points, radius)
     r = ustrip(WhatsThePoint._get_radius(radius, points))

@@ -72,6 +72,12 @@ class KnnStats(C.Structure):
                 ("sum_u", C.c_double), ("ssd_u", C.c_double), ("sum_coord", C.c_int64)]
 
 
+class NormalGraphInfo(C.Structure):
+    """wtp_normal_graph_info: what wtp_orient_normals / wtp_normal_components report about the row graph."""
+    _fields_ = [("n_edges", C.c_int64), ("n_components", C.c_int64), ("n_reached", C.c_int64), ("n_flipped", C.c_int64),
+                ("start", C.c_int64), ("rounds", C.c_int32), ("host_syncs", C.c_int32)]
+
+
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                           C.POINTER(C.c_void_p), C.POINTER(C.c_int64))
@@ -113,6 +119,9 @@ SIGNATURES = {
     "wtp_pca_normals": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp]),
     "wtp_knn_stats": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _d, _d, C.POINTER(KnnStats), _vp, _vp]),
     "wtp_knn_stats_dev": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _d, _d, C.POINTER(KnnStats), _vp, _vp]),
+    "wtp_orient_normals": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, C.POINTER(NormalGraphInfo)]),
+    "wtp_orient_normals_dev": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, C.POINTER(NormalGraphInfo)]),
+    "wtp_normal_components": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _d, _vp, C.POINTER(NormalGraphInfo)]),
     "wtp_gradient_limit": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _d, _d, _i, _vp, C.POINTER(_i)]),
     "wtp_mesh_set": (_i, [_vp, _vp, _i64, _vp, _i64, _i]),
     "wtp_mesh_clear": (_i, [_vp]),

@@ -496,6 +496,7 @@ struct wtp_ctx {
     const int32_t* stop_dev = nullptr; // its first word while such a run is enqueued, else NULL (kernels then never look)
     wtp::DevBuf scratch;       // misc (relax_get staging, radius rows)
     wtp::DevBuf kstats;        // wtp_knn_stats: block partials, the result, the first bad spacing index
+    wtp::DevBuf ngraph;        // wtp_orient_normals / wtp_normal_components: components, per-component minima, control block
     wtp::DevBuf diag;          // diagnostic builds only
     wtp::DevBuf ins_in, ins_elems, ins_partial, ins_out; // isinside filter
     wtp::MeshState mesh;
@@ -652,6 +653,20 @@ int knn_stats_rows(wtp_ctx* ctx, const void* d_dist, int64_t n, int k, int dtype
                    KnnStats* out, int64_t* bad_out);
 void knn_stats_merge(KnnStats& a, const KnnStats& b); // a <- a merged with b (host; the kernels' own rule)
 KnnStats knn_stats_neutral();
+// the graph part of orient_normals! / split_surface! (wtp_normal_graph.hip): prep, `rounds` rounds from round `first`
+// (components in bufs[r & 1] before round r), and the flips / labels with the counts; d_ctl: normal_graph_ctl_bytes()
+size_t normal_graph_ctl_bytes();
+template <typename T>
+int launch_normal_graph_prep(wtp_ctx* ctx, const T* d_xyz, const T* d_nrm, const int32_t* d_rows, int64_t n, int dim, int k,
+                             int orient, double angle, uint32_t* d_cur, uint8_t* d_keep, unsigned long long* d_ctl);
+template <typename T>
+int launch_normal_graph_rounds(wtp_ctx* ctx, const T* d_nrm, const int32_t* d_rows, int64_t n, int dim, int k, int orient,
+                               const uint8_t* d_keep, uint32_t* d_buf0, uint32_t* d_buf1, unsigned long long* d_best_w,
+                               unsigned long long* d_best_e, int32_t* d_mst_out, int first, int rounds,
+                               unsigned long long* d_ctl);
+template <typename T>
+int launch_normal_graph_apply(wtp_ctx* ctx, T* d_nrm, int64_t n, int dim, const uint32_t* d_cur, int32_t* d_label_out,
+                              unsigned long long* d_ctl);
 // wall rule of the octree method (wtp_mesh.hip)
 template <typename TP>
 int launch_mesh_constrain(wtp_ctx* ctx, const Pt<TP>* old, Pt<TP>* cur, int64_t n, int64_t n_fixed, double offset,

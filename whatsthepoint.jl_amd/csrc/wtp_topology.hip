@@ -402,6 +402,125 @@ WTP_API int wtp_knn_stats_dev(wtp_ctx* ctx, const void* d_xyz, int64_t n, int di
     return knn_stats_call(ctx, d_xyz, n, dim, dtype, k, d_h, h_const, coord_radius, out, d_nn_out, d_mean_out, true);
 }
 
+// ---- the graph part of orient_normals! / split_surface! (wtp_normal_graph.hip) ---------------------
+// orient != 0: wtp_orient_normals (normals changed in place, mst_out or NULL); else wtp_normal_components (label_out)
+static int normal_graph_call(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype, int k, void* normals, int32_t* mst_out,
+                             double angle, int32_t* label_out, wtp_normal_graph_info* info, bool orient, bool dev) {
+    int rc = check_cloud(ctx, xyz, n, dim, dtype);
+    if (rc) return rc;
+    if ((rc = check_k(ctx, n, k, 1))) return rc;
+    if ((rc = check_idle(ctx))) return rc;
+    if (!normals) return fail(ctx, WTP_ERR_ARG, "normals is NULL");
+    if (!orient && !label_out) return fail(ctx, WTP_ERR_ARG, "label_out is NULL");
+    if (!orient && std::isnan(angle)) return fail(ctx, WTP_ERR_ARG, "angle is NaN");
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t ts = tsize(dtype);
+    if (dev) {
+        if ((rc = ensure(ctx, ctx->idx_out, sizeof(int32_t) * (size_t)n * k))) return rc;
+        rc = knn_on_device(ctx, xyz, n, dim, dtype, k, 1, (int32_t*)ctx->idx_out.p, nullptr);
+    } else {
+        rc = knn_rows_on_device(ctx, xyz, n, dim, dtype, k, 1, false);
+    }
+    if (rc) return rc;
+    const int64_t syncs0 = ctx->n_syncs; // (the graph part's: the search's own are not counted)
+    const void* d_xyz = dev ? xyz : ctx->raw_in.p;
+    const int32_t* d_rows = (const int32_t*)ctx->idx_out.p;
+    // staging of the host arrays: [normals | mst or labels]
+    const size_t nb = (ts * (size_t)n * dim + 255) / 256 * 256;
+    const size_t ob = orient ? sizeof(int32_t) * 2 * (size_t)(n - 1) : sizeof(int32_t) * (size_t)n;
+    void* d_nrm = normals;
+    int32_t* d_out = orient ? mst_out : label_out;
+    if (!dev) {
+        if ((rc = ensure(ctx, ctx->scratch, nb + ob))) return rc;
+        d_nrm = ctx->scratch.p;
+        d_out = (orient && !mst_out) ? nullptr : (int32_t*)((char*)ctx->scratch.p + nb);
+        WTP_HIP(ctx, hipMemcpyAsync(d_nrm, normals, ts * (size_t)n * dim, hipMemcpyHostToDevice, ctx->stream));
+    }
+    // [control block | components x 2 | per-component minima x 2 | kept entries (split)]
+    const size_t cb = normal_graph_ctl_bytes();
+    const size_t vb = (sizeof(uint32_t) * (size_t)n + 255) / 256 * 256, mb = sizeof(unsigned long long) * (size_t)n;
+    if ((rc = ensure(ctx, ctx->ngraph, cb + 2 * vb + 2 * mb + (orient ? 0 : (size_t)n * (k - 1))))) return rc;
+    char* g = (char*)ctx->ngraph.p;
+    unsigned long long* d_ctl = (unsigned long long*)g;
+    uint32_t* bufs[2] = {(uint32_t*)(g + cb), (uint32_t*)(g + cb + vb)};
+    unsigned long long* d_best_w = (unsigned long long*)(g + cb + 2 * vb);
+    unsigned long long* d_best_e = d_best_w + n;
+    uint8_t* d_keep = (uint8_t*)(d_best_e + n);
+    if ((rc = ensure_pinned(ctx, cb))) return rc;
+    unsigned long long* h = (unsigned long long*)ctx->host_pinned;
+    int sp = span_begin(ctx, 2);
+    rc = by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_normal_graph_prep<T>(ctx, (const T*)d_xyz, (const T*)d_nrm, d_rows, n, dim, k, orient, angle, bufs[0], d_keep,
+                                           d_ctl);
+    });
+    if (rc) return rc;
+    int enq = 0; // rounds enqueued
+    h[0] = k > 1 ? 0 : 1;
+    while (!h[0]) { // batches: one read-back per 4 rounds
+        rc = by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            return launch_normal_graph_rounds<T>(ctx, (const T*)d_nrm, d_rows, n, dim, k, orient, d_keep, bufs[0], bufs[1], d_best_w,
+                                                 d_best_e, orient ? d_out : nullptr, enq, 4, d_ctl);
+        });
+        if (rc) return rc;
+        enq += 4;
+        WTP_HIP(ctx, hipMemcpyAsync(h, d_ctl, 128, hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = sync(ctx))) return rc;
+        if (h[4] != ~0ull) break;
+    }
+    if (k == 1) { // no rounds: the control block is read here for the normals' check
+        WTP_HIP(ctx, hipMemcpyAsync(h, d_ctl, 128, hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = sync(ctx))) return rc;
+    }
+    if (h[4] != ~0ull) { // (found before anything was written)
+        span_end(ctx, sp);
+        return fail(ctx, WTP_ERR_ARG, "normals[" + std::to_string((long long)h[4]) + "] has a non-finite component");
+    }
+    rc = by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_normal_graph_apply<T>(ctx, (T*)d_nrm, n, dim, bufs[enq & 1], orient ? nullptr : d_out, d_ctl);
+    });
+    span_end(ctx, sp);
+    if (rc) return rc;
+    WTP_HIP(ctx, hipMemcpyAsync(h, d_ctl, 128, hipMemcpyDeviceToHost, ctx->stream));
+    if (!dev) {
+        if (orient) {
+            WTP_HIP(ctx, hipMemcpyAsync(normals, d_nrm, ts * (size_t)n * dim, hipMemcpyDeviceToHost, ctx->stream));
+            if (mst_out && n > 1)
+                WTP_HIP(ctx, hipMemcpyAsync(mst_out, d_out, sizeof(int32_t) * 2 * (size_t)(n - 1), hipMemcpyDeviceToHost, ctx->stream));
+        } else {
+            WTP_HIP(ctx, hipMemcpyAsync(label_out, d_out, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        }
+    }
+    if ((rc = sync(ctx))) return rc;
+    if (info) {
+        info->n_edges = (int64_t)h[11];
+        info->n_components = (int64_t)h[8];
+        info->n_reached = orient ? (int64_t)h[9] : 0;
+        info->n_flipped = orient ? (int64_t)h[10] : 0;
+        info->start = orient ? (int64_t)h[6] : -1;
+        info->rounds = (int32_t)h[1];
+        info->host_syncs = (int32_t)(ctx->n_syncs - syncs0);
+    }
+    return WTP_OK;
+}
+
+WTP_API int wtp_orient_normals(wtp_ctx* ctx, const void* xyz, int64_t n, int dim, int dtype, int k, void* normals_inout,
+                               int32_t* mst_out, wtp_normal_graph_info* info) {
+    return normal_graph_call(ctx, xyz, n, dim, dtype, k, normals_inout, mst_out, 0.0, nullptr, info, true, false);
+}
+
+WTP_API int wtp_orient_normals_dev(wtp_ctx* ctx, const void* d_xyz, int64_t n, int dim, int dtype, int k, void* d_normals_inout,
+                                   int32_t* d_mst_out, wtp_normal_graph_info* info) {
+    return normal_graph_call(ctx, d_xyz, n, dim, dtype, k, d_normals_inout, d_mst_out, 0.0, nullptr, info, true, true);
+}
+
+WTP_API int wtp_normal_components(wtp_ctx* ctx, const void* xyz, const void* normals, int64_t n, int dim, int dtype, int k,
+                                  double angle, int32_t* label_out, wtp_normal_graph_info* info) {
+    return normal_graph_call(ctx, xyz, n, dim, dtype, k, (void*)normals, nullptr, angle, label_out, info, false, false);
+}
+
 // ---- RadiusTopology ------------------------------------------------------------------------------
 template <typename T> static int radius_count_t(wtp_ctx* ctx, int64_t n, int dim, double r, int32_t* d_counts) {
     int rc;

@@ -239,6 +239,59 @@ class Context:
         L.check(self._h, rc)
         return {name: getattr(st, name) for name, _ in L.KnnStats._fields_}
 
+    @staticmethod
+    def _graph_info(info):
+        return {name: int(getattr(info, name)) for name, _ in L.NormalGraphInfo._fields_}
+
+    def _cloud_and_normals(self, points, normals):
+        xyz = _cloud(points)
+        nrm = np.ascontiguousarray(normals, dtype=xyz.dtype)
+        if nrm.shape != xyz.shape:
+            raise L.WtpArgumentError("normals need the shape of the points")
+        return xyz, nrm
+
+    def orient_normals(self, points, normals, k: int, return_tree: bool = False):
+        """The graph part of orient_normals! (src/normals.jl:75-161) on the device (wtp_orient_normals): returns
+        (oriented normals as a new (n, dim) array of the cloud's dtype, info dict), with return_tree also the
+        (n - n_components, 2) int32 edges {a < b} of the minimum spanning forest, sorted.  k counts the point itself,
+        1 <= k <= n.  The rows never leave the device."""
+        xyz, nrm = self._cloud_and_normals(points, normals)
+        out = nrm.copy()
+        n, dim = xyz.shape
+        mst = np.empty((max(n - 1, 0), 2), dtype=np.int32) if return_tree else None
+        info = L.NormalGraphInfo()
+        rc = self._lib.wtp_orient_normals(self._h, _vp(xyz), n, dim, _dtype_code(xyz.dtype), int(k), _vp(out), _vp(mst),
+                                          C.byref(info))
+        L.check(self._h, rc)
+        d = self._graph_info(info)
+        if not return_tree:
+            return out, d
+        mst = mst[: n - d["n_components"]]
+        return out, d, mst[np.lexsort((mst[:, 1], mst[:, 0]))]
+
+    def orient_normals_dev(self, d_xyz_ptr: int, n: int, dim: int, dtype, k: int, d_normals_ptr: int, d_mst_ptr: int = 0):
+        """wtp_orient_normals_dev: the same over device arrays given as addresses (d_mst_ptr 0 = absent); the normals
+        are oriented in place, the info dict is returned."""
+        info = L.NormalGraphInfo()
+        rc = self._lib.wtp_orient_normals_dev(self._h, C.c_void_p(d_xyz_ptr), n, dim, _dtype_code(dtype), int(k),
+                                              C.c_void_p(d_normals_ptr), C.c_void_p(d_mst_ptr) if d_mst_ptr else None,
+                                              C.byref(info))
+        L.check(self._h, rc)
+        return self._graph_info(info)
+
+    def normal_components(self, points, normals, k: int, angle: float):
+        """The graph part of split_surface! (src/surface_operations.jl:58-94) on the device (wtp_normal_components):
+        (labels, info dict); labels[i] is the smallest id in i's component of the row edges whose normals differ by
+        less than `angle` radians."""
+        xyz, nrm = self._cloud_and_normals(points, normals)
+        n, dim = xyz.shape
+        label = np.empty(n, dtype=np.int32)
+        info = L.NormalGraphInfo()
+        rc = self._lib.wtp_normal_components(self._h, _vp(xyz), _vp(nrm), n, dim, _dtype_code(xyz.dtype), int(k), float(angle),
+                                             _vp(label), C.byref(info))
+        L.check(self._h, rc)
+        return label, self._graph_info(info)
+
     # ---- triangle-mesh geometry index (octree method of repel; src/octree/triangle_octree.jl) -----
     def mesh_set(self, vertices, triangles):
         """vertices (nv, 3) float32/float64 = the index's machine type; triangles (nt, 3) 0-based."""

@@ -2,10 +2,12 @@
 the k-NN rows.
 
 `compute_normals` / `update_normals` run on the GPU end to end (k-NN rows + per-point PCA,
-csrc/wtp_consumers.hip).  `orient_normals` and `split_surface` take their k-NN rows from the device and
-do the graph part — a minimum spanning tree walk, connected components — on the calling thread, where
-the reference does it too (Graphs.jl `kruskal_mst`, `connected_components`; "TODO below is slow",
-src/normals.jl:95)."""
+csrc/wtp_consumers.hip).  `orient_normals` and `split_surface` do too by default (`graph="device"`): the
+minimum spanning forest with its sign propagation and the connected components are built from the rows
+where the search left them (csrc/wtp_normal_graph.hip; include/wtp.h: wtp_orient_normals,
+wtp_normal_components).  `graph="host"` fetches the rows and does the graph part on the calling thread,
+where the reference does it too (Graphs.jl `kruskal_mst`, `connected_components`; "TODO below is slow",
+src/normals.jl:95): the executable description of what the kernels compute."""
 from __future__ import annotations
 
 import numpy as np
@@ -49,22 +51,33 @@ def _rows(p, k, ctx):
     return (ctx or default_context()).knn(np.ascontiguousarray(p), k, include_self=True)
 
 
-def orient_normals(normals, points=None, k: int = 5, ctx=None):
+def _graph_mode(graph):
+    if graph not in ("device", "host"):
+        raise ValueError(f'graph must be "device" or "host", not {graph!r}')
+    return graph == "device"
+
+
+def orient_normals(normals, points=None, k: int = 5, ctx=None, graph: str = "device"):
     """orient_normals!(normals, points; k) (src/normals.jl:79-147), in place: minimum spanning tree of the
     k-NN graph weighted by 1 - |n_i . n_j|, the highest point (last coordinate) made to face up, signs
-    propagated along the tree.  Accepts a PointSurface / PointCloud as the only argument, too."""
+    propagated along the tree.  Accepts a PointSurface / PointCloud as the only argument, too.
+    graph="device": tree and signs on the GPU (wtp_orient_normals), in the points' dtype; "host": here."""
+    device = _graph_mode(graph)
     if points is None and isinstance(normals, PointCloud):
         for s in normals.boundary.surfaces.values():
-            orient_normals(s, k=k, ctx=ctx)
+            orient_normals(s, k=k, ctx=ctx, graph=graph)
         return None
     if points is None and isinstance(normals, PointSurface):
         surf = normals
-        orient_normals(surf.normals, surf.points(), k=k, ctx=ctx)
+        orient_normals(surf.normals, surf.points(), k=k, ctx=ctx, graph=graph)
         return None
     p = np.ascontiguousarray(_pts(points))
     nrm = normals
     n = len(p)
     k = min(int(k), n)
+    if device:
+        nrm[...] = (ctx or default_context()).orient_normals(p, nrm, k)[0]
+        return None
     rows = _rows(p, k, ctx)
     src = np.repeat(rows[:, 0], k - 1).astype(np.int64)        # n[1] of the reference (the query itself)
     dst = rows[:, 1:].reshape(-1).astype(np.int64)
@@ -133,25 +146,8 @@ def combine_surfaces(cloud, *surfs):
     return None
 
 
-def split_surface(cloud, angle: float, target=None, k: int = 10, ctx=None):
-    """split_surface!(cloud|boundary, [target], angle; k) (src/surface_operations.jl:33-94): splits a surface
-    into the connected components of its k-NN graph restricted to edges whose normals differ by less than
-    `angle` (radians).  target: a surface name, a PointSurface already taken out of the boundary, or None
-    (the boundary must then hold exactly one surface)."""
-    bnd = cloud.boundary if isinstance(cloud, PointCloud) else cloud
-    assert isinstance(bnd, PointBoundary)
-    if target is None:
-        assert len(bnd.surfaces) == 1, "More than 1 surface in this cloud. Please specify a target surface."
-        target = next(iter(bnd.surfaces))
-    if isinstance(target, PointSurface):
-        surf = target
-    else:
-        assert target in bnd.surfaces, "Target surface not found in cloud."
-        surf = bnd.surfaces.pop(target)
-    p, nrm, areas = surf.points(), surf.normals, surf.areas
-    assert nrm is not None, "split_surface needs normals"
+def _host_labels(p, nrm, kk, angle, ctx):
     n = len(p)
-    kk = min(int(k), n)
     rows = _rows(p, kk, ctx)
     src = np.repeat(rows[:, 0], kk - 1).astype(np.int64)
     dst = rows[:, 1:].reshape(-1).astype(np.int64)
@@ -165,7 +161,33 @@ def split_surface(cloud, angle: float, target=None, k: int = 10, ctx=None):
                 dsu.p[rb] = ra
             else:
                 dsu.p[ra] = rb
-    label = np.array([dsu.find(i) for i in range(n)])
+    return np.array([dsu.find(i) for i in range(n)])
+
+
+def split_surface(cloud, angle: float, target=None, k: int = 10, ctx=None, graph: str = "device"):
+    """split_surface!(cloud|boundary, [target], angle; k) (src/surface_operations.jl:33-94): splits a surface
+    into the connected components of its k-NN graph restricted to edges whose normals differ by less than
+    `angle` (radians).  target: a surface name, a PointSurface already taken out of the boundary, or None
+    (the boundary must then hold exactly one surface).  graph="device": the components on the GPU
+    (wtp_normal_components); "host": here.  Either way the new surfaces are numbered by first vertex."""
+    device = _graph_mode(graph)
+    bnd = cloud.boundary if isinstance(cloud, PointCloud) else cloud
+    assert isinstance(bnd, PointBoundary)
+    if target is None:
+        assert len(bnd.surfaces) == 1, "More than 1 surface in this cloud. Please specify a target surface."
+        target = next(iter(bnd.surfaces))
+    if isinstance(target, PointSurface):
+        surf = target
+    else:
+        assert target in bnd.surfaces, "Target surface not found in cloud."
+        surf = bnd.surfaces.pop(target)
+    p, nrm, areas = surf.points(), surf.normals, surf.areas
+    assert nrm is not None, "split_surface needs normals"
+    kk = min(int(k), len(p))
+    if device:
+        label = (ctx or default_context()).normal_components(p, nrm, kk, angle)[0]
+    else:
+        label = _host_labels(p, nrm, kk, angle, ctx)
     for comp in np.unique(label):                                # connected_components: by first vertex
         ids = np.nonzero(label == comp)[0]
         i = 1
