@@ -39,7 +39,8 @@ typedef enum wtp_status {
     WTP_ERR_OOM = 2,      /* device or host allocation failed */
     WTP_ERR_HIP = 3,      /* HIP runtime / kernel error */
     WTP_ERR_STATE = 4,    /* call out of order (e.g. relax_step before relax_init) */
-    WTP_ERR_NO_DEVICE = 5 /* no usable gfx950 device: the library never falls back to a CPU path */
+    WTP_ERR_NO_DEVICE = 5,/* no usable gfx950 device: the library never falls back to a CPU path */
+    WTP_ERR_INTERNAL = 6  /* a bound the algorithm guarantees was exceeded (wtp_mesh_sample's round limit): a defect */
 } wtp_status;
 
 typedef enum wtp_dtype { WTP_F32 = 0, WTP_F64 = 1 } wtp_dtype;
@@ -304,6 +305,51 @@ int wtp_relax_query_knn(wtp_ctx* ctx, const void* xyz, int64_t nq, int k, int32_
 /* Writes membership and landing triangles back after the host-side deposition pass
  * (_deposit_escaped!, src/repel.jl:471-520, serial by design).  */
 int wtp_relax_set_wall_flags(wtp_ctx* ctx, const uint8_t* is_bnd, const int32_t* tri);
+
+/* ---- graded Poisson-disk sampling of the mesh surface ----
+ * Replaces sample_surface(mesh, spacing; factor, max_points, stall_limit) / PointBoundary(mesh, spacing)
+ * (src/surface_sampling.jl:34-118): dart throwing on the continuous surface under ||x_i - x_j|| >= min(r_i, r_j),
+ * r = factor h(x).  The reference draws from rand(); here the darts are a seeded counter-based stream and the result is
+ * DEFINED as the serial loop over that stream, so a run can be reproduced anywhere, bit for bit:
+ *   Host, once, in double: area_t = sqrt((c_x^2 + c_y^2) + c_z^2) / 2 with c = (v2 - v1) x (v3 - v1) from the corners
+ * converted to double (c_x = e_y g_z - e_z g_y, c_y = e_z g_x - e_x g_z, c_z = e_x g_y - e_y g_x); cum = their running
+ * sum in triangle order; total_area = cum[nt - 1].
+ *   Dart j = 0, 1, ... (64-bit) of seed s < 2^24: w_a = splitmix64((s << 40) + 3 j + a), a = 0, 1, 2 (the keys of
+ * wtp_gen_uniform_dev).  Triangle, in double: x = ((w_0 >> 11) 2^-53) total_area; t = the first index with
+ * cum[t] >= x, at most nt - 1.  In the mesh's type T, no contraction: u = T((w_1 >> 40) 2^-24), v = T((w_2 >> 40) 2^-24)
+ * (wtp_gen_uniform_dev's values), su = sqrt(u), position c = ((1 - su) v1 + (su (1 - v)) v2) + (su v) v3 per component,
+ * r = T(factor) h(c) with the spacing law evaluated at c in T (CONSTANT: h = T(constant)).
+ *   Darts p and q conflict when ((dx^2 + dy^2) + dz^2) < m m, m = min(r_p, r_q), all in T.
+ *   Run.  Darts are taken in order.  Before each dart the run ends if max_points darts have been accepted
+ * (stop_reason 2) or the last stall_limit darts were all rejected (stop_reason 1); n_darts counts the darts taken.  A
+ * dart is accepted iff it conflicts with no earlier accepted dart.  The samples are the accepted darts in dart order.
+ * The device decides whole batches of darts at once (rounds of "decide every dart whose lower-numbered conflicting darts
+ * are decided"); the result does not depend on the batch size, uses no floating-point atomics and does not depend on
+ * arrival order: two calls return the same bits, and a smaller max_points returns a prefix.
+ *   batch: darts per batch, 0 = the library chooses; it changes time only.  A spacing value that is not finite and > 0
+ * at a dart the run takes is WTP_ERR_ARG naming the smallest such dart; such a dart is never sampled with.
+ *   WTP_ERR_STATE: no mesh set; wtp_mesh_sample_get* before a successful wtp_mesh_sample; another boundary's law while a
+ * relax session evaluates its own.  WTP_ERR_ARG: factor not finite or <= 0, stall_limit < 1, max_points < 1,
+ * seed >= 2^24, batch < 0 or > 2^24, kind WTP_SPACING_PER_POINT, total_area not > 0, a bad spacing value.  WTP_ERR_INTERNAL: a
+ * batch of B darts was not decided within B rounds (the algorithm's bound).  */
+typedef struct wtp_sample_info {
+    int64_t n_points, n_darts, batch;   /* batch: the size used in the last batch */
+    int32_t stop_reason;                /* 1 stall_limit misses in a row, 2 max_points */
+    int32_t n_batches, rounds_max, host_syncs;
+    double total_area, r_min, r_max;    /* r over the samples */
+} wtp_sample_info;
+/* Samples the mesh of wtp_mesh_set; the result stays on the device until the next call / wtp_mesh_set / wtp_mesh_clear. */
+int wtp_mesh_sample(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, int64_t max_points,
+                    int64_t stall_limit, uint64_t seed, int64_t batch, wtp_sample_info* info);
+/* n_points rows (xyz_out n x 3 and r_out of the mesh's dtype); every output may be NULL.  dart_out: the dart index each
+ * sample came from.  */
+int wtp_mesh_sample_get(wtp_ctx* ctx, void* xyz_out, int32_t* tri_out, void* r_out, int64_t* dart_out);
+/* The same into device memory.  */
+int wtp_mesh_sample_get_dev(wtp_ctx* ctx, void* d_xyz_out, int32_t* d_tri_out, void* d_r_out);
+/* Read-out, no acceptance: darts first .. first + n - 1 as the rule above makes them (host outputs, may be NULL).  The
+ * values are returned as computed, a spacing that is not > 0 included.  Leaves a resident sample untouched.  */
+int wtp_mesh_sample_darts(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, uint64_t seed,
+                          int64_t first, int64_t n, void* xyz_out, int32_t* tri_out, void* r_out);
 
 /* ---- consumers of the k-NN rows ------------------------------------
  * Replaces compute_normals(points; k) / update_normals! (src/normals.jl:15-69): per point the

@@ -10,7 +10,7 @@ CSRC = os.path.join(_HERE, "csrc")
 # WTP_LIB selects another build of the same sources (A/B experiments); default: csrc/libwtp.so
 SO_PATH = os.environ.get("WTP_LIB") or os.path.join(CSRC, "libwtp.so")
 
-WTP_OK, WTP_ERR_ARG, WTP_ERR_OOM, WTP_ERR_HIP, WTP_ERR_STATE, WTP_ERR_NO_DEVICE = range(6)
+WTP_OK, WTP_ERR_ARG, WTP_ERR_OOM, WTP_ERR_HIP, WTP_ERR_STATE, WTP_ERR_NO_DEVICE, WTP_ERR_INTERNAL = range(7)
 WTP_F32, WTP_F64 = 0, 1
 WTP_SPACING_CONSTANT, WTP_SPACING_PER_POINT, WTP_SPACING_LOGLIKE, WTP_SPACING_BOUNDARY_LAYER = range(4)
 
@@ -78,6 +78,13 @@ class NormalGraphInfo(C.Structure):
                 ("start", C.c_int64), ("rounds", C.c_int32), ("host_syncs", C.c_int32)]
 
 
+class SampleInfo(C.Structure):
+    """wtp_sample_info: what wtp_mesh_sample reports about a run."""
+    _fields_ = [("n_points", C.c_int64), ("n_darts", C.c_int64), ("batch", C.c_int64), ("stop_reason", C.c_int32),
+                ("n_batches", C.c_int32), ("rounds_max", C.c_int32), ("host_syncs", C.c_int32),
+                ("total_area", C.c_double), ("r_min", C.c_double), ("r_max", C.c_double)]
+
+
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                           C.POINTER(C.c_void_p), C.POINTER(C.c_int64))
@@ -128,6 +135,10 @@ SIGNATURES = {
     "wtp_mesh_face_normals": (_i, [_vp, _vp]),
     "wtp_mesh_bounds": (_i, [_vp, _vp]),
     "wtp_mesh_query": (_i, [_vp, _vp, _i64, _i, _d, _vp, _vp, _vp, _vp, _vp]),
+    "wtp_mesh_sample": (_i, [_vp, C.POINTER(SpacingDesc), _d, _i64, _i64, C.c_uint64, _i64, C.POINTER(SampleInfo)]),
+    "wtp_mesh_sample_get": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "wtp_mesh_sample_get_dev": (_i, [_vp, _vp, _vp, _vp]),
+    "wtp_mesh_sample_darts": (_i, [_vp, C.POINTER(SpacingDesc), _d, C.c_uint64, _i64, _i64, _vp, _vp, _vp]),
     "wtp_relax_set_wall": (_i, [_vp, _i64, _d]),
     "wtp_relax_get_wall": (_i, [_vp, _vp, _vp, _vp, _i]),
     "wtp_relax_set_wall_flags": (_i, [_vp, _vp, _vp]),

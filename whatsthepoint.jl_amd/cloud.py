@@ -125,6 +125,14 @@ class PointBoundary:
 
         return cls(PointSurface(*stl.surface_elements(path, dtype)), name=name)
 
+    @classmethod
+    def from_mesh(cls, mesh, spacing, name: str = "surface1", **kw):
+        """PointBoundary(mesh, spacing; kwargs...) (src/surface_sampling.jl:113-118): Poisson-disk samples of the mesh
+        surface at the prescribed spacing (sampling.sample_surface takes the keywords) instead of the face centres."""
+        from .sampling import sample_surface
+
+        return cls(sample_surface(mesh, spacing, **kw), name=name)
+
     def elements(self):
         """(points, normals, areas) over all surfaces, or None if a surface lacks normals/areas."""
         ss = list(self.surfaces.values())

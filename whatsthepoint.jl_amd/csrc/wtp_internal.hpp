@@ -360,6 +360,23 @@ struct MeshState {
     bool cls_ready = false;
     int cls_dim[3] = {0, 0, 0};
     double cls_cell = 0;
+    DevBuf corners, cum;           // wtp_mesh_sample: nt x 9 corner coordinates (mesh dtype), running area sums (double), triangle order
+    double total_area = 0;         // cum[nt - 1]
+};
+
+// Poisson-disk surface sampling (wtp_sample.hip): the accepted samples and their cell table stay on the device between
+// wtp_mesh_sample and the wtp_mesh_sample_get* calls; the batch buffers are reused by every batch and by the dart read-out.
+struct SampleState {
+    bool valid = false;            // a sample of the current mesh is resident
+    int dtype = -1;
+    int64_t n = 0, cap = 0;        // samples held, rows the arrays below have room for
+    DevBuf pts, tri, dart, next;   // per sample: {x, y, z, r} (Pt), parent triangle, dart index, next sample of its cell
+    DevBuf table;                  // open addressing over 64-bit cell keys: [keys ; heads], tsz slots each
+    int64_t tsz = 0;
+    int64_t bcap = 0;              // darts the batch buffers have room for
+    DevBuf b_xyz, b_h, b_pts, b_tri, b_st, b_next, b_pos, b_last, b_table, b_blk;
+    int64_t b_tsz = 0;
+    DevBuf ctl;                    // one SampleCtl
 };
 
 struct KdTree {
@@ -500,6 +517,7 @@ struct wtp_ctx {
     wtp::DevBuf diag;          // diagnostic builds only
     wtp::DevBuf ins_in, ins_elems, ins_partial, ins_out; // isinside filter
     wtp::MeshState mesh;
+    wtp::SampleState sample;
     wtp::DevBuf sp_hint;       // variable spacings: nearest tree node of each snapshot point at the last sweep
     wtp::KdTree kd;
     int64_t n_syncs = 0;       // host synchronisations of the context's stream so far (wtp_block_info.host_syncs counts with it)
@@ -667,6 +685,8 @@ int launch_normal_graph_rounds(wtp_ctx* ctx, const T* d_nrm, const int32_t* d_ro
 template <typename T>
 int launch_normal_graph_apply(wtp_ctx* ctx, T* d_nrm, int64_t n, int dim, const uint32_t* d_cur, int32_t* d_label_out,
                               unsigned long long* d_ctl);
+// wtp_sample.hip: a new or cleared mesh voids the resident sample
+void sample_invalidate(wtp_ctx* ctx);
 // wall rule of the octree method (wtp_mesh.hip)
 template <typename TP>
 int launch_mesh_constrain(wtp_ctx* ctx, const Pt<TP>* old, Pt<TP>* cur, int64_t n, int64_t n_fixed, double offset,

@@ -748,6 +748,26 @@ template <typename TM> static int mesh_set_t(wtp_ctx* ctx, const TM* verts, int6
     ctx->mesh.face_host.assign((size_t)nt * 3, 0.0);
     for (int64_t t = 0; t < nt; ++t)
         for (int a = 0; a < 3; ++a) ctx->mesh.face_host[3 * t + a] = (double)pn[21 * t + a];
+    // wtp_mesh_sample (wtp_sample.hip): the corners in triangle order and the running sum of the areas, in double
+    std::vector<TM> corners((size_t)nt * 9);
+    std::vector<double> cum((size_t)nt);
+    double run = 0;
+    for (int64_t t = 0; t < nt; ++t) {
+        double v[3][3];
+        for (int c = 0; c < 3; ++c)
+            for (int a = 0; a < 3; ++a) v[c][a] = (double)(corners[9 * t + 3 * c + a] = verts[3 * (int64_t)tris[3 * t + c] + a]);
+        const double e[3] = {v[1][0] - v[0][0], v[1][1] - v[0][1], v[1][2] - v[0][2]};
+        const double g[3] = {v[2][0] - v[0][0], v[2][1] - v[0][1], v[2][2] - v[0][2]};
+        const double cx = e[1] * g[2] - e[2] * g[1], cy = e[2] * g[0] - e[0] * g[2], cz = e[0] * g[1] - e[1] * g[0];
+        run += std::sqrt((cx * cx + cy * cy) + cz * cz) / 2;
+        cum[t] = run;
+    }
+    if ((rc = ensure(ctx, ctx->mesh.corners, sizeof(TM) * 9 * (size_t)nt))) return rc;
+    if ((rc = ensure(ctx, ctx->mesh.cum, sizeof(double) * (size_t)nt))) return rc;
+    WTP_HIP(ctx, hipMemcpyAsync(ctx->mesh.corners.p, corners.data(), sizeof(TM) * 9 * (size_t)nt, hipMemcpyHostToDevice, ctx->stream));
+    WTP_HIP(ctx, hipMemcpyAsync(ctx->mesh.cum.p, cum.data(), sizeof(double) * (size_t)nt, hipMemcpyHostToDevice, ctx->stream));
+    WTP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->mesh.total_area = run;
     return WTP_OK;
 }
 
@@ -771,6 +791,7 @@ WTP_API int wtp_mesh_set(wtp_ctx* ctx, const void* vertices, int64_t nv, const i
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     ctx->mesh.nt = 0;
     ctx->mesh.cls_ready = false;
+    sample_invalidate(ctx);
     const int rc = dtype == WTP_F32 ? mesh_set_t<float>(ctx, (const float*)vertices, nv, triangles, nt)
                                     : mesh_set_t<double>(ctx, (const double*)vertices, nv, triangles, nt);
     if (rc) return rc;
@@ -786,6 +807,7 @@ WTP_API int wtp_mesh_clear(wtp_ctx* ctx) {
     ctx->mesh.nt = 0;
     ctx->mesh.cls_ready = false;
     ctx->mesh.face_host.clear();
+    sample_invalidate(ctx);
     return WTP_OK;
 }
 

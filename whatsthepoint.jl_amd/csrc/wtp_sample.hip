@@ -1,0 +1,787 @@
+// wtp_sample.hip — graded Poisson-disk sampling of the mesh surface.
+//
+//   sample_surface(mesh, spacing; factor, max_points, stall_limit)     src/surface_sampling.jl:34-104
+//   PointBoundary(mesh, spacing)                                       :113-118
+//
+// The reference throws one dart at a time: area-weighted triangle, uniform point in it, accepted iff it keeps
+// min(r_i, r_j) from every accepted sample, r = factor h(x).  include/wtp.h pins the darts to a counter-based stream, so
+// the serial loop over that stream is the definition of the result; this file computes it in batches of B consecutive
+// darts.  Dart throwing in a fixed order is the greedy maximal independent set under fixed priorities, and that set is
+// reached by rounds of "decide every dart whose lower-numbered conflicting darts are all decided":
+//   1. generate      one thread per dart: triangle by binary search of the area sums (double), position and r in T;
+//   2. cull          a dart in conflict with an accepted sample is dead; the live ones enter the batch's cell table;
+//   3. rounds        an undecided dart is rejected if a lower-numbered conflicting dart was accepted in an EARLIER round,
+//                    accepted if all of them were rejected earlier (Jacobi: a word per dart holds the round of its
+//                    decision, so the round count is as unique as the result); the lowest undecided dart is decided
+//                    every round, so B rounds bound a batch; in practice about ten do;
+//   4. stop + append a scan over the accept flags in dart order carries the miss run and the sample count in, finds the
+//                    first dart at which the run ends, and appends the accepted darts before it by prefix sum.
+// Rounds are launched in groups of kGroup; a per-round device counter of undecided darts turns the rest of a group into
+// no-ops, and the scan, the append and the insertion into the accepted table follow in the same group, guarded by the
+// same counter: the host reads one control block per group.  No kernel waits for another thread's store; every loop is
+// bounded by a count known at launch.
+//
+// Cells.  Both the accepted samples and a batch's live darts are kept in an open-addressing table of 64-bit cell keys
+// (three 20-bit cell coordinates over the mesh's bounding box), each slot heading a chain of the points in that cell: a
+// dense array over the box would hold O((L / r)^3) cells of which the surface fills O((L / r)^2).  A sample in conflict
+// with dart p lies within r_p of it, so p scans the cells its ball touches; the cell map is monotone and the ball is
+// widened by the rounding of its own bounds, so nothing rests on one point per cell or on an r_min known in advance.  A
+// ball that touches more cells than there are points scans the points instead.  The chain order depends on arrival;
+// nothing read from a chain does (a conflict exists or not).  The cell edge is sqrt(r_min r_max) of the first batch.
+#include <climits>
+#include <cmath>
+
+#include "wtp_device.hpp"
+
+namespace wtp {
+
+static constexpr int kSmThreads = 256;
+static constexpr int kGroup = 8;                       // rounds per host read-back
+static constexpr int kScanItems = 8;                   // darts per thread of the stop scan
+static constexpr int kTile = kSmThreads * kScanItems;  // darts per block of the stop scan
+static constexpr int64_t kBatchFirst = 4096, kBatchMax = 1 << 20; // batch = 0: doubled from / up to
+static constexpr int64_t kReadChunk = 1 << 18;         // wtp_mesh_sample_darts works in pieces of this many darts
+static constexpr unsigned long long kEmpty = ~0ull;
+
+// dart states: 0 undecided, else ((round of the decision + 1) << 1) | accepted; culled darts count as round 0
+static constexpr int32_t kCulled = 2;
+
+struct SampleCtl {
+    unsigned long long bad;        // smallest dart index with a bad spacing value (~0: none)
+    unsigned long long rmin, rmax; // bits of the smallest / largest r (as double) a range pass saw
+    long long n;                   // samples accepted so far
+    long long miss;                // rejected darts in a row so far
+    long long n_darts;             // darts taken so far
+    int32_t stopped;               // 0 running, 1 the run ended, 3 a dart the run took has a bad spacing value
+    int32_t reason;
+    int32_t end;                   // batch-local index of the first dart the run does not take (INT_MAX: none)
+    int32_t n_new;                 // samples the batch appended
+    int32_t und[kGroup];           // darts left undecided by each round of the group
+};
+
+template <typename T> struct CellMap {
+    T org[3];
+    T inv_c;
+    int32_t nc[3];
+};
+
+template <typename T> struct SmEps;
+template <> struct SmEps<float> { static constexpr float v = 1.1920928955078125e-07f; };
+template <> struct SmEps<double> { static constexpr double v = 2.220446049250313e-16; };
+
+struct Table {
+    unsigned long long* keys;
+    int32_t* heads;
+    uint32_t mask;
+    int32_t shift;
+};
+
+__device__ inline uint64_t sm_splitmix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+template <typename T> __device__ inline int cell_of(const CellMap<T>& m, T v, int a) {
+    const T s = (v - m.org[a]) * m.inv_c; // monotone in v; anything outside the box piles into the edge cells
+    if (!(s > (T)0)) return 0;
+    if (s >= (T)(m.nc[a] - 1)) return m.nc[a] - 1;
+    return (int)s;
+}
+
+__device__ inline unsigned long long cell_key(int cx, int cy, int cz) {
+    return ((unsigned long long)cz << 40) | ((unsigned long long)cy << 20) | (unsigned long long)cx;
+}
+
+template <typename T> __device__ inline unsigned long long key_of(const CellMap<T>& m, const Pt<T>& p) {
+    return cell_key(cell_of(m, p.x, 0), cell_of(m, p.y, 1), cell_of(m, p.z, 2));
+}
+
+__device__ inline uint32_t slot_of(const Table& t, unsigned long long key) {
+    return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> t.shift) & t.mask;
+}
+
+// the table holds at most half as many keys as slots, so a probe ends within mask + 1 steps
+__device__ inline void table_insert(const Table& t, int32_t* next, unsigned long long key, int32_t i) {
+    uint32_t s = slot_of(t, key);
+    for (uint32_t it = 0; it <= t.mask; ++it) {
+        const unsigned long long prev = atomicCAS(&t.keys[s], kEmpty, key);
+        if (prev == kEmpty || prev == key) {
+            next[i] = atomicExch(&t.heads[s], i);
+            return;
+        }
+        s = (s + 1) & t.mask;
+    }
+}
+
+__device__ inline int32_t table_find(const Table& t, unsigned long long key) {
+    uint32_t s = slot_of(t, key);
+    for (uint32_t it = 0; it <= t.mask; ++it) {
+        const unsigned long long k = t.keys[s];
+        if (k == key) return t.heads[s];
+        if (k == kEmpty) return -1;
+        s = (s + 1) & t.mask;
+    }
+    return -1;
+}
+
+template <typename T> __device__ inline bool conflict(const Pt<T>& p, const Pt<T>& q) {
+    const T dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
+    const T m = p.w < q.w ? p.w : q.w;
+    return ((dx * dx + dy * dy) + dz * dz) < m * m;
+}
+
+// Calls f(j, pts[j]) for every point j < count of the table that can be in conflict with p (and maybe others), until f
+// returns true.  A conflict has |fl(p.x - q.x)| < r_p on every axis, so q lies in a cell between those of the ball's
+// bounds, widened by the rounding of the bounds themselves.
+template <typename T, typename F>
+__device__ inline void for_near(const CellMap<T>& m, const Table& t, const int32_t* __restrict__ next,
+                                const Pt<T>* __restrict__ pts, int64_t count, const Pt<T>& p, F f) {
+    int lo[3], hi[3];
+    const T c[3] = {p.x, p.y, p.z};
+    int64_t cells = 1;
+    for (int a = 0; a < 3; ++a) {
+        const T marg = (T)8 * SmEps<T>::v * ((c[a] < 0 ? -c[a] : c[a]) + p.w);
+        lo[a] = cell_of(m, (c[a] - p.w) - marg, a);
+        hi[a] = cell_of(m, (c[a] + p.w) + marg, a);
+        cells *= (int64_t)(hi[a] - lo[a] + 1);
+    }
+    if (cells > count) { // fewer points than cells: look at the points
+        for (int64_t j = 0; j < count; ++j)
+            if (f((int32_t)j, pts[j])) return;
+        return;
+    }
+    for (int cz = lo[2]; cz <= hi[2]; ++cz)
+        for (int cy = lo[1]; cy <= hi[1]; ++cy)
+            for (int cx = lo[0]; cx <= hi[0]; ++cx) {
+                int32_t j = table_find(t, cell_key(cx, cy, cz));
+                for (int64_t steps = 0; j >= 0 && steps < count; ++steps) { // a chain is no longer than the table's points
+                    if (f(j, pts[j])) return;
+                    j = next[j];
+                }
+            }
+}
+
+// ---- step 1: the darts ---------------------------------------------------------------------------------------------
+template <typename T>
+__global__ void sample_gen_kernel(uint64_t seed, int64_t first, int64_t n, const T* __restrict__ corners,
+                                  const double* __restrict__ cum, int32_t nt, double total_area, T* __restrict__ xyz,
+                                  int32_t* __restrict__ tri) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t base = (seed << 40) + 3ull * (uint64_t)(first + i);
+        const uint64_t w0 = sm_splitmix64(base), w1 = sm_splitmix64(base + 1), w2 = sm_splitmix64(base + 2);
+        const double x = ((double)(w0 >> 11) * 0x1p-53) * total_area;
+        int32_t lo = 0, hi = nt; // first index with cum >= x (searchsortedfirst), then the clamp
+        for (int it = 0; it < 32 && lo < hi; ++it) {
+            const int32_t mid = lo + ((hi - lo) >> 1);
+            if (cum[mid] < x) lo = mid + 1;
+            else hi = mid;
+        }
+        const int32_t t = lo < nt - 1 ? lo : nt - 1;
+        const T u = (T)((float)(w1 >> 40) * (1.0f / 16777216.0f));
+        const T v = (T)((float)(w2 >> 40) * (1.0f / 16777216.0f));
+        const T su = wsqrt(u);
+        const T a = (T)1 - su, b = su * ((T)1 - v), c = su * v;
+        const T* k = corners + 9 * (int64_t)t;
+        for (int d = 0; d < 3; ++d) xyz[3 * i + d] = (a * k[d] + b * k[3 + d]) + c * k[6 + d];
+        tri[i] = t;
+    }
+}
+
+template <typename T> __device__ inline bool good_value(T v) { return v > (T)0 && v < Lim<T>::inf(); }
+
+// r = T(factor) h; a spacing value that is not finite and > 0 is reported by the smallest dart index
+template <typename T>
+__global__ void sample_radius_kernel(const T* __restrict__ xyz, const T* __restrict__ h, T h_const, T factor, int64_t first,
+                                     int64_t n, Pt<T>* __restrict__ pts, SampleCtl* __restrict__ ctl) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const T hv = h ? h[i] : h_const;
+        Pt<T> p;
+        p.x = xyz[3 * i], p.y = xyz[3 * i + 1], p.z = xyz[3 * i + 2], p.w = factor * hv;
+        pts[i] = p;
+        if (!(good_value(hv) && good_value(p.w))) atomicMin(&ctl->bad, (unsigned long long)(first + i));
+    }
+}
+
+// smallest and largest good r of pts[0, n) into ctl (integer atomics on the bits of positive doubles)
+template <typename T>
+__global__ void sample_range_kernel(const Pt<T>* __restrict__ pts, int64_t n, SampleCtl* __restrict__ ctl) {
+    __shared__ unsigned long long s_lo[kSmThreads], s_hi[kSmThreads];
+    unsigned long long lo = kEmpty, hi = 0;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const T r = pts[i].w;
+        if (!good_value(r)) continue;
+        const unsigned long long b = __builtin_bit_cast(unsigned long long, (double)r);
+        lo = b < lo ? b : lo;
+        hi = b > hi ? b : hi;
+    }
+    s_lo[threadIdx.x] = lo, s_hi[threadIdx.x] = hi;
+    __syncthreads();
+    for (int d = kSmThreads / 2; d > 0; d >>= 1) {
+        if ((int)threadIdx.x < d) {
+            if (s_lo[threadIdx.x + d] < s_lo[threadIdx.x]) s_lo[threadIdx.x] = s_lo[threadIdx.x + d];
+            if (s_hi[threadIdx.x + d] > s_hi[threadIdx.x]) s_hi[threadIdx.x] = s_hi[threadIdx.x + d];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        if (s_lo[0] != kEmpty) atomicMin(&ctl->rmin, s_lo[0]);
+        if (s_hi[0] != 0) atomicMax(&ctl->rmax, s_hi[0]);
+    }
+}
+
+__global__ void sample_begin_kernel(SampleCtl* __restrict__ ctl) {
+    ctl->end = INT_MAX;
+    ctl->n_new = 0;
+}
+
+// ---- step 2: cull against the accepted samples; the live darts enter the batch's table ----------------------------------
+template <typename T>
+__global__ void sample_cull_kernel(CellMap<T> m, const Pt<T>* __restrict__ b_pts, int32_t B, int32_t* __restrict__ st,
+                                   Table acc, const int32_t* __restrict__ s_next, const Pt<T>* __restrict__ s_pts,
+                                   int64_t n_acc, Table bt, int32_t* __restrict__ b_next) {
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    const Pt<T> p = b_pts[i];
+    bool dead = !good_value(p.w); // a bad spacing value: never sampled with (the stop scan decides whether it is an error)
+    if (!dead)
+        for_near<T>(m, acc, s_next, s_pts, n_acc, p, [&](int32_t, const Pt<T>& q) { return dead = conflict<T>(p, q); });
+    st[i] = dead ? kCulled : 0;
+    if (!dead) table_insert(bt, b_next, key_of(m, p), i);
+}
+
+// ---- step 3: one round.  g: position in the group; round: 1-based round of the batch -----------------------------------
+template <typename T>
+__global__ void sample_round_kernel(CellMap<T> m, const Pt<T>* __restrict__ b_pts, int32_t B, int32_t* __restrict__ st,
+                                    Table bt, const int32_t* __restrict__ b_next, int g, int32_t round,
+                                    SampleCtl* __restrict__ ctl) {
+    if (g > 0 && ctl->und[g - 1] == 0) return; // nothing was left undecided: the rest of the group does nothing
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B || st[i] != 0) return;
+    const Pt<T> p = b_pts[i];
+    bool rejected = false, pending = false;
+    // the points of the table are the live darts; of a linear scan (count = i) the lower-numbered darts, culled ones too
+    for_near<T>(m, bt, b_next, b_pts, (int64_t)B, p, [&](int32_t j, const Pt<T>& q) {
+        if (j >= i || !conflict<T>(p, q)) return false;
+        const int32_t s = __atomic_load_n(&st[j], __ATOMIC_RELAXED);
+        if (s == 0 || (s >> 1) > round) pending = true; // undecided before this round
+        else if (s & 1) rejected = true;
+        return rejected;
+    });
+    if (rejected) __atomic_store_n(&st[i], (round + 1) << 1, __ATOMIC_RELAXED);
+    else if (!pending) __atomic_store_n(&st[i], ((round + 1) << 1) | 1, __ATOMIC_RELAXED);
+    else atomicAdd(&ctl->und[g], 1);
+}
+
+// ---- step 4: the stop rule as a scan in dart order ---------------------------------------------------------------------
+__device__ inline bool is_accepted(const int32_t* __restrict__ st, int32_t B, int64_t i) { return i < B && (st[i] & 1); }
+
+// per tile: accepted darts, index of the last one (-1: none)
+__global__ void sample_scan_a_kernel(const int32_t* __restrict__ st, int32_t B, int2* __restrict__ blk,
+                                     const SampleCtl* __restrict__ ctl) {
+    if (ctl->und[kGroup - 1] != 0) return;
+    __shared__ int32_t s_cnt[kSmThreads], s_last[kSmThreads];
+    const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kScanItems;
+    int32_t cnt = 0, last = -1;
+    for (int e = 0; e < kScanItems; ++e)
+        if (is_accepted(st, B, base + e)) ++cnt, last = (int32_t)(base + e);
+    s_cnt[threadIdx.x] = cnt, s_last[threadIdx.x] = last;
+    __syncthreads();
+    for (int d = kSmThreads / 2; d > 0; d >>= 1) {
+        if ((int)threadIdx.x < d) {
+            s_cnt[threadIdx.x] += s_cnt[threadIdx.x + d];
+            if (s_last[threadIdx.x + d] > s_last[threadIdx.x]) s_last[threadIdx.x] = s_last[threadIdx.x + d];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) blk[blockIdx.x] = make_int2(s_cnt[0], s_last[0]);
+}
+
+// Exclusive (sum, max) scan of s_cnt / s_last over the block's threads, in place; returns the block's totals.
+__device__ inline int2 block_scan_excl(int32_t* s_cnt, int32_t* s_last, int32_t cnt, int32_t last) {
+    const int t = threadIdx.x;
+    s_cnt[t] = cnt, s_last[t] = last;
+    __syncthreads();
+    for (int d = 1; d < kSmThreads; d <<= 1) {
+        const int32_t c = t >= d ? s_cnt[t - d] : 0, l = t >= d ? s_last[t - d] : -1;
+        __syncthreads();
+        s_cnt[t] += c;
+        if (l > s_last[t]) s_last[t] = l;
+        __syncthreads();
+    }
+    const int2 total = make_int2(s_cnt[kSmThreads - 1], s_last[kSmThreads - 1]);
+    const int32_t ec = t > 0 ? s_cnt[t - 1] : 0, el = t > 0 ? s_last[t - 1] : -1;
+    __syncthreads();
+    s_cnt[t] = ec, s_last[t] = el;
+    __syncthreads();
+    return total;
+}
+
+// one block: what precedes each tile (accepted darts, index of the last one)
+__global__ void sample_scan_b_kernel(const int2* __restrict__ blk, int32_t nblk, int2* __restrict__ blk_ex,
+                                     const SampleCtl* __restrict__ ctl) {
+    if (ctl->und[kGroup - 1] != 0) return;
+    __shared__ int32_t s_cnt[kSmThreads], s_last[kSmThreads];
+    int32_t carry_c = 0, carry_l = -1;
+    for (int32_t base = 0; base < nblk; base += kSmThreads) {
+        const int32_t b = base + threadIdx.x;
+        const int2 v = b < nblk ? blk[b] : make_int2(0, -1);
+        const int2 tot = block_scan_excl(s_cnt, s_last, v.x, v.y);
+        if (b < nblk) blk_ex[b] = make_int2(carry_c + s_cnt[threadIdx.x], s_last[threadIdx.x] > carry_l ? s_last[threadIdx.x] : carry_l);
+        carry_c += tot.x;
+        carry_l = tot.y > carry_l ? tot.y : carry_l;
+        __syncthreads();
+    }
+}
+
+// per dart i of [0, B] (B: the position behind the batch): accepted darts before it, index of the last one; the first i
+// at which the run ends goes to ctl->end
+__global__ void sample_scan_c_kernel(const int32_t* __restrict__ st, int32_t B, const int2* __restrict__ blk_ex,
+                                     int32_t* __restrict__ pos, int32_t* __restrict__ lastb, int64_t max_points,
+                                     int64_t stall_limit, SampleCtl* __restrict__ ctl) {
+    if (ctl->und[kGroup - 1] != 0) return;
+    __shared__ int32_t s_cnt[kSmThreads], s_last[kSmThreads];
+    __shared__ int32_t s_end;
+    if (threadIdx.x == 0) s_end = INT_MAX;
+    const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kScanItems;
+    int32_t cnt = 0, last = -1;
+    for (int e = 0; e < kScanItems; ++e)
+        if (is_accepted(st, B, base + e)) ++cnt, last = (int32_t)(base + e);
+    block_scan_excl(s_cnt, s_last, cnt, last);
+    const int2 pre = blk_ex[blockIdx.x];
+    int32_t c = pre.x + s_cnt[threadIdx.x];
+    int32_t l = s_last[threadIdx.x] > pre.y ? s_last[threadIdx.x] : pre.y;
+    const long long n0 = ctl->n, miss0 = ctl->miss;
+    int32_t end = INT_MAX;
+    for (int e = 0; e < kScanItems; ++e) {
+        const int64_t i = base + e;
+        if (i > B) break;
+        pos[i] = c, lastb[i] = l;
+        const long long miss = l >= 0 ? i - l - 1 : miss0 + i;
+        if (end == INT_MAX && (n0 + c >= max_points || miss >= stall_limit)) end = (int32_t)i;
+        if (is_accepted(st, B, i)) ++c, l = (int32_t)i;
+    }
+    if (end != INT_MAX) atomicMin(&s_end, end);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_end != INT_MAX) atomicMin(&ctl->end, s_end);
+}
+
+template <typename T>
+__global__ void sample_append_kernel(const Pt<T>* __restrict__ b_pts, const int32_t* __restrict__ b_tri,
+                                     const int32_t* __restrict__ st, int32_t B, const int32_t* __restrict__ pos, int64_t first,
+                                     Pt<T>* __restrict__ s_pts, int32_t* __restrict__ s_tri, int64_t* __restrict__ s_dart,
+                                     const SampleCtl* __restrict__ ctl) {
+    if (ctl->und[kGroup - 1] != 0) return;
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B || i >= ctl->end || !(st[i] & 1)) return;
+    const int64_t j = ctl->n + pos[i]; // dart order
+    s_pts[j] = b_pts[i];
+    s_tri[j] = b_tri[i];
+    s_dart[j] = first + i;
+}
+
+__global__ void sample_finish_kernel(const int32_t* __restrict__ pos, const int32_t* __restrict__ lastb, int32_t B,
+                                     int64_t first, int64_t max_points, SampleCtl* __restrict__ ctl) {
+    if (ctl->und[kGroup - 1] != 0) return;
+    const bool ended = ctl->end != INT_MAX;
+    const int32_t e = ended ? ctl->end : B;
+    const int32_t l = lastb[e];
+    ctl->n_new = pos[e];
+    ctl->n += pos[e];
+    ctl->miss = l >= 0 ? e - l - 1 : ctl->miss + e;
+    ctl->n_darts = first + e;
+    if (ended) {
+        ctl->stopped = 1;
+        ctl->reason = ctl->n >= max_points ? 2 : 1;
+    }
+    if (ctl->bad < (unsigned long long)(first + e)) ctl->stopped = 3; // a dart the run took
+}
+
+// the batch's new samples into the accepted table
+template <typename T>
+__global__ void sample_insert_kernel(CellMap<T> m, const Pt<T>* __restrict__ s_pts, Table acc, int32_t* __restrict__ s_next,
+                                     int32_t B, const SampleCtl* __restrict__ ctl) {
+    if (ctl->und[kGroup - 1] != 0) return;
+    const int32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= B || k >= ctl->n_new) return;
+    const int64_t j = ctl->n - ctl->n_new + k;
+    table_insert(acc, s_next, key_of(m, s_pts[j]), (int32_t)j);
+}
+
+// every sample again, into a table that was just enlarged
+template <typename T>
+__global__ void sample_rehash_kernel(CellMap<T> m, const Pt<T>* __restrict__ s_pts, Table acc, int32_t* __restrict__ s_next,
+                                     int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride)
+        table_insert(acc, s_next, key_of(m, s_pts[j]), (int32_t)j);
+}
+
+template <typename T>
+__global__ void sample_unpack_kernel(const Pt<T>* __restrict__ pts, int64_t n, T* __restrict__ xyz, T* __restrict__ r) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const Pt<T> p = pts[i];
+        if (xyz) xyz[3 * i] = p.x, xyz[3 * i + 1] = p.y, xyz[3 * i + 2] = p.z;
+        if (r) r[i] = p.w;
+    }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------
+void sample_invalidate(wtp_ctx* ctx) {
+    ctx->sample.valid = false;
+    ctx->sample.n = 0;
+}
+
+static int64_t pow2_at_least(int64_t v) {
+    int64_t p = 2;
+    while (p < v) p <<= 1;
+    return p;
+}
+
+static Table table_view(const DevBuf& b, int64_t tsz) {
+    Table t;
+    t.keys = (unsigned long long*)b.p;
+    t.heads = (int32_t*)((char*)b.p + 8 * (size_t)tsz);
+    t.mask = (uint32_t)(tsz - 1);
+    int lg = 0;
+    while ((int64_t(1) << lg) < tsz) ++lg;
+    t.shift = 64 - lg;
+    return t;
+}
+
+static int32_t scan_tiles(int64_t B) { return (int32_t)((B + 1 + kTile - 1) / kTile); }
+
+// the batch buffers, for B darts
+template <typename T> static int ensure_batch(wtp_ctx* ctx, int64_t B) {
+    SampleState& S = ctx->sample;
+    int rc;
+    if ((rc = ensure(ctx, S.ctl, sizeof(SampleCtl)))) return rc;
+    if (S.bcap >= B && S.dtype == (sizeof(T) == 4 ? WTP_F32 : WTP_F64)) return WTP_OK;
+    const size_t b = (size_t)B;
+    S.b_tsz = pow2_at_least(2 * B);
+    if ((rc = ensure(ctx, S.b_xyz, sizeof(T) * 3 * b))) return rc;
+    if ((rc = ensure(ctx, S.b_h, sizeof(T) * b))) return rc;
+    if ((rc = ensure(ctx, S.b_pts, sizeof(Pt<T>) * b))) return rc;
+    if ((rc = ensure(ctx, S.b_tri, 4 * b))) return rc;
+    if ((rc = ensure(ctx, S.b_st, 4 * b))) return rc;
+    if ((rc = ensure(ctx, S.b_next, 4 * b))) return rc;
+    if ((rc = ensure(ctx, S.b_pos, 4 * (b + 1)))) return rc;
+    if ((rc = ensure(ctx, S.b_last, 4 * (b + 1)))) return rc;
+    if ((rc = ensure(ctx, S.b_blk, sizeof(int2) * 2 * (size_t)scan_tiles(B)))) return rc;
+    if ((rc = ensure(ctx, S.b_table, 12 * (size_t)S.b_tsz))) return rc;
+    S.bcap = B;
+    return WTP_OK;
+}
+
+// a larger buffer that keeps the first `keep` bytes
+static int grow_keep(wtp_ctx* ctx, DevBuf& b, size_t keep, size_t bytes) {
+    if (b.cap >= bytes) return WTP_OK;
+    DevBuf nb;
+    int rc;
+    if ((rc = ensure(ctx, nb, bytes))) return rc;
+    if (keep) WTP_HIP(ctx, hipMemcpyAsync(nb.p, b.p, keep, hipMemcpyDeviceToDevice, ctx->stream));
+    WTP_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the old block is freed when nb leaves this scope
+    b = std::move(nb);
+    return WTP_OK;
+}
+
+static int sm_grid(int64_t n) { return grid_for(n, kSmThreads, 1 << 20); }
+static int sm_stride_grid(int64_t n) { return grid_for(n, kSmThreads, 8192); }
+
+// darts first .. first + n - 1 into the batch buffers: b_xyz, b_tri, b_pts (r = factor h); bad values into ctl->bad
+template <typename T>
+static int enqueue_darts(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, uint64_t seed, int64_t first, int64_t n) {
+    SampleState& S = ctx->sample;
+    const MeshState& M = ctx->mesh;
+    hipLaunchKernelGGL(sample_gen_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream, seed, first, n,
+                       (const T*)M.corners.p, (const double*)M.cum.p, (int32_t)M.nt, M.total_area, (T*)S.b_xyz.p,
+                       (int32_t*)S.b_tri.p);
+    WTP_HIP(ctx, hipGetLastError());
+    const bool law = spacing_on_device(sp->kind);
+    if (law) {
+        const int rc = launch_spacing_eval<T>(ctx, (const T*)S.b_xyz.p, n, 3, ctx->kd.nodes.p, ctx->kd.m, sp->kind, sp->p0,
+                                              sp->p1, sp->p2, (T*)S.b_h.p);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(sample_radius_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream,
+                       (const T*)S.b_xyz.p, law ? (const T*)S.b_h.p : (const T*)nullptr, (T)sp->constant, (T)factor, first, n,
+                       (Pt<T>*)S.b_pts.p, (SampleCtl*)S.ctl.p);
+    WTP_HIP(ctx, hipGetLastError());
+    return WTP_OK;
+}
+
+static int check_sample_args(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, uint64_t seed) {
+    if (ctx->mesh.nt < 1) return fail(ctx, WTP_ERR_STATE, "no mesh: call wtp_mesh_set first");
+    if (!sp) return fail(ctx, WTP_ERR_ARG, "spacing is NULL");
+    if (!(factor > 0) || !std::isfinite(factor)) return fail(ctx, WTP_ERR_ARG, "factor must be positive");
+    if (seed >= (1ull << 24)) return fail(ctx, WTP_ERR_ARG, "seed must be below 2^24 (the stream's key layout)");
+    if (sp->kind == WTP_SPACING_PER_POINT)
+        return fail(ctx, WTP_ERR_ARG, "a per-point spacing array cannot be evaluated at a new position: pass a constant or a device law");
+    if (sp->kind != WTP_SPACING_CONSTANT && !spacing_on_device(sp->kind)) return fail(ctx, WTP_ERR_ARG, "unknown spacing kind");
+    if (spacing_on_device(sp->kind)) {
+        const int rc = check_spacing_law(ctx, sp);
+        if (rc) return rc;
+    }
+    if (!(ctx->mesh.total_area > 0) || !std::isfinite(ctx->mesh.total_area))
+        return fail(ctx, WTP_ERR_ARG, "mesh has zero surface area");
+    return WTP_OK;
+}
+
+static std::string bad_spacing_text(unsigned long long dart) {
+    return "the spacing at dart " + std::to_string(dart) + " is not finite and > 0";
+}
+
+template <typename T>
+static int sample_run(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, int64_t max_points, int64_t stall_limit,
+                      uint64_t seed, int64_t batch, wtp_sample_info* info) {
+    SampleState& S = ctx->sample;
+    const int dtype = sizeof(T) == 4 ? WTP_F32 : WTP_F64;
+    const int64_t syncs0 = ctx->n_syncs;
+    int rc;
+    sample_invalidate(ctx);
+    if (spacing_on_device(sp->kind) && (rc = ensure_kd(ctx, sp, 3, dtype))) return rc;
+    if ((rc = ensure_pinned(ctx, sizeof(SampleCtl)))) return rc;
+    if (S.dtype != dtype) S.cap = 0, S.bcap = 0; // the rows have another size
+    int64_t B = batch > 0 ? batch : kBatchFirst;
+    if ((rc = ensure_batch<T>(ctx, B))) return rc;
+    S.dtype = dtype;
+    SampleCtl h{};
+    h.bad = kEmpty, h.rmin = kEmpty, h.rmax = 0, h.end = INT_MAX;
+    SampleCtl* d_ctl = (SampleCtl*)S.ctl.p;
+    SampleCtl* pin = (SampleCtl*)ctx->host_pinned;
+    *pin = h;
+    WTP_HIP(ctx, hipMemcpyAsync(d_ctl, pin, sizeof(SampleCtl), hipMemcpyHostToDevice, ctx->stream));
+
+    CellMap<T> map{};
+    bool have_map = false;
+    int64_t first = 0, n = 0;
+    int32_t n_batches = 0, rounds_max = 0;
+    for (;;) {
+        if (n + B >= (int64_t(1) << 31) - 1) return fail(ctx, WTP_ERR_ARG, "samples + batch exceed the int32 index space");
+        if ((rc = ensure_batch<T>(ctx, B))) return rc;
+        // room for n + B samples, and a table of at least twice as many slots
+        bool rehash = false;
+        if (n + B > S.cap) {
+            const int64_t cap = std::max(n + B, 2 * S.cap);
+            if ((rc = grow_keep(ctx, S.pts, sizeof(Pt<T>) * (size_t)n, sizeof(Pt<T>) * (size_t)cap))) return rc;
+            if ((rc = grow_keep(ctx, S.tri, 4 * (size_t)n, 4 * (size_t)cap))) return rc;
+            if ((rc = grow_keep(ctx, S.dart, 8 * (size_t)n, 8 * (size_t)cap))) return rc;
+            if ((rc = ensure(ctx, S.next, 4 * (size_t)cap))) return rc; // rebuilt with the table
+            S.tsz = pow2_at_least(2 * cap);
+            if ((rc = ensure(ctx, S.table, 12 * (size_t)S.tsz))) return rc;
+            S.cap = cap;
+            rehash = true;
+        } else if (n_batches == 0) {
+            S.tsz = pow2_at_least(2 * S.cap); // buffers of an earlier call: the table is stale
+            rehash = true;
+        }
+        const Table acc = table_view(S.table, S.tsz), bt = table_view(S.b_table, S.b_tsz);
+        if (rehash) WTP_HIP(ctx, hipMemsetAsync(S.table.p, 0xFF, 12 * (size_t)S.tsz, ctx->stream));
+        if (rehash && n > 0) {
+            hipLaunchKernelGGL(sample_rehash_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream, map,
+                               (const Pt<T>*)S.pts.p, acc, (int32_t*)S.next.p, n);
+            WTP_HIP(ctx, hipGetLastError());
+        }
+        hipLaunchKernelGGL(sample_begin_kernel, dim3(1), dim3(1), 0, ctx->stream, d_ctl);
+        if ((rc = enqueue_darts<T>(ctx, sp, factor, seed, first, B))) return rc;
+        if (!have_map) { // the cell edge: sqrt(r_min r_max) of the first batch (it changes time only)
+            hipLaunchKernelGGL(sample_range_kernel<T>, dim3(sm_stride_grid(B)), dim3(kSmThreads), 0, ctx->stream,
+                               (const Pt<T>*)S.b_pts.p, B, d_ctl);
+            WTP_HIP(ctx, hipMemcpyAsync(pin, d_ctl, sizeof(SampleCtl), hipMemcpyDeviceToHost, ctx->stream));
+            if ((rc = sync(ctx))) return rc;
+            double ext = 0;
+            for (int a = 0; a < 3; ++a) ext = std::max(ext, ctx->mesh.bbox[3 + a] - ctx->mesh.bbox[a]);
+            double c = ext;
+            if (pin->rmin != kEmpty)
+                c = std::sqrt(__builtin_bit_cast(double, pin->rmin) * __builtin_bit_cast(double, pin->rmax));
+            c = std::min(std::max(c, ext / 1.0e6), ext > 0 ? ext : c); // at most 2^20 cells per axis, at least one
+            if (!(c > 0) || !std::isfinite(c)) c = 1;
+            for (int a = 0; a < 3; ++a) {
+                map.org[a] = (T)ctx->mesh.bbox[a];
+                map.nc[a] = (int32_t)std::min(1048575.0, std::floor((ctx->mesh.bbox[3 + a] - ctx->mesh.bbox[a]) / c) + 1);
+            }
+            map.inv_c = (T)(1.0 / c);
+            have_map = true;
+        }
+        WTP_HIP(ctx, hipMemsetAsync(S.b_table.p, 0xFF, 12 * (size_t)S.b_tsz, ctx->stream));
+        const int32_t Bi = (int32_t)B;
+        hipLaunchKernelGGL(sample_cull_kernel<T>, dim3(sm_grid(B)), dim3(kSmThreads), 0, ctx->stream, map,
+                           (const Pt<T>*)S.b_pts.p, Bi, (int32_t*)S.b_st.p, acc, (const int32_t*)S.next.p,
+                           (const Pt<T>*)S.pts.p, n, bt, (int32_t*)S.b_next.p);
+        WTP_HIP(ctx, hipGetLastError());
+        int32_t round0 = 0, rounds = 0;
+        for (;;) {
+            WTP_HIP(ctx, hipMemsetAsync(d_ctl->und, 0, sizeof(h.und), ctx->stream));
+            for (int g = 0; g < kGroup; ++g)
+                hipLaunchKernelGGL(sample_round_kernel<T>, dim3(sm_grid(B)), dim3(kSmThreads), 0, ctx->stream, map,
+                                   (const Pt<T>*)S.b_pts.p, Bi, (int32_t*)S.b_st.p, bt, (const int32_t*)S.b_next.p, g,
+                                   round0 + g + 1, d_ctl);
+            int2* blk = (int2*)S.b_blk.p;
+            const int32_t nblk = scan_tiles(B);
+            hipLaunchKernelGGL(sample_scan_a_kernel, dim3(nblk), dim3(kSmThreads), 0, ctx->stream, (const int32_t*)S.b_st.p, Bi,
+                               blk, d_ctl);
+            hipLaunchKernelGGL(sample_scan_b_kernel, dim3(1), dim3(kSmThreads), 0, ctx->stream, blk, nblk, blk + nblk, d_ctl);
+            hipLaunchKernelGGL(sample_scan_c_kernel, dim3(nblk), dim3(kSmThreads), 0, ctx->stream, (const int32_t*)S.b_st.p, Bi,
+                               blk + nblk, (int32_t*)S.b_pos.p, (int32_t*)S.b_last.p, max_points, stall_limit, d_ctl);
+            hipLaunchKernelGGL(sample_append_kernel<T>, dim3(sm_grid(B)), dim3(kSmThreads), 0, ctx->stream,
+                               (const Pt<T>*)S.b_pts.p, (const int32_t*)S.b_tri.p, (const int32_t*)S.b_st.p, Bi,
+                               (const int32_t*)S.b_pos.p, first, (Pt<T>*)S.pts.p, (int32_t*)S.tri.p, (int64_t*)S.dart.p, d_ctl);
+            hipLaunchKernelGGL(sample_finish_kernel, dim3(1), dim3(1), 0, ctx->stream, (const int32_t*)S.b_pos.p,
+                               (const int32_t*)S.b_last.p, Bi, first, max_points, d_ctl);
+            hipLaunchKernelGGL(sample_insert_kernel<T>, dim3(sm_grid(B)), dim3(kSmThreads), 0, ctx->stream, map,
+                               (const Pt<T>*)S.pts.p, acc, (int32_t*)S.next.p, Bi, d_ctl);
+            WTP_HIP(ctx, hipGetLastError());
+            WTP_HIP(ctx, hipMemcpyAsync(pin, d_ctl, sizeof(SampleCtl), hipMemcpyDeviceToHost, ctx->stream));
+            if ((rc = sync(ctx))) return rc;
+            if (pin->und[kGroup - 1] == 0) {
+                int g = 0;
+                while (pin->und[g] != 0) ++g;
+                rounds = round0 + g + 1;
+                break;
+            }
+            round0 += kGroup;
+            if (round0 >= B) return fail(ctx, WTP_ERR_INTERNAL, "a batch was not decided within as many rounds as it has darts");
+        }
+        ++n_batches;
+        rounds_max = std::max(rounds_max, rounds);
+        if (pin->stopped == 3) return fail(ctx, WTP_ERR_ARG, bad_spacing_text(pin->bad));
+        n = pin->n;
+        if (pin->stopped) break;
+        first += B;
+        if (batch == 0) B = std::min(2 * B, kBatchMax);
+    }
+    // r over the samples
+    h = *pin;
+    pin->rmin = kEmpty, pin->rmax = 0;
+    WTP_HIP(ctx, hipMemcpyAsync(d_ctl, pin, sizeof(SampleCtl), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(sample_range_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream, (const Pt<T>*)S.pts.p,
+                       n, d_ctl);
+    WTP_HIP(ctx, hipGetLastError());
+    WTP_HIP(ctx, hipMemcpyAsync(pin, d_ctl, sizeof(SampleCtl), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = sync(ctx))) return rc;
+    S.n = n;
+    S.valid = true;
+    if (info) {
+        info->n_points = n;
+        info->n_darts = h.n_darts;
+        info->batch = B;
+        info->stop_reason = h.reason;
+        info->n_batches = n_batches;
+        info->rounds_max = rounds_max;
+        info->host_syncs = (int32_t)(ctx->n_syncs - syncs0);
+        info->total_area = ctx->mesh.total_area;
+        info->r_min = pin->rmin != kEmpty ? __builtin_bit_cast(double, pin->rmin) : 0.0;
+        info->r_max = __builtin_bit_cast(double, pin->rmax);
+    }
+    return WTP_OK;
+}
+
+template <typename T>
+static int sample_unpack(wtp_ctx* ctx, const void* pts, int64_t n, T* d_xyz, T* d_r) {
+    hipLaunchKernelGGL(sample_unpack_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream, (const Pt<T>*)pts, n,
+                       d_xyz, d_r);
+    WTP_HIP(ctx, hipGetLastError());
+    return WTP_OK;
+}
+
+template <typename T>
+static int sample_darts(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, uint64_t seed, int64_t first, int64_t n,
+                        T* xyz_out, int32_t* tri_out, T* r_out) {
+    SampleState& S = ctx->sample;
+    const int dtype = sizeof(T) == 4 ? WTP_F32 : WTP_F64;
+    int rc;
+    if (spacing_on_device(sp->kind) && (rc = ensure_kd(ctx, sp, 3, dtype))) return rc;
+    if (S.dtype != dtype) S.cap = 0, S.bcap = 0, S.dtype = dtype; // (a sample of another dtype died with its mesh)
+    const int64_t chunk = std::min(n, kReadChunk);
+    if ((rc = ensure_batch<T>(ctx, std::max(chunk, S.bcap)))) return rc;
+    for (int64_t done = 0; done < n; done += chunk) {
+        const int64_t m = std::min(chunk, n - done);
+        if ((rc = enqueue_darts<T>(ctx, sp, factor, seed, first + done, m))) return rc;
+        if (xyz_out)
+            WTP_HIP(ctx, hipMemcpyAsync(xyz_out + 3 * done, S.b_xyz.p, sizeof(T) * 3 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+        if (tri_out) WTP_HIP(ctx, hipMemcpyAsync(tri_out + done, S.b_tri.p, 4 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+        if (r_out) {
+            if ((rc = sample_unpack<T>(ctx, S.b_pts.p, m, nullptr, (T*)S.b_h.p))) return rc;
+            WTP_HIP(ctx, hipMemcpyAsync(r_out + done, S.b_h.p, sizeof(T) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        if ((rc = sync(ctx))) return rc;
+    }
+    return WTP_OK;
+}
+
+} // namespace wtp
+
+using namespace wtp;
+#define WTP_API extern "C"
+
+WTP_API int wtp_mesh_sample(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, int64_t max_points,
+                            int64_t stall_limit, uint64_t seed, int64_t batch, wtp_sample_info* info) {
+    if (!ctx) return WTP_ERR_ARG;
+    int rc = check_sample_args(ctx, spacing, factor, seed);
+    if (rc) return rc;
+    if (stall_limit < 1) return fail(ctx, WTP_ERR_ARG, "stall_limit must be positive");
+    if (max_points < 1) return fail(ctx, WTP_ERR_ARG, "max_points must be positive");
+    if (batch < 0 || batch > (int64_t(1) << 24)) return fail(ctx, WTP_ERR_ARG, "batch must be in [0, 2^24]");
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    return by_dtype(ctx->mesh.dtype, [&](auto t) {
+        return sample_run<decltype(t)>(ctx, spacing, factor, max_points, stall_limit, seed, batch, info);
+    });
+}
+
+WTP_API int wtp_mesh_sample_get(wtp_ctx* ctx, void* xyz_out, int32_t* tri_out, void* r_out, int64_t* dart_out) {
+    if (!ctx) return WTP_ERR_ARG;
+    SampleState& S = ctx->sample;
+    if (!S.valid) return fail(ctx, WTP_ERR_STATE, "no sample: call wtp_mesh_sample first");
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t ts = tsize(S.dtype), n = (size_t)S.n;
+    int rc;
+    if (xyz_out || r_out) {
+        if ((rc = ensure(ctx, ctx->scratch, ts * 4 * n))) return rc;
+        char* d = (char*)ctx->scratch.p;
+        rc = by_dtype(S.dtype, [&](auto t) {
+            using T = decltype(t);
+            return sample_unpack<T>(ctx, S.pts.p, S.n, (T*)d, (T*)(d + ts * 3 * n));
+        });
+        if (rc) return rc;
+        if (xyz_out) WTP_HIP(ctx, hipMemcpyAsync(xyz_out, d, ts * 3 * n, hipMemcpyDeviceToHost, ctx->stream));
+        if (r_out) WTP_HIP(ctx, hipMemcpyAsync(r_out, d + ts * 3 * n, ts * n, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (tri_out) WTP_HIP(ctx, hipMemcpyAsync(tri_out, S.tri.p, 4 * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (dart_out) WTP_HIP(ctx, hipMemcpyAsync(dart_out, S.dart.p, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
+}
+
+WTP_API int wtp_mesh_sample_get_dev(wtp_ctx* ctx, void* d_xyz_out, int32_t* d_tri_out, void* d_r_out) {
+    if (!ctx) return WTP_ERR_ARG;
+    SampleState& S = ctx->sample;
+    if (!S.valid) return fail(ctx, WTP_ERR_STATE, "no sample: call wtp_mesh_sample first");
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    if (d_xyz_out || d_r_out) {
+        const int rc = by_dtype(S.dtype, [&](auto t) {
+            using T = decltype(t);
+            return sample_unpack<T>(ctx, S.pts.p, S.n, (T*)d_xyz_out, (T*)d_r_out);
+        });
+        if (rc) return rc;
+    }
+    if (d_tri_out) WTP_HIP(ctx, hipMemcpyAsync(d_tri_out, S.tri.p, 4 * (size_t)S.n, hipMemcpyDeviceToDevice, ctx->stream));
+    return sync(ctx);
+}
+
+WTP_API int wtp_mesh_sample_darts(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, uint64_t seed, int64_t first,
+                                  int64_t n, void* xyz_out, int32_t* tri_out, void* r_out) {
+    if (!ctx) return WTP_ERR_ARG;
+    int rc = check_sample_args(ctx, spacing, factor, seed);
+    if (rc) return rc;
+    if (first < 0 || n < 0 || first > (int64_t(1) << 62) - n) return fail(ctx, WTP_ERR_ARG, "bad dart range");
+    if (n == 0) return WTP_OK;
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    return by_dtype(ctx->mesh.dtype, [&](auto t) {
+        using T = decltype(t);
+        return sample_darts<T>(ctx, spacing, factor, seed, first, n, (T*)xyz_out, tri_out, (T*)r_out);
+    });
+}

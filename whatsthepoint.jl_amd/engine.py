@@ -346,6 +346,65 @@ class Context:
             out["inside"] = out["inside"].astype(bool)
         return out
 
+    # ---- graded Poisson-disk sampling of the mesh surface (src/surface_sampling.jl; wtp_mesh_sample) ----------
+    def _mesh_dtype(self):
+        return np.dtype(self._mesh_key[2]) if self._mesh_key else np.dtype(np.float64)
+
+    def _sample_spacing(self, spacing):
+        """wtp_spacing_desc for the sampler: a number (ConstantSpacing) or a device law's dict.  (desc, keepalive)"""
+        if isinstance(spacing, dict):
+            return _law_desc(spacing, self._mesh_dtype(), 3)
+        sd = L.SpacingDesc()
+        sd.kind, sd.constant = L.WTP_SPACING_CONSTANT, float(spacing)
+        return sd, None
+
+    def mesh_sample(self, spacing, factor: float = 0.75, max_points: int = 10_000_000, stall_limit: int = 2000,
+                    seed: int = 0, batch: int = 0, spacing_desc=None):
+        """wtp_mesh_sample on the mesh of mesh_set: the serial dart thrower over the seeded stream, decided in batches on
+        the device.  Returns the info dict; the samples stay on the device (mesh_sample_get).  spacing_desc: a ready
+        L.SpacingDesc instead of `spacing`."""
+        sd, keep = (spacing_desc, None) if spacing_desc is not None else self._sample_spacing(spacing)
+        info = L.SampleInfo()
+        rc = self._lib.wtp_mesh_sample(self._h, C.byref(sd), float(factor), int(max_points), int(stall_limit),
+                                       C.c_uint64(int(seed)), int(batch), C.byref(info))
+        L.check(self._h, rc)
+        del keep
+        return {name: getattr(info, name) for name, _ in L.SampleInfo._fields_}
+
+    def mesh_sample_get(self, n: int, want=("xyz", "tri", "r", "dart")):
+        """The n = info['n_points'] samples of the last mesh_sample as a dict of host arrays (mesh dtype)."""
+        dt = self._mesh_dtype()
+        out = {}
+        if "xyz" in want:
+            out["xyz"] = np.empty((n, 3), dtype=dt)
+        if "tri" in want:
+            out["tri"] = np.empty(n, dtype=np.int32)
+        if "r" in want:
+            out["r"] = np.empty(n, dtype=dt)
+        if "dart" in want:
+            out["dart"] = np.empty(n, dtype=np.int64)
+        rc = self._lib.wtp_mesh_sample_get(self._h, _vp(out.get("xyz")), _vp(out.get("tri")), _vp(out.get("r")),
+                                           _vp(out.get("dart")))
+        L.check(self._h, rc)
+        return out
+
+    def mesh_sample_get_dev(self, d_xyz_ptr: int = 0, d_tri_ptr: int = 0, d_r_ptr: int = 0):
+        """wtp_mesh_sample_get_dev: the samples into device arrays given as addresses (0 = absent)."""
+        rc = self._lib.wtp_mesh_sample_get_dev(self._h, C.c_void_p(d_xyz_ptr or None), C.c_void_p(d_tri_ptr or None),
+                                               C.c_void_p(d_r_ptr or None))
+        L.check(self._h, rc)
+
+    def mesh_sample_darts(self, spacing, factor: float, seed: int, first: int, n: int):
+        """wtp_mesh_sample_darts: darts first .. first + n - 1 as the sampler makes them: (xyz, tri, r)."""
+        sd, keep = self._sample_spacing(spacing)
+        dt = self._mesh_dtype()
+        xyz, tri, r = np.empty((n, 3), dtype=dt), np.empty(n, dtype=np.int32), np.empty(n, dtype=dt)
+        rc = self._lib.wtp_mesh_sample_darts(self._h, C.byref(sd), float(factor), C.c_uint64(int(seed)), int(first), int(n),
+                                             _vp(xyz), _vp(tri), _vp(r))
+        L.check(self._h, rc)
+        del keep
+        return xyz, tri, r
+
     def set_stream(self, stream_handle=None):
         """Run the library on a caller-owned HIP stream (handle as an int; 0 = the device's default
         stream, which is torch's current stream unless the caller switched); None = own stream."""
