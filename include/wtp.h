@@ -338,7 +338,8 @@ typedef struct wtp_sample_info {
     int32_t n_batches, rounds_max, host_syncs;
     double total_area, r_min, r_max;    /* r over the samples */
 } wtp_sample_info;
-/* Samples the mesh of wtp_mesh_set; the result stays on the device until the next call / wtp_mesh_set / wtp_mesh_clear. */
+/* Samples the mesh of wtp_mesh_set; the result stays on the device until the next call / wtp_mesh_fill (which shares the
+ * buffers) / wtp_mesh_set / wtp_mesh_clear. */
 int wtp_mesh_sample(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, int64_t max_points,
                     int64_t stall_limit, uint64_t seed, int64_t batch, wtp_sample_info* info);
 /* n_points rows (xyz_out n x 3 and r_out of the mesh's dtype); every output may be NULL.  dart_out: the dart index each
@@ -350,6 +351,57 @@ int wtp_mesh_sample_get_dev(wtp_ctx* ctx, void* d_xyz_out, int32_t* d_tri_out, v
  * values are returned as computed, a spacing that is not > 0 included.  Leaves a resident sample untouched.  */
 int wtp_mesh_sample_darts(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, uint64_t seed,
                           int64_t first, int64_t n, void* xyz_out, int32_t* tri_out, void* r_out);
+
+/* ---- graded Poisson-disk fill of the mesh's volume ----------------------------------------------
+ * Replaces the point placement of discretize(bnd, spacing; alg = Orthtree(mesh; spacing, placement = :bridson), max_points)
+ * (src/discretization/algorithms/octree.jl:804-902): volume points under ||x_i - x_j|| >= min(r_i, r_j), r = factor h(x),
+ * against each other and against the boundary points (the seeds).  The reference's advancing front is serial and draws
+ * from rand(); here, as for the surface, the darts are a seeded counter-based stream over the mesh's bounding box and the
+ * result is DEFINED as the serial loop over that stream.  All arithmetic is in the mesh's type T, no contraction:
+ *   Dart j = 0, 1, ... (64-bit) of seed s < 2^24: w_a = splitmix64((s << 40) + 3 j + a), u_a = T(float(w_a >> 40) 2^-24)
+ * (point j of wtp_gen_uniform_dev's dim-3 stream), position c_a = lo_a + u_a (hi_a - lo_a), a = 0, 1, 2, with {lo, hi} the
+ * mesh's vertex bounding box as wtp_mesh_set holds it (wtp_mesh_bounds), in T.
+ *   r = T(factor) h(c), the spacing law evaluated at c in T as wtp_mesh_sample does.  Kinds: CONSTANT, LOGLIKE,
+ * BOUNDARY_LAYER.
+ *   A dart is inside iff wtp_mesh_query's inside flag holds for c: in the box, closest-feature pseudonormal side < 0,
+ * distance > 0.  Only an inside dart is a candidate; the spacing value of a dart that is not inside is never looked at.
+ *   Points p and q conflict when ((dx^2 + dy^2) + dz^2) < m m, m = min(r_p, r_q).
+ *   Seeds: n_seeds points (host, n_seeds x 3 of T; NULL / 0 for none), r = T(factor) h(seed) under the same law.  They
+ * occupy space from the start, are never tested against each other, are not returned and may lie on or outside the box.
+ *   Run.  Darts are taken in order.  Before each dart the run ends if max_points darts have been accepted (stop_reason 2)
+ * or the last stall_limit darts were all rejected (stop_reason 1); n_darts counts the darts taken and n_inside those of
+ * them that were inside.  A dart is accepted iff it is a candidate and conflicts with no seed and no earlier accepted dart;
+ * any other dart is a miss, one outside the domain included.  The result is the accepted darts in dart order; it does not
+ * depend on batch or on arrival order and uses no floating-point atomics: two calls return the same bits, and a smaller
+ * max_points returns a prefix.  A run that ends with no point returns WTP_OK with n_points = 0.
+ *   bbox_volume n_inside / n_darts is the run's own estimate of the domain's volume.  The stream is uniform over the box:
+ * there is no thinning by h, no node octree, no max_growth limiter and no 2-D.
+ *   WTP_ERR_ARG: a spacing value that is not finite and > 0 at a seed (naming the seed) or at an inside dart the run takes
+ * (naming the smallest such dart; such a value at any other dart is no error); a seed coordinate that is not finite;
+ * n_seeds < 0, or seeds NULL with n_seeds > 0; and every row of wtp_mesh_sample: factor, stall_limit, max_points, seed,
+ * batch, kind WTP_SPACING_PER_POINT, a mesh of no area.  WTP_ERR_STATE and WTP_ERR_INTERNAL as for wtp_mesh_sample.
+ *   State.  The surface sample and the volume fill share their device buffers: wtp_mesh_sample voids a resident fill and
+ * wtp_mesh_fill a resident sample, once its arguments have passed, and the other's *_get* is WTP_ERR_STATE after that.  */
+typedef struct wtp_fill_info {
+    int64_t n_points, n_darts, n_inside, n_seeds, batch; /* batch: the size used in the last batch */
+    int32_t stop_reason;                                 /* 1 stall_limit misses in a row, 2 max_points */
+    int32_t n_batches, rounds_max, host_syncs;
+    double bbox_volume, r_min, r_max;                    /* r over the accepted points (0 when there are none) */
+} wtp_fill_info;
+/* Fills the mesh of wtp_mesh_set; the result stays on the device until the next wtp_mesh_fill / wtp_mesh_sample /
+ * wtp_mesh_set / wtp_mesh_clear.  seeds: host array of the mesh's dtype.  */
+int wtp_mesh_fill(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, const void* seeds, int64_t n_seeds,
+                  int64_t max_points, int64_t stall_limit, uint64_t seed, int64_t batch, wtp_fill_info* info);
+/* n_points rows (xyz_out n x 3 and r_out of the mesh's dtype); every output may be NULL.  dart_out: the dart index each
+ * point came from.  */
+int wtp_mesh_fill_get(wtp_ctx* ctx, void* xyz_out, void* r_out, int64_t* dart_out);
+/* The same into device memory.  */
+int wtp_mesh_fill_get_dev(wtp_ctx* ctx, void* d_xyz_out, void* d_r_out);
+/* Read-out, no acceptance: darts first .. first + n - 1 as the rule above makes them (host outputs, may be NULL); inside_out
+ * one byte per dart.  r is returned as computed for every dart, a spacing that is not > 0 included.  Leaves a resident
+ * sample or fill untouched.  */
+int wtp_mesh_fill_darts(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, uint64_t seed, int64_t first,
+                        int64_t n, void* xyz_out, uint8_t* inside_out, void* r_out);
 
 /* ---- consumers of the k-NN rows ------------------------------------
  * Replaces compute_normals(points; k) / update_normals! (src/normals.jl:15-69): per point the

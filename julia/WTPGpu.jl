@@ -96,6 +96,33 @@ function metrics(cloud; k::Int = 20)
             separation = st.nn_min, fill = st.nn_max, mesh_ratio = st.nn_min > 0 ? st.nn_max / st.nn_min : Inf)
 end
 
+# ---- the Bridson placement of discretize (src/discretization/algorithms/octree.jl:804-902) on the device ----------------
+# (include/wtp.h: wtp_mesh_fill; the mesh is the one wtp_mesh_set holds)
+mutable struct FillInfo
+    n_points::Int64; n_darts::Int64; n_inside::Int64; n_seeds::Int64; batch::Int64
+    stop_reason::Int32; n_batches::Int32; rounds_max::Int32; host_syncs::Int32
+    bbox_volume::Float64; r_min::Float64; r_max::Float64
+    FillInfo() = new()
+end
+
+# sd: the SpacingDesc of a ConstantSpacing, LogLike or BoundaryLayerSpacing; seeds: the boundary points (may be empty),
+# of the mesh's eltype T.  Returns (volume points as SVector{3,T}, their r, info).
+function fill_volume(sd::SpacingDesc, seeds, ::Type{T}; factor = 0.75, max_points::Int = 10_000_000, stall_limit::Int = 2000,
+                     seed::Integer = 0) where {T}
+    xs = isempty(seeds) ? SVector{3, T}[] : raw(seeds)
+    info = FillInfo()
+    check(context(), ccall((:wtp_mesh_fill, lib), Cint,
+        (Ptr{Cvoid}, Ref{SpacingDesc}, Float64, Ptr{Cvoid}, Int64, Int64, Int64, UInt64, Int64, Ref{FillInfo}),
+        context(), sd, Float64(factor), isempty(xs) ? C_NULL : xs, length(xs), max_points, stall_limit, UInt64(seed), 0, info))
+    n = info.n_points
+    vol = Vector{SVector{3, T}}(undef, n); rs = Vector{T}(undef, n)
+    check(context(), ccall((:wtp_mesh_fill_get, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}),
+        context(), vol, rs, C_NULL))
+    info.stop_reason == 2 &&
+        @warn "Bridson front truncated by max_points before saturation — parts of the domain may be unfilled" max_points
+    return vol, rs, info
+end
+
 # ---- src/normals.jl:75-161 and src/surface_operations.jl:58-94: the graph part on the device ------------------------
 # (include/wtp.h: wtp_orient_normals, wtp_normal_components)
 mutable struct NormalGraphInfo

@@ -366,8 +366,11 @@ struct MeshState {
 
 // Poisson-disk surface sampling (wtp_sample.hip): the accepted samples and their cell table stay on the device between
 // wtp_mesh_sample and the wtp_mesh_sample_get* calls; the batch buffers are reused by every batch and by the dart read-out.
+// wtp_mesh_fill runs in the same buffers (its seeds at the front of the accepted array), so one result is resident at a time.
 struct SampleState {
-    bool valid = false;            // a sample of the current mesh is resident
+    bool valid = false;            // a result of the current mesh is resident ...
+    bool fill = false;             // ... and it is wtp_mesh_fill's, behind n_seeds seed rows
+    int64_t n_seeds = 0;
     int dtype = -1;
     int64_t n = 0, cap = 0;        // samples held, rows the arrays below have room for
     DevBuf pts, tri, dart, next;   // per sample: {x, y, z, r} (Pt), parent triangle, dart index, next sample of its cell
@@ -375,6 +378,7 @@ struct SampleState {
     int64_t tsz = 0;
     int64_t bcap = 0;              // darts the batch buffers have room for
     DevBuf b_xyz, b_h, b_pts, b_tri, b_st, b_next, b_pos, b_last, b_table, b_blk;
+    DevBuf b_in;                   // wtp_mesh_fill: the domain test's flag per dart
     int64_t b_tsz = 0;
     DevBuf ctl;                    // one SampleCtl
 };
@@ -687,6 +691,12 @@ int launch_normal_graph_apply(wtp_ctx* ctx, T* d_nrm, int64_t n, int dim, const 
                               unsigned long long* d_ctl);
 // wtp_sample.hip: a new or cleared mesh voids the resident sample
 void sample_invalidate(wtp_ctx* ctx);
+// wtp_mesh_query's inside flag for n device points of the mesh's own type (wtp_mesh.hip): the domain test of wtp_mesh_fill
+template <typename T> int launch_mesh_inside(wtp_ctx* ctx, const T* d_xyz, int64_t n, uint8_t* d_inside);
+// the mesh's inside/outside class grid with cells of about `cell` (kept if one about as fine exists), and the number of
+// cells such a grid has: one exact test each, which launch_mesh_inside then saves every point of a one-sided cell
+int mesh_ensure_classes(wtp_ctx* ctx, double cell);
+int64_t mesh_class_cells(const wtp_ctx* ctx, double cell);
 // wall rule of the octree method (wtp_mesh.hip)
 template <typename TP>
 int launch_mesh_constrain(wtp_ctx* ctx, const Pt<TP>* old, Pt<TP>* cur, int64_t n, int64_t n_fixed, double offset,

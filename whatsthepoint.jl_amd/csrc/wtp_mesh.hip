@@ -587,6 +587,34 @@ mesh_query_kernel(const TP* __restrict__ xyz, int64_t n, MeshView<TM> mv, TM off
     }
 }
 
+// mesh_query_kernel's inside flag alone, for points of the mesh's own type (the darts of wtp_mesh_fill).  A point outside
+// the box is outside without a search, and one whose class-grid cell lies wholly on one side of the surface takes the
+// cell's answer (the grid is conservative: the flag is the exact test's); whole waves enter the walk or skip it.
+template <typename T>
+__global__ void __launch_bounds__(kMeshThreads)
+mesh_inside_kernel(const T* __restrict__ xyz, int64_t n, MeshView<T> mv, uint8_t* __restrict__ inside_out) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t span = (n + 63) / 64 * 64;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < span; i += stride) {
+        const bool active = i < n;
+        const int64_t ii = active ? i : n - 1;
+        const T q[3] = {xyz[3 * ii], xyz[3 * ii + 1], xyz[3 * ii + 2]};
+        const bool boxed = in_bbox<T>(mv, q);
+        const uint8_t cls = (active && boxed && mv.cls) ? cell_class<T>(mv, q) : (uint8_t)CLS_BOUNDARY;
+        const bool search = active && boxed && cls == CLS_BOUNDARY;
+        Nearest<T> r;
+        r.tri = -1;
+        r.d2 = (T)1;
+        if (__any(search)) {
+            int32_t bn = -1;
+            r = mesh_nearest_guess<T>(mv.nodes, mv.m, q, search, mv.scale, search ? mesh_greedy_guess<T>(mv.nodes, mv.m, q) : -1, &bn);
+        }
+        if (!active) continue;
+        inside_out[i] = (boxed && (cls == CLS_INTERIOR ||
+                                   (cls == CLS_BOUNDARY && r.tri >= 0 && side_of<T>(mv, q, r) < (T)0 && r.d2 > (T)0))) ? 1 : 0;
+    }
+}
+
 // The wall rule after a sweep (src/repel.jl:448-469).  old = the sweep's query buffer (x_i), cur = its
 // output (x_proposed), same slot order.  Boundary points land on the mesh; volume points that left
 // the domain go back to x_i and are flagged.
@@ -677,6 +705,15 @@ static int launch_mesh_query(wtp_ctx* ctx, const TP* d_xyz, int64_t n, double of
     WTP_HIP(ctx, hipGetLastError());
     return WTP_OK;
 }
+
+template <typename T> int launch_mesh_inside(wtp_ctx* ctx, const T* d_xyz, int64_t n, uint8_t* d_inside) {
+    hipLaunchKernelGGL((mesh_inside_kernel<T>), dim3(mesh_grid(n)), dim3(kMeshThreads), 0, ctx->stream, d_xyz, n,
+                       make_view<T>(ctx), d_inside);
+    WTP_HIP(ctx, hipGetLastError());
+    return WTP_OK;
+}
+template int launch_mesh_inside<float>(wtp_ctx*, const float*, int64_t, uint8_t*);
+template int launch_mesh_inside<double>(wtp_ctx*, const double*, int64_t, uint8_t*);
 
 template <typename TP>
 int launch_mesh_constrain(wtp_ctx* ctx, const Pt<TP>* old, Pt<TP>* cur, int64_t n, int64_t n_fixed, double offset,
@@ -866,6 +903,22 @@ WTP_API int wtp_mesh_query(wtp_ctx* ctx, const void* xyz, int64_t n, int dtype, 
     WTP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return WTP_OK;
 }
+
+namespace wtp {
+int mesh_ensure_classes(wtp_ctx* ctx, double cell) {
+    return ctx->mesh.dtype == WTP_F32 ? mesh_classes_t<float>(ctx, cell) : mesh_classes_t<double>(ctx, cell);
+}
+
+int64_t mesh_class_cells(const wtp_ctx* ctx, double cell) { // the count mesh_classes_t arrives at
+    double ext[3], vol = 1;
+    for (int a = 0; a < 3; ++a) vol *= (ext[a] = ctx->mesh.bbox[3 + a] - ctx->mesh.bbox[a]);
+    const double floor_cell = std::cbrt(vol / 67108864.0);
+    if (!(cell > floor_cell)) cell = floor_cell;
+    int64_t ncell = 1;
+    for (int a = 0; a < 3; ++a) ncell *= std::max<int64_t>(1, (int64_t)std::ceil(ext[a] / cell));
+    return ncell;
+}
+} // namespace wtp
 
 // Installs the wall rule of the octree method on the current relax session: from now on every sweep
 // is followed by _constrain_octree (src/repel.jl:448-469).  Movable points with index below

@@ -28,6 +28,11 @@
 // widened by the rounding of its own bounds, so nothing rests on one point per cell or on an r_min known in advance.  A
 // ball that touches more cells than there are points scans the points instead.  The chain order depends on arrival;
 // nothing read from a chain does (a conflict exists or not).  The cell edge is sqrt(r_min r_max) of the first batch.
+//
+// The volume fill (wtp_mesh_fill) is the same run over another stream: darts uniform in the mesh's
+// bounding box, of which only those inside the mesh (wtp_mesh_query's flag, wtp_mesh.hip) may be taken, and seed points
+// that occupy space from the start.  The seeds sit at the front of the accepted array and in its table; the counts the
+// stop rule carries are of accepted darts alone.  Everything from the cull to the insertion is the sampler's.
 #include <climits>
 #include <cmath>
 
@@ -57,6 +62,7 @@ struct SampleCtl {
     int32_t end;                   // batch-local index of the first dart the run does not take (INT_MAX: none)
     int32_t n_new;                 // samples the batch appended
     int32_t und[kGroup];           // darts left undecided by each round of the group
+    unsigned long long n_inside;   // wtp_mesh_fill: darts taken so far that were inside the mesh
 };
 
 template <typename T> struct CellMap {
@@ -190,19 +196,35 @@ __global__ void sample_gen_kernel(uint64_t seed, int64_t first, int64_t n, const
     }
 }
 
+// the volume fill's darts: point j of wtp_gen_uniform_dev's dim-3 stream, scaled into the box [lo, hi]
+template <typename T> struct Box3 { T lo[3], hi[3]; };
+
+template <typename T>
+__global__ void fill_gen_kernel(uint64_t seed, int64_t first, int64_t n, Box3<T> box, T* __restrict__ xyz) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t base = (seed << 40) + 3ull * (uint64_t)(first + i);
+        for (int a = 0; a < 3; ++a) {
+            const T u = (T)((float)(sm_splitmix64(base + a) >> 40) * (1.0f / 16777216.0f));
+            xyz[3 * i + a] = box.lo[a] + u * (box.hi[a] - box.lo[a]);
+        }
+    }
+}
+
 template <typename T> __device__ inline bool good_value(T v) { return v > (T)0 && v < Lim<T>::inf(); }
 
-// r = T(factor) h; a spacing value that is not finite and > 0 is reported by the smallest dart index
+// r = T(factor) h; a spacing value that is not finite and > 0 is reported by the smallest dart index (report = false: the
+// cull reports it, for the darts that may be taken)
 template <typename T>
 __global__ void sample_radius_kernel(const T* __restrict__ xyz, const T* __restrict__ h, T h_const, T factor, int64_t first,
-                                     int64_t n, Pt<T>* __restrict__ pts, SampleCtl* __restrict__ ctl) {
+                                     int64_t n, Pt<T>* __restrict__ pts, bool report, SampleCtl* __restrict__ ctl) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const T hv = h ? h[i] : h_const;
         Pt<T> p;
         p.x = xyz[3 * i], p.y = xyz[3 * i + 1], p.z = xyz[3 * i + 2], p.w = factor * hv;
         pts[i] = p;
-        if (!(good_value(hv) && good_value(p.w))) atomicMin(&ctl->bad, (unsigned long long)(first + i));
+        if (report && !(good_value(hv) && good_value(p.w))) atomicMin(&ctl->bad, (unsigned long long)(first + i));
     }
 }
 
@@ -243,11 +265,16 @@ __global__ void sample_begin_kernel(SampleCtl* __restrict__ ctl) {
 template <typename T>
 __global__ void sample_cull_kernel(CellMap<T> m, const Pt<T>* __restrict__ b_pts, int32_t B, int32_t* __restrict__ st,
                                    Table acc, const int32_t* __restrict__ s_next, const Pt<T>* __restrict__ s_pts,
-                                   int64_t n_acc, Table bt, int32_t* __restrict__ b_next) {
+                                   int64_t n_acc, Table bt, int32_t* __restrict__ b_next,
+                                   const uint8_t* __restrict__ inside, int64_t first, SampleCtl* __restrict__ ctl) {
     const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B) return;
     const Pt<T> p = b_pts[i];
     bool dead = !good_value(p.w); // a bad spacing value: never sampled with (the stop scan decides whether it is an error)
+    if (inside) { // the volume fill: a dart outside the mesh is a miss whatever its spacing value; one inside reports a bad one
+        if (!inside[i]) dead = true;
+        else if (dead) atomicMin(&ctl->bad, (unsigned long long)(first + i));
+    }
     if (!dead)
         for_near<T>(m, acc, s_next, s_pts, n_acc, p, [&](int32_t, const Pt<T>& q) { return dead = conflict<T>(p, q); });
     st[i] = dead ? kCulled : 0;
@@ -373,15 +400,24 @@ __global__ void sample_scan_c_kernel(const int32_t* __restrict__ st, int32_t B, 
 template <typename T>
 __global__ void sample_append_kernel(const Pt<T>* __restrict__ b_pts, const int32_t* __restrict__ b_tri,
                                      const int32_t* __restrict__ st, int32_t B, const int32_t* __restrict__ pos, int64_t first,
-                                     Pt<T>* __restrict__ s_pts, int32_t* __restrict__ s_tri, int64_t* __restrict__ s_dart,
-                                     const SampleCtl* __restrict__ ctl) {
+                                     int64_t off, Pt<T>* __restrict__ s_pts, int32_t* __restrict__ s_tri,
+                                     int64_t* __restrict__ s_dart, const SampleCtl* __restrict__ ctl) {
     if (ctl->und[kGroup - 1] != 0) return;
     const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B || i >= ctl->end || !(st[i] & 1)) return;
-    const int64_t j = ctl->n + pos[i]; // dart order
+    const int64_t j = off + ctl->n + pos[i]; // dart order, behind the fill's `off` seeds
     s_pts[j] = b_pts[i];
-    s_tri[j] = b_tri[i];
+    if (b_tri) s_tri[j] = b_tri[i];
     s_dart[j] = first + i;
+}
+
+// wtp_mesh_fill: the darts before the batch's end that were inside the mesh (integer count, one atomic per block)
+__global__ void fill_count_kernel(const uint8_t* __restrict__ inside, int32_t B, SampleCtl* __restrict__ ctl) {
+    if (ctl->und[kGroup - 1] != 0) return;
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int32_t e = ctl->end < B ? ctl->end : B;
+    const int cnt = __syncthreads_count(i < e && inside[i < e ? i : 0] != 0);
+    if (threadIdx.x == 0 && cnt > 0) atomicAdd(&ctl->n_inside, (unsigned long long)cnt);
 }
 
 __global__ void sample_finish_kernel(const int32_t* __restrict__ pos, const int32_t* __restrict__ lastb, int32_t B,
@@ -404,11 +440,11 @@ __global__ void sample_finish_kernel(const int32_t* __restrict__ pos, const int3
 // the batch's new samples into the accepted table
 template <typename T>
 __global__ void sample_insert_kernel(CellMap<T> m, const Pt<T>* __restrict__ s_pts, Table acc, int32_t* __restrict__ s_next,
-                                     int32_t B, const SampleCtl* __restrict__ ctl) {
+                                     int32_t B, int64_t off, const SampleCtl* __restrict__ ctl) {
     if (ctl->und[kGroup - 1] != 0) return;
     const int32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= B || k >= ctl->n_new) return;
-    const int64_t j = ctl->n - ctl->n_new + k;
+    const int64_t j = off + ctl->n - ctl->n_new + k;
     table_insert(acc, s_next, key_of(m, s_pts[j]), (int32_t)j);
 }
 
@@ -434,7 +470,9 @@ __global__ void sample_unpack_kernel(const Pt<T>* __restrict__ pts, int64_t n, T
 // ---- host side -----------------------------------------------------------------------------------------------------------
 void sample_invalidate(wtp_ctx* ctx) {
     ctx->sample.valid = false;
+    ctx->sample.fill = false;
     ctx->sample.n = 0;
+    ctx->sample.n_seeds = 0;
 }
 
 static int64_t pow2_at_least(int64_t v) {
@@ -474,6 +512,7 @@ template <typename T> static int ensure_batch(wtp_ctx* ctx, int64_t B) {
     if ((rc = ensure(ctx, S.b_last, 4 * (b + 1)))) return rc;
     if ((rc = ensure(ctx, S.b_blk, sizeof(int2) * 2 * (size_t)scan_tiles(B)))) return rc;
     if ((rc = ensure(ctx, S.b_table, 12 * (size_t)S.b_tsz))) return rc;
+    if ((rc = ensure(ctx, S.b_in, b))) return rc;
     S.bcap = B;
     return WTP_OK;
 }
@@ -493,15 +532,27 @@ static int grow_keep(wtp_ctx* ctx, DevBuf& b, size_t keep, size_t bytes) {
 static int sm_grid(int64_t n) { return grid_for(n, kSmThreads, 1 << 20); }
 static int sm_stride_grid(int64_t n) { return grid_for(n, kSmThreads, 8192); }
 
-// darts first .. first + n - 1 into the batch buffers: b_xyz, b_tri, b_pts (r = factor h); bad values into ctl->bad
+// darts first .. first + n - 1 into the batch buffers: b_xyz, b_tri, b_pts (r = factor h); bad values into ctl->bad.
+// fill: the volume fill's darts instead, b_in (inside the mesh) in place of b_tri, and bad values left to the cull.
 template <typename T>
-static int enqueue_darts(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, uint64_t seed, int64_t first, int64_t n) {
+static int enqueue_darts(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, uint64_t seed, int64_t first, int64_t n,
+                         bool fill) {
     SampleState& S = ctx->sample;
     const MeshState& M = ctx->mesh;
-    hipLaunchKernelGGL(sample_gen_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream, seed, first, n,
-                       (const T*)M.corners.p, (const double*)M.cum.p, (int32_t)M.nt, M.total_area, (T*)S.b_xyz.p,
-                       (int32_t*)S.b_tri.p);
-    WTP_HIP(ctx, hipGetLastError());
+    if (fill) {
+        Box3<T> box;
+        for (int a = 0; a < 3; ++a) box.lo[a] = (T)M.bbox[a], box.hi[a] = (T)M.bbox[3 + a];
+        hipLaunchKernelGGL(fill_gen_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream, seed, first, n, box,
+                           (T*)S.b_xyz.p);
+        WTP_HIP(ctx, hipGetLastError());
+        const int rc = launch_mesh_inside<T>(ctx, (const T*)S.b_xyz.p, n, (uint8_t*)S.b_in.p);
+        if (rc) return rc;
+    } else {
+        hipLaunchKernelGGL(sample_gen_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream, seed, first, n,
+                           (const T*)M.corners.p, (const double*)M.cum.p, (int32_t)M.nt, M.total_area, (T*)S.b_xyz.p,
+                           (int32_t*)S.b_tri.p);
+        WTP_HIP(ctx, hipGetLastError());
+    }
     const bool law = spacing_on_device(sp->kind);
     if (law) {
         const int rc = launch_spacing_eval<T>(ctx, (const T*)S.b_xyz.p, n, 3, ctx->kd.nodes.p, ctx->kd.m, sp->kind, sp->p0,
@@ -510,7 +561,7 @@ static int enqueue_darts(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor
     }
     hipLaunchKernelGGL(sample_radius_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream,
                        (const T*)S.b_xyz.p, law ? (const T*)S.b_h.p : (const T*)nullptr, (T)sp->constant, (T)factor, first, n,
-                       (Pt<T>*)S.b_pts.p, (SampleCtl*)S.ctl.p);
+                       (Pt<T>*)S.b_pts.p, !fill, (SampleCtl*)S.ctl.p);
     WTP_HIP(ctx, hipGetLastError());
     return WTP_OK;
 }
@@ -536,9 +587,66 @@ static std::string bad_spacing_text(unsigned long long dart) {
     return "the spacing at dart " + std::to_string(dart) + " is not finite and > 0";
 }
 
+// room for `rows` accepted rows of which the first `keep` hold data, and a table of at least twice as many slots;
+// *rehash: the table was replaced
+template <typename T> static int ensure_rows(wtp_ctx* ctx, int64_t keep, int64_t rows, bool* rehash) {
+    SampleState& S = ctx->sample;
+    if (rows <= S.cap) return WTP_OK;
+    int rc;
+    const int64_t cap = std::max(rows, 2 * S.cap);
+    if ((rc = grow_keep(ctx, S.pts, sizeof(Pt<T>) * (size_t)keep, sizeof(Pt<T>) * (size_t)cap))) return rc;
+    if ((rc = grow_keep(ctx, S.tri, 4 * (size_t)keep, 4 * (size_t)cap))) return rc;
+    if ((rc = grow_keep(ctx, S.dart, 8 * (size_t)keep, 8 * (size_t)cap))) return rc;
+    if ((rc = ensure(ctx, S.next, 4 * (size_t)cap))) return rc; // rebuilt with the table
+    S.tsz = pow2_at_least(2 * cap);
+    if ((rc = ensure(ctx, S.table, 12 * (size_t)S.tsz))) return rc;
+    S.cap = cap;
+    *rehash = true;
+    return WTP_OK;
+}
+
+// The fill's seeds into the front of the accepted array: r = T(factor) h(seed), every one checked.
+template <typename T>
+static int fill_seeds(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, const T* seeds, int64_t ns) {
+    SampleState& S = ctx->sample;
+    for (int64_t i = 0; i < 3 * ns; ++i)
+        if (!std::isfinite(seeds[i])) return fail(ctx, WTP_ERR_ARG, "seed " + std::to_string(i / 3) + " has a coordinate that is not finite");
+    std::vector<T> h((size_t)ns, (T)sp->constant);
+    int rc;
+    if (spacing_on_device(sp->kind)) {
+        if ((rc = ensure(ctx, ctx->scratch, sizeof(T) * 4 * (size_t)ns))) return rc;
+        T* d_xyz = (T*)ctx->scratch.p;
+        T* d_h = d_xyz + 3 * ns;
+        WTP_HIP(ctx, hipMemcpyAsync(d_xyz, seeds, sizeof(T) * 3 * (size_t)ns, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = launch_spacing_eval<T>(ctx, d_xyz, ns, 3, ctx->kd.nodes.p, ctx->kd.m, sp->kind, sp->p0, sp->p1, sp->p2, d_h)))
+            return rc;
+        WTP_HIP(ctx, hipMemcpyAsync(h.data(), d_h, sizeof(T) * (size_t)ns, hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = sync(ctx))) return rc;
+    }
+    std::vector<Pt<T>> rows((size_t)ns);
+    const T f = (T)factor;
+    for (int64_t i = 0; i < ns; ++i) {
+        Pt<T> p;
+        p.x = seeds[3 * i], p.y = seeds[3 * i + 1], p.z = seeds[3 * i + 2], p.w = f * h[i];
+        if (!(h[i] > 0 && std::isfinite(h[i]) && p.w > 0 && std::isfinite(p.w)))
+            return fail(ctx, WTP_ERR_ARG, "the spacing at seed " + std::to_string(i) + " is not finite and > 0");
+        rows[i] = p;
+    }
+    WTP_HIP(ctx, hipMemcpyAsync(S.pts.p, rows.data(), sizeof(Pt<T>) * (size_t)ns, hipMemcpyHostToDevice, ctx->stream));
+    return sync(ctx); // `rows` leaves this scope
+}
+
+// what a run reports: the fields of wtp_sample_info and wtp_fill_info
+struct RunInfo {
+    int64_t n_points, n_darts, n_inside, batch;
+    int32_t stop_reason, n_batches, rounds_max, host_syncs;
+    double r_min, r_max;
+};
+
+// The run of wtp_mesh_sample (fill = false) or wtp_mesh_fill (fill = true, with ns seeds in the mesh's type).
 template <typename T>
 static int sample_run(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, int64_t max_points, int64_t stall_limit,
-                      uint64_t seed, int64_t batch, wtp_sample_info* info) {
+                      uint64_t seed, int64_t batch, bool fill, const T* seeds, int64_t ns, RunInfo* info) {
     SampleState& S = ctx->sample;
     const int dtype = sizeof(T) == 4 ? WTP_F32 : WTP_F64;
     const int64_t syncs0 = ctx->n_syncs;
@@ -550,6 +658,12 @@ static int sample_run(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, i
     int64_t B = batch > 0 ? batch : kBatchFirst;
     if ((rc = ensure_batch<T>(ctx, B))) return rc;
     S.dtype = dtype;
+    if (ns > 0) {
+        bool replaced = false;
+        if (ns + B >= (int64_t(1) << 31) - 1) return fail(ctx, WTP_ERR_ARG, "seeds + batch exceed the int32 index space");
+        if ((rc = ensure_rows<T>(ctx, 0, ns + B, &replaced))) return rc;
+        if ((rc = fill_seeds<T>(ctx, sp, factor, seeds, ns))) return rc;
+    }
     SampleCtl h{};
     h.bad = kEmpty, h.rmin = kEmpty, h.rmax = 0, h.end = INT_MAX;
     SampleCtl* d_ctl = (SampleCtl*)S.ctl.p;
@@ -558,37 +672,37 @@ static int sample_run(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, i
     WTP_HIP(ctx, hipMemcpyAsync(d_ctl, pin, sizeof(SampleCtl), hipMemcpyHostToDevice, ctx->stream));
 
     CellMap<T> map{};
-    bool have_map = false;
-    int64_t first = 0, n = 0;
+    bool have_map = false, classes = false;
+    double cell_edge = 0;
+    int64_t first = 0, n = ns; // n: rows of the accepted array, the fill's seeds included
     int32_t n_batches = 0, rounds_max = 0;
     for (;;) {
         if (n + B >= (int64_t(1) << 31) - 1) return fail(ctx, WTP_ERR_ARG, "samples + batch exceed the int32 index space");
         if ((rc = ensure_batch<T>(ctx, B))) return rc;
-        // room for n + B samples, and a table of at least twice as many slots
+        // The fill has by now walked the mesh's tree for more darts than a class grid of its cell size has cells: build
+        // one (an exact test per cell), and from here on the darts of cells wholly inside or outside skip the walk.
+        if (fill && have_map && !classes) {
+            const int64_t cells = mesh_class_cells(ctx, cell_edge);
+            if (cells <= first && cells <= (int64_t(1) << 26)) {
+                if ((rc = mesh_ensure_classes(ctx, cell_edge))) return rc;
+                classes = true;
+            }
+        }
         bool rehash = false;
-        if (n + B > S.cap) {
-            const int64_t cap = std::max(n + B, 2 * S.cap);
-            if ((rc = grow_keep(ctx, S.pts, sizeof(Pt<T>) * (size_t)n, sizeof(Pt<T>) * (size_t)cap))) return rc;
-            if ((rc = grow_keep(ctx, S.tri, 4 * (size_t)n, 4 * (size_t)cap))) return rc;
-            if ((rc = grow_keep(ctx, S.dart, 8 * (size_t)n, 8 * (size_t)cap))) return rc;
-            if ((rc = ensure(ctx, S.next, 4 * (size_t)cap))) return rc; // rebuilt with the table
-            S.tsz = pow2_at_least(2 * cap);
-            if ((rc = ensure(ctx, S.table, 12 * (size_t)S.tsz))) return rc;
-            S.cap = cap;
-            rehash = true;
-        } else if (n_batches == 0) {
-            S.tsz = pow2_at_least(2 * S.cap); // buffers of an earlier call: the table is stale
+        if ((rc = ensure_rows<T>(ctx, n, n + B, &rehash))) return rc;
+        if (n_batches == 0) {
+            S.tsz = pow2_at_least(2 * S.cap); // buffers of an earlier call, or the seeds' own: the table is stale
             rehash = true;
         }
         const Table acc = table_view(S.table, S.tsz), bt = table_view(S.b_table, S.b_tsz);
         if (rehash) WTP_HIP(ctx, hipMemsetAsync(S.table.p, 0xFF, 12 * (size_t)S.tsz, ctx->stream));
-        if (rehash && n > 0) {
+        if (rehash && n > 0 && have_map) {
             hipLaunchKernelGGL(sample_rehash_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream, map,
                                (const Pt<T>*)S.pts.p, acc, (int32_t*)S.next.p, n);
             WTP_HIP(ctx, hipGetLastError());
         }
         hipLaunchKernelGGL(sample_begin_kernel, dim3(1), dim3(1), 0, ctx->stream, d_ctl);
-        if ((rc = enqueue_darts<T>(ctx, sp, factor, seed, first, B))) return rc;
+        if ((rc = enqueue_darts<T>(ctx, sp, factor, seed, first, B, fill))) return rc;
         if (!have_map) { // the cell edge: sqrt(r_min r_max) of the first batch (it changes time only)
             hipLaunchKernelGGL(sample_range_kernel<T>, dim3(sm_stride_grid(B)), dim3(kSmThreads), 0, ctx->stream,
                                (const Pt<T>*)S.b_pts.p, B, d_ctl);
@@ -606,13 +720,20 @@ static int sample_run(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, i
                 map.nc[a] = (int32_t)std::min(1048575.0, std::floor((ctx->mesh.bbox[3 + a] - ctx->mesh.bbox[a]) / c) + 1);
             }
             map.inv_c = (T)(1.0 / c);
+            cell_edge = c;
             have_map = true;
+            if (n > 0) { // the fill's seeds enter the table now that cells exist
+                hipLaunchKernelGGL(sample_rehash_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream, map,
+                                   (const Pt<T>*)S.pts.p, acc, (int32_t*)S.next.p, n);
+                WTP_HIP(ctx, hipGetLastError());
+            }
         }
         WTP_HIP(ctx, hipMemsetAsync(S.b_table.p, 0xFF, 12 * (size_t)S.b_tsz, ctx->stream));
         const int32_t Bi = (int32_t)B;
         hipLaunchKernelGGL(sample_cull_kernel<T>, dim3(sm_grid(B)), dim3(kSmThreads), 0, ctx->stream, map,
                            (const Pt<T>*)S.b_pts.p, Bi, (int32_t*)S.b_st.p, acc, (const int32_t*)S.next.p,
-                           (const Pt<T>*)S.pts.p, n, bt, (int32_t*)S.b_next.p);
+                           (const Pt<T>*)S.pts.p, n, bt, (int32_t*)S.b_next.p,
+                           fill ? (const uint8_t*)S.b_in.p : (const uint8_t*)nullptr, first, d_ctl);
         WTP_HIP(ctx, hipGetLastError());
         int32_t round0 = 0, rounds = 0;
         for (;;) {
@@ -629,12 +750,16 @@ static int sample_run(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, i
             hipLaunchKernelGGL(sample_scan_c_kernel, dim3(nblk), dim3(kSmThreads), 0, ctx->stream, (const int32_t*)S.b_st.p, Bi,
                                blk + nblk, (int32_t*)S.b_pos.p, (int32_t*)S.b_last.p, max_points, stall_limit, d_ctl);
             hipLaunchKernelGGL(sample_append_kernel<T>, dim3(sm_grid(B)), dim3(kSmThreads), 0, ctx->stream,
-                               (const Pt<T>*)S.b_pts.p, (const int32_t*)S.b_tri.p, (const int32_t*)S.b_st.p, Bi,
-                               (const int32_t*)S.b_pos.p, first, (Pt<T>*)S.pts.p, (int32_t*)S.tri.p, (int64_t*)S.dart.p, d_ctl);
+                               (const Pt<T>*)S.b_pts.p, fill ? (const int32_t*)nullptr : (const int32_t*)S.b_tri.p,
+                               (const int32_t*)S.b_st.p, Bi, (const int32_t*)S.b_pos.p, first, ns, (Pt<T>*)S.pts.p,
+                               (int32_t*)S.tri.p, (int64_t*)S.dart.p, d_ctl);
+            if (fill)
+                hipLaunchKernelGGL(fill_count_kernel, dim3(sm_grid(B)), dim3(kSmThreads), 0, ctx->stream,
+                                   (const uint8_t*)S.b_in.p, Bi, d_ctl);
             hipLaunchKernelGGL(sample_finish_kernel, dim3(1), dim3(1), 0, ctx->stream, (const int32_t*)S.b_pos.p,
                                (const int32_t*)S.b_last.p, Bi, first, max_points, d_ctl);
             hipLaunchKernelGGL(sample_insert_kernel<T>, dim3(sm_grid(B)), dim3(kSmThreads), 0, ctx->stream, map,
-                               (const Pt<T>*)S.pts.p, acc, (int32_t*)S.next.p, Bi, d_ctl);
+                               (const Pt<T>*)S.pts.p, acc, (int32_t*)S.next.p, Bi, ns, d_ctl);
             WTP_HIP(ctx, hipGetLastError());
             WTP_HIP(ctx, hipMemcpyAsync(pin, d_ctl, sizeof(SampleCtl), hipMemcpyDeviceToHost, ctx->stream));
             if ((rc = sync(ctx))) return rc;
@@ -650,7 +775,7 @@ static int sample_run(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, i
         ++n_batches;
         rounds_max = std::max(rounds_max, rounds);
         if (pin->stopped == 3) return fail(ctx, WTP_ERR_ARG, bad_spacing_text(pin->bad));
-        n = pin->n;
+        n = ns + pin->n;
         if (pin->stopped) break;
         first += B;
         if (batch == 0) B = std::min(2 * B, kBatchMax);
@@ -659,25 +784,25 @@ static int sample_run(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, i
     h = *pin;
     pin->rmin = kEmpty, pin->rmax = 0;
     WTP_HIP(ctx, hipMemcpyAsync(d_ctl, pin, sizeof(SampleCtl), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(sample_range_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream, (const Pt<T>*)S.pts.p,
-                       n, d_ctl);
+    hipLaunchKernelGGL(sample_range_kernel<T>, dim3(sm_stride_grid(n - ns)), dim3(kSmThreads), 0, ctx->stream,
+                       (const Pt<T>*)S.pts.p + ns, n - ns, d_ctl);
     WTP_HIP(ctx, hipGetLastError());
     WTP_HIP(ctx, hipMemcpyAsync(pin, d_ctl, sizeof(SampleCtl), hipMemcpyDeviceToHost, ctx->stream));
     if ((rc = sync(ctx))) return rc;
-    S.n = n;
+    S.n = n - ns;
+    S.n_seeds = ns;
+    S.fill = fill;
     S.valid = true;
-    if (info) {
-        info->n_points = n;
-        info->n_darts = h.n_darts;
-        info->batch = B;
-        info->stop_reason = h.reason;
-        info->n_batches = n_batches;
-        info->rounds_max = rounds_max;
-        info->host_syncs = (int32_t)(ctx->n_syncs - syncs0);
-        info->total_area = ctx->mesh.total_area;
-        info->r_min = pin->rmin != kEmpty ? __builtin_bit_cast(double, pin->rmin) : 0.0;
-        info->r_max = __builtin_bit_cast(double, pin->rmax);
-    }
+    info->n_points = n - ns;
+    info->n_darts = h.n_darts;
+    info->n_inside = (int64_t)h.n_inside;
+    info->batch = B;
+    info->stop_reason = h.reason;
+    info->n_batches = n_batches;
+    info->rounds_max = rounds_max;
+    info->host_syncs = (int32_t)(ctx->n_syncs - syncs0);
+    info->r_min = pin->rmin != kEmpty ? __builtin_bit_cast(double, pin->rmin) : 0.0;
+    info->r_max = __builtin_bit_cast(double, pin->rmax);
     return WTP_OK;
 }
 
@@ -691,7 +816,7 @@ static int sample_unpack(wtp_ctx* ctx, const void* pts, int64_t n, T* d_xyz, T* 
 
 template <typename T>
 static int sample_darts(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, uint64_t seed, int64_t first, int64_t n,
-                        T* xyz_out, int32_t* tri_out, T* r_out) {
+                        bool fill, T* xyz_out, int32_t* tri_out, uint8_t* inside_out, T* r_out) {
     SampleState& S = ctx->sample;
     const int dtype = sizeof(T) == 4 ? WTP_F32 : WTP_F64;
     int rc;
@@ -701,10 +826,11 @@ static int sample_darts(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor,
     if ((rc = ensure_batch<T>(ctx, std::max(chunk, S.bcap)))) return rc;
     for (int64_t done = 0; done < n; done += chunk) {
         const int64_t m = std::min(chunk, n - done);
-        if ((rc = enqueue_darts<T>(ctx, sp, factor, seed, first + done, m))) return rc;
+        if ((rc = enqueue_darts<T>(ctx, sp, factor, seed, first + done, m, fill))) return rc;
         if (xyz_out)
             WTP_HIP(ctx, hipMemcpyAsync(xyz_out + 3 * done, S.b_xyz.p, sizeof(T) * 3 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
         if (tri_out) WTP_HIP(ctx, hipMemcpyAsync(tri_out + done, S.b_tri.p, 4 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+        if (inside_out) WTP_HIP(ctx, hipMemcpyAsync(inside_out + done, S.b_in.p, (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
         if (r_out) {
             if ((rc = sample_unpack<T>(ctx, S.b_pts.p, m, nullptr, (T*)S.b_h.p))) return rc;
             WTP_HIP(ctx, hipMemcpyAsync(r_out + done, S.b_h.p, sizeof(T) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
@@ -719,69 +845,161 @@ static int sample_darts(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor,
 using namespace wtp;
 #define WTP_API extern "C"
 
-WTP_API int wtp_mesh_sample(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, int64_t max_points,
-                            int64_t stall_limit, uint64_t seed, int64_t batch, wtp_sample_info* info) {
-    if (!ctx) return WTP_ERR_ARG;
-    int rc = check_sample_args(ctx, spacing, factor, seed);
+// the argument rows wtp_mesh_sample and wtp_mesh_fill share
+static int check_run_args(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, int64_t max_points, int64_t stall_limit,
+                          uint64_t seed, int64_t batch) {
+    const int rc = check_sample_args(ctx, spacing, factor, seed);
     if (rc) return rc;
     if (stall_limit < 1) return fail(ctx, WTP_ERR_ARG, "stall_limit must be positive");
     if (max_points < 1) return fail(ctx, WTP_ERR_ARG, "max_points must be positive");
     if (batch < 0 || batch > (int64_t(1) << 24)) return fail(ctx, WTP_ERR_ARG, "batch must be in [0, 2^24]");
+    return WTP_OK;
+}
+
+WTP_API int wtp_mesh_sample(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, int64_t max_points,
+                            int64_t stall_limit, uint64_t seed, int64_t batch, wtp_sample_info* info) {
+    if (!ctx) return WTP_ERR_ARG;
+    int rc = check_run_args(ctx, spacing, factor, max_points, stall_limit, seed, batch);
+    if (rc) return rc;
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    return by_dtype(ctx->mesh.dtype, [&](auto t) {
-        return sample_run<decltype(t)>(ctx, spacing, factor, max_points, stall_limit, seed, batch, info);
+    RunInfo ri{};
+    rc = by_dtype(ctx->mesh.dtype, [&](auto t) {
+        using T = decltype(t);
+        return sample_run<T>(ctx, spacing, factor, max_points, stall_limit, seed, batch, false, (const T*)nullptr, 0, &ri);
     });
+    if (rc || !info) return rc;
+    info->n_points = ri.n_points, info->n_darts = ri.n_darts, info->batch = ri.batch;
+    info->stop_reason = ri.stop_reason;
+    info->n_batches = ri.n_batches, info->rounds_max = ri.rounds_max, info->host_syncs = ri.host_syncs;
+    info->total_area = ctx->mesh.total_area, info->r_min = ri.r_min, info->r_max = ri.r_max;
+    return WTP_OK;
+}
+
+// xyz and r of the resident rows [first, first + n) into host arrays, through the context's scratch block
+static int rows_to_host(wtp_ctx* ctx, int64_t first, void* xyz_out, void* r_out) {
+    SampleState& S = ctx->sample;
+    const size_t ts = tsize(S.dtype), n = (size_t)S.n;
+    int rc;
+    if ((rc = ensure(ctx, ctx->scratch, ts * 4 * n))) return rc;
+    char* d = (char*)ctx->scratch.p;
+    rc = by_dtype(S.dtype, [&](auto t) {
+        using T = decltype(t);
+        return sample_unpack<T>(ctx, (const Pt<T>*)S.pts.p + first, S.n, (T*)d, (T*)(d + ts * 3 * n));
+    });
+    if (rc) return rc;
+    if (xyz_out) WTP_HIP(ctx, hipMemcpyAsync(xyz_out, d, ts * 3 * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (r_out) WTP_HIP(ctx, hipMemcpyAsync(r_out, d + ts * 3 * n, ts * n, hipMemcpyDeviceToHost, ctx->stream));
+    return WTP_OK;
 }
 
 WTP_API int wtp_mesh_sample_get(wtp_ctx* ctx, void* xyz_out, int32_t* tri_out, void* r_out, int64_t* dart_out) {
     if (!ctx) return WTP_ERR_ARG;
     SampleState& S = ctx->sample;
-    if (!S.valid) return fail(ctx, WTP_ERR_STATE, "no sample: call wtp_mesh_sample first");
+    if (!S.valid || S.fill) return fail(ctx, WTP_ERR_STATE, "no sample: call wtp_mesh_sample first");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t ts = tsize(S.dtype), n = (size_t)S.n;
+    const size_t n = (size_t)S.n;
     int rc;
-    if (xyz_out || r_out) {
-        if ((rc = ensure(ctx, ctx->scratch, ts * 4 * n))) return rc;
-        char* d = (char*)ctx->scratch.p;
-        rc = by_dtype(S.dtype, [&](auto t) {
-            using T = decltype(t);
-            return sample_unpack<T>(ctx, S.pts.p, S.n, (T*)d, (T*)(d + ts * 3 * n));
-        });
-        if (rc) return rc;
-        if (xyz_out) WTP_HIP(ctx, hipMemcpyAsync(xyz_out, d, ts * 3 * n, hipMemcpyDeviceToHost, ctx->stream));
-        if (r_out) WTP_HIP(ctx, hipMemcpyAsync(r_out, d + ts * 3 * n, ts * n, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    if ((xyz_out || r_out) && (rc = rows_to_host(ctx, 0, xyz_out, r_out))) return rc;
     if (tri_out) WTP_HIP(ctx, hipMemcpyAsync(tri_out, S.tri.p, 4 * n, hipMemcpyDeviceToHost, ctx->stream));
     if (dart_out) WTP_HIP(ctx, hipMemcpyAsync(dart_out, S.dart.p, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
     return sync(ctx);
 }
 
+// xyz and r of the resident rows from `first` on into device arrays
+static int rows_to_dev(wtp_ctx* ctx, int64_t first, void* d_xyz_out, void* d_r_out) {
+    SampleState& S = ctx->sample;
+    if (!d_xyz_out && !d_r_out) return WTP_OK;
+    return by_dtype(S.dtype, [&](auto t) {
+        using T = decltype(t);
+        return sample_unpack<T>(ctx, (const Pt<T>*)S.pts.p + first, S.n, (T*)d_xyz_out, (T*)d_r_out);
+    });
+}
+
 WTP_API int wtp_mesh_sample_get_dev(wtp_ctx* ctx, void* d_xyz_out, int32_t* d_tri_out, void* d_r_out) {
     if (!ctx) return WTP_ERR_ARG;
     SampleState& S = ctx->sample;
-    if (!S.valid) return fail(ctx, WTP_ERR_STATE, "no sample: call wtp_mesh_sample first");
+    if (!S.valid || S.fill) return fail(ctx, WTP_ERR_STATE, "no sample: call wtp_mesh_sample first");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    if (d_xyz_out || d_r_out) {
-        const int rc = by_dtype(S.dtype, [&](auto t) {
-            using T = decltype(t);
-            return sample_unpack<T>(ctx, S.pts.p, S.n, (T*)d_xyz_out, (T*)d_r_out);
-        });
-        if (rc) return rc;
-    }
+    const int rc = rows_to_dev(ctx, 0, d_xyz_out, d_r_out);
+    if (rc) return rc;
     if (d_tri_out) WTP_HIP(ctx, hipMemcpyAsync(d_tri_out, S.tri.p, 4 * (size_t)S.n, hipMemcpyDeviceToDevice, ctx->stream));
     return sync(ctx);
+}
+
+static int check_dart_range(wtp_ctx* ctx, int64_t first, int64_t n) {
+    if (first < 0 || n < 0 || first > (int64_t(1) << 62) - n) return fail(ctx, WTP_ERR_ARG, "bad dart range");
+    return WTP_OK;
 }
 
 WTP_API int wtp_mesh_sample_darts(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, uint64_t seed, int64_t first,
                                   int64_t n, void* xyz_out, int32_t* tri_out, void* r_out) {
     if (!ctx) return WTP_ERR_ARG;
     int rc = check_sample_args(ctx, spacing, factor, seed);
-    if (rc) return rc;
-    if (first < 0 || n < 0 || first > (int64_t(1) << 62) - n) return fail(ctx, WTP_ERR_ARG, "bad dart range");
+    if (rc || (rc = check_dart_range(ctx, first, n))) return rc;
     if (n == 0) return WTP_OK;
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     return by_dtype(ctx->mesh.dtype, [&](auto t) {
         using T = decltype(t);
-        return sample_darts<T>(ctx, spacing, factor, seed, first, n, (T*)xyz_out, tri_out, (T*)r_out);
+        return sample_darts<T>(ctx, spacing, factor, seed, first, n, false, (T*)xyz_out, tri_out, nullptr, (T*)r_out);
+    });
+}
+
+// ---- the volume fill ---------------------------------------------------------------------------------------------------
+WTP_API int wtp_mesh_fill(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, const void* seeds, int64_t n_seeds,
+                          int64_t max_points, int64_t stall_limit, uint64_t seed, int64_t batch, wtp_fill_info* info) {
+    if (!ctx) return WTP_ERR_ARG;
+    int rc = check_run_args(ctx, spacing, factor, max_points, stall_limit, seed, batch);
+    if (rc) return rc;
+    if (n_seeds < 0) return fail(ctx, WTP_ERR_ARG, "n_seeds must not be negative");
+    if (n_seeds > 0 && !seeds) return fail(ctx, WTP_ERR_ARG, "seeds is NULL");
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    RunInfo ri{};
+    rc = by_dtype(ctx->mesh.dtype, [&](auto t) {
+        using T = decltype(t);
+        return sample_run<T>(ctx, spacing, factor, max_points, stall_limit, seed, batch, true, (const T*)seeds, n_seeds, &ri);
+    });
+    if (rc || !info) return rc;
+    const double* b = ctx->mesh.bbox;
+    info->n_points = ri.n_points, info->n_darts = ri.n_darts, info->n_inside = ri.n_inside, info->n_seeds = n_seeds;
+    info->batch = ri.batch;
+    info->stop_reason = ri.stop_reason;
+    info->n_batches = ri.n_batches, info->rounds_max = ri.rounds_max, info->host_syncs = ri.host_syncs;
+    info->bbox_volume = ((b[3] - b[0]) * (b[4] - b[1])) * (b[5] - b[2]);
+    info->r_min = ri.r_min, info->r_max = ri.r_max;
+    return WTP_OK;
+}
+
+WTP_API int wtp_mesh_fill_get(wtp_ctx* ctx, void* xyz_out, void* r_out, int64_t* dart_out) {
+    if (!ctx) return WTP_ERR_ARG;
+    SampleState& S = ctx->sample;
+    if (!S.valid || !S.fill) return fail(ctx, WTP_ERR_STATE, "no fill: call wtp_mesh_fill first");
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if ((xyz_out || r_out) && (rc = rows_to_host(ctx, S.n_seeds, xyz_out, r_out))) return rc;
+    if (dart_out)
+        WTP_HIP(ctx, hipMemcpyAsync(dart_out, (const int64_t*)S.dart.p + S.n_seeds, 8 * (size_t)S.n, hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
+}
+
+WTP_API int wtp_mesh_fill_get_dev(wtp_ctx* ctx, void* d_xyz_out, void* d_r_out) {
+    if (!ctx) return WTP_ERR_ARG;
+    SampleState& S = ctx->sample;
+    if (!S.valid || !S.fill) return fail(ctx, WTP_ERR_STATE, "no fill: call wtp_mesh_fill first");
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    const int rc = rows_to_dev(ctx, S.n_seeds, d_xyz_out, d_r_out);
+    if (rc) return rc;
+    return sync(ctx);
+}
+
+WTP_API int wtp_mesh_fill_darts(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, uint64_t seed, int64_t first,
+                                int64_t n, void* xyz_out, uint8_t* inside_out, void* r_out) {
+    if (!ctx) return WTP_ERR_ARG;
+    int rc = check_sample_args(ctx, spacing, factor, seed);
+    if (rc || (rc = check_dart_range(ctx, first, n))) return rc;
+    if (n == 0) return WTP_OK;
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    return by_dtype(ctx->mesh.dtype, [&](auto t) {
+        using T = decltype(t);
+        return sample_darts<T>(ctx, spacing, factor, seed, first, n, true, (T*)xyz_out, nullptr, inside_out, (T*)r_out);
     });
 }

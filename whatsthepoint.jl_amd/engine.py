@@ -405,6 +405,55 @@ class Context:
         del keep
         return xyz, tri, r
 
+    # ---- graded Poisson-disk fill of the mesh's volume (discretize's Orthtree / :bridson placement; wtp_mesh_fill) ----
+    def mesh_fill(self, spacing, factor: float = 0.75, seeds=None, max_points: int = 10_000_000, stall_limit: int = 2000,
+                  seed: int = 0, batch: int = 0, spacing_desc=None):
+        """wtp_mesh_fill on the mesh of mesh_set: the serial dart thrower over the seeded stream of the mesh's bounding
+        box, decided in batches on the device.  seeds: (n, 3) points that occupy space from the start (converted to the
+        mesh's dtype), or None.  Returns the info dict; the points stay on the device (mesh_fill_get)."""
+        sd, keep = (spacing_desc, None) if spacing_desc is not None else self._sample_spacing(spacing)
+        s = None
+        if seeds is not None and len(seeds):
+            s = np.ascontiguousarray(seeds, dtype=self._mesh_dtype())
+            if s.ndim != 2 or s.shape[1] != 3:
+                raise L.WtpArgumentError("seeds must have shape (n, 3)")
+        info = L.FillInfo()
+        rc = self._lib.wtp_mesh_fill(self._h, C.byref(sd), float(factor), _vp(s), 0 if s is None else len(s), int(max_points),
+                                     int(stall_limit), C.c_uint64(int(seed)), int(batch), C.byref(info))
+        L.check(self._h, rc)
+        del keep
+        return {name: getattr(info, name) for name, _ in L.FillInfo._fields_}
+
+    def mesh_fill_get(self, n: int, want=("xyz", "r", "dart")):
+        """The n = info['n_points'] points of the last mesh_fill as a dict of host arrays (mesh dtype)."""
+        dt = self._mesh_dtype()
+        out = {}
+        if "xyz" in want:
+            out["xyz"] = np.empty((n, 3), dtype=dt)
+        if "r" in want:
+            out["r"] = np.empty(n, dtype=dt)
+        if "dart" in want:
+            out["dart"] = np.empty(n, dtype=np.int64)
+        rc = self._lib.wtp_mesh_fill_get(self._h, _vp(out.get("xyz")), _vp(out.get("r")), _vp(out.get("dart")))
+        L.check(self._h, rc)
+        return out
+
+    def mesh_fill_get_dev(self, d_xyz_ptr: int = 0, d_r_ptr: int = 0):
+        """wtp_mesh_fill_get_dev: the points into device arrays given as addresses (0 = absent)."""
+        rc = self._lib.wtp_mesh_fill_get_dev(self._h, C.c_void_p(d_xyz_ptr or None), C.c_void_p(d_r_ptr or None))
+        L.check(self._h, rc)
+
+    def mesh_fill_darts(self, spacing, factor: float, seed: int, first: int, n: int):
+        """wtp_mesh_fill_darts: darts first .. first + n - 1 as the fill makes them: (xyz, inside, r)."""
+        sd, keep = self._sample_spacing(spacing)
+        dt = self._mesh_dtype()
+        xyz, inside, r = np.empty((n, 3), dtype=dt), np.zeros(n, dtype=np.uint8), np.empty(n, dtype=dt)
+        rc = self._lib.wtp_mesh_fill_darts(self._h, C.byref(sd), float(factor), C.c_uint64(int(seed)), int(first), int(n),
+                                           _vp(xyz), _vp(inside), _vp(r))
+        L.check(self._h, rc)
+        del keep
+        return xyz, inside.astype(bool), r
+
     def set_stream(self, stream_handle=None):
         """Run the library on a caller-owned HIP stream (handle as an int; 0 = the device's default
         stream, which is torch's current stream unless the caller switched); None = own stream."""

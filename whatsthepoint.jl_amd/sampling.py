@@ -1,11 +1,15 @@
-"""Boundary preprocessing that makes points: `sample_surface` / `PointBoundary.from_mesh`
-(src/surface_sampling.jl) and `generate_shadows` (src/shadow.jl).
+"""Preprocessing that makes points: `sample_surface` / `PointBoundary.from_mesh` (src/surface_sampling.jl),
+`fill_volume` / `discretize` (the Bridson placement of src/discretization/algorithms/octree.jl) and `generate_shadows`
+(src/shadow.jl).
 
 `sample_surface` is graded Poisson-disk dart throwing on the continuous mesh surface.  The reference draws
 its darts from `rand`; here they come from the library's counter-based stream (include/wtp.h,
 wtp_mesh_sample), and the result is the serial loop over that stream, decided in batches on the device
 (csrc/wtp_sample.hip).  There is no CPU path: the host only checks arguments, looks up the parent
-triangles' normals and divides the area shares."""
+triangles' normals and divides the area shares.
+
+`fill_volume` is the same run over darts uniform in the mesh's bounding box, of which those inside the mesh may be
+taken, with the boundary points as seeds that occupy space from the start (include/wtp.h, wtp_mesh_fill)."""
 from __future__ import annotations
 
 import warnings
@@ -25,7 +29,7 @@ def _sampler_spacing(spacing):
         return float(spacing.dx)
     if isinstance(spacing, (int, float, np.integer, np.floating)) and not isinstance(spacing, bool):
         return float(spacing)
-    raise WtpArgumentError("sample_surface evaluates the spacing on the device at every dart: pass a number, "
+    raise WtpArgumentError("the spacing is evaluated on the device at every dart: pass a number, "
                            f"ConstantSpacing, LogLike or BoundaryLayerSpacing, not {type(spacing).__name__}")
 
 
@@ -70,6 +74,70 @@ def sample_surface(mesh, spacing, *, factor: float = 0.75, max_points: int = 10_
     surf = PointSurface(got["xyz"], normals, areas.astype(dt))
     surf.sample_info, surf.sample_r, surf.sample_tri = info, got["r"], got["tri"]
     return surf
+
+
+def _as_octree(mesh, ctx, guards: bool):
+    from .octree import TriangleOctree
+
+    if not isinstance(mesh, TriangleOctree):
+        vertices, triangles = mesh
+        mesh = TriangleOctree(vertices, triangles, classify_leaves=guards, verify_orientation=guards, ctx=ctx)
+    if len(mesh) == 0:
+        raise WtpArgumentError("mesh has no elements")
+    return mesh
+
+
+def fill_volume(mesh, spacing, *, seeds=None, factor: float = 0.75, max_points: int = 10_000_000, stall_limit: int = 2000,
+                seed: int = synth.SEED, batch: int = 0, ctx=None):
+    """Graded Poisson-disk points inside a closed triangle mesh -> PointVolume: the placement of the reference's default
+    discretize (Orthtree(mesh; spacing, placement = :bridson), src/discretization/algorithms/octree.jl:804-902).
+
+    mesh: a TriangleOctree or a (vertices, triangles) pair (a pair passes the TriangleOctree orientation guards here:
+    an inside-out mesh has no inside).  Every point keeps min(r_i, r_j), r = factor * spacing(x), from every other
+    point and from the seeds (the boundary points, (n, 3) or None), which are not returned.  seed and batch as for
+    sample_surface.  The returned volume carries the run's wtp_fill_info as `fill_info` (with `volume_estimate` =
+    bbox_volume * n_inside / n_darts added) and the points' r as `fill_r`."""
+    from .cloud import PointVolume
+
+    if not factor > 0:
+        raise WtpArgumentError("factor must be positive")
+    if not stall_limit > 0:
+        raise WtpArgumentError("stall_limit must be positive")
+    if not max_points > 0:
+        raise WtpArgumentError("max_points must be positive")
+    law = _sampler_spacing(spacing)
+    mesh = _as_octree(mesh, ctx, True)
+    c = mesh._resident(ctx)
+    info = c.mesh_fill(law, factor, seeds, max_points, stall_limit, int(seed) & 0xFFFFFF, batch)
+    n = int(info["n_points"])
+    if n == 0:
+        raise WtpArgumentError("volume fill produced no points — check spacing vs domain size and mesh orientation")
+    if info["stop_reason"] == 2:
+        warnings.warn("Volume fill truncated by max_points before saturation — parts of the domain may be unfilled "
+                      f"(max_points = {max_points})")
+    got = c.mesh_fill_get(n, want=("xyz", "r"))
+    info["volume_estimate"] = info["bbox_volume"] * info["n_inside"] / info["n_darts"]
+    vol = PointVolume(got["xyz"])
+    vol.fill_info, vol.fill_r = info, got["r"]
+    return vol
+
+
+def discretize(boundary, spacing, mesh, *, factor: float = 0.75, max_points: int = 10_000_000, stall_limit: int = 2000,
+               seed: int = synth.SEED, ctx=None):
+    """discretize(bnd, spacing; alg = Orthtree(mesh; spacing, placement = :bridson), max_points) -> PointCloud(boundary,
+    volume): the boundary's points are the seeds of fill_volume; the boundary itself is returned unchanged."""
+    from .cloud import PointBoundary, PointCloud
+
+    if not isinstance(boundary, PointBoundary):
+        boundary = PointBoundary(boundary)
+    vol = fill_volume(mesh, spacing, seeds=boundary.points(), factor=factor, max_points=max_points,
+                      stall_limit=stall_limit, seed=seed, ctx=ctx)
+    bp = boundary.points()
+    if vol.points().dtype != bp.dtype:  # the cloud keeps the boundary's type (the mesh's decided the run)
+        info, r = vol.fill_info, vol.fill_r
+        vol = type(vol)(vol.points().astype(bp.dtype))
+        vol.fill_info, vol.fill_r = info, r
+    return PointCloud(boundary, vol)
 
 
 class ShadowPoints:
