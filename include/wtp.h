@@ -338,8 +338,8 @@ typedef struct wtp_sample_info {
     int32_t n_batches, rounds_max, host_syncs;
     double total_area, r_min, r_max;    /* r over the samples */
 } wtp_sample_info;
-/* Samples the mesh of wtp_mesh_set; the result stays on the device until the next call / wtp_mesh_fill (which shares the
- * buffers) / wtp_mesh_set / wtp_mesh_clear. */
+/* Samples the mesh of wtp_mesh_set; the result stays on the device until the next call / wtp_mesh_fill / wtp_mesh_front
+ * (which share the buffers) / wtp_mesh_set / wtp_mesh_clear. */
 int wtp_mesh_sample(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, int64_t max_points,
                     int64_t stall_limit, uint64_t seed, int64_t batch, wtp_sample_info* info);
 /* n_points rows (xyz_out n x 3 and r_out of the mesh's dtype); every output may be NULL.  dart_out: the dart index each
@@ -402,6 +402,70 @@ int wtp_mesh_fill_get_dev(wtp_ctx* ctx, void* d_xyz_out, void* d_r_out);
  * sample or fill untouched.  */
 int wtp_mesh_fill_darts(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, uint64_t seed, int64_t first,
                         int64_t n, void* xyz_out, uint8_t* inside_out, void* r_out);
+
+/* ---- advancing-front fill of the mesh's volume ----------------------------------------------------
+ * Replaces discretize(bnd, spacing; alg = SlakKosec(octree), max_points) (src/discretization/algorithms/slak_kosec.jl:72-123;
+ * Slak & Kosec 2019): every point of a queue that starts as the boundary points throws n candidates onto the sphere of its
+ * own spacing around it, and a candidate that is inside the domain and far enough from every point is appended to the
+ * queue.  The reference loop is serial and draws from rand(); as for the sampler and the fill, the result is DEFINED as
+ * the serial loop over a counter-based stream.  All arithmetic is in the mesh's type T, no contraction:
+ *   Queue.  Entries q = 0 .. n_seeds - 1 are the seeds (host, n_seeds x 3 of T), in the order given; behind them the
+ * accepted points in acceptance order: the queue is the accepted array with the seeds at its front.  Every entry has
+ * h_q = T(h(x_q)), the spacing law evaluated at it in T as wtp_mesh_sample does (CONSTANT: T(constant)).  Kinds: CONSTANT,
+ * LOGLIKE, BOUNDARY_LAYER.  There is no factor: the reference uses r = spacing(p).
+ *   Candidate j = q n + s (64-bit), s = 0 .. n - 1, of parent q, seed < 2^24: w_a = splitmix64((seed << 40) + 2 j + a),
+ * a = 0, 1; u = T(float(w_0 >> 40) 2^-24), v likewise from w_1.  Polar part z = 2 u - 1, rho = sqrt(1 - z z).  Azimuth
+ * without libm, so that any IEEE machine agrees bit for bit: t = 8 v, o = floor(t), f = t - o, g = (o odd) ? 1 - f : f (all
+ * exact), theta = g T(pi / 4), x = theta theta,
+ *     s = theta (1 + x (S_1 + x (S_2 + ... + x S_9))),    c = 1 + x (C_1 + x (C_2 + ... + x C_9))      (Horner)
+ * with S_k = T((-1)^k / (2k + 1)!), C_k = T((-1)^k / (2k)!), each the double quotient (n! is exact in double up to 19!)
+ * rounded to T; (cos l, sin l) by octant o = 0 .. 7: (c, s) (s, c) (-s, c) (-c, s) (-c, -s) (-s, -c) (s, -c) (c, -s).
+ * Direction d = (rho cos l, rho sin l, z), | |d| - 1 | <= 1.02 eps; position c_a = x_{q,a} + h_q d_a; test radius r_j = h_q.
+ *   A candidate is inside iff wtp_mesh_query's inside flag holds for it, as in wtp_mesh_fill.
+ *   Conflict is one-sided: candidate j conflicts with queue entry e iff ((dx^2 + dy^2) + dz^2) < r_j r_j.  The entry's own
+ * h plays no part, and a candidate is never tested against its own parent (which sits at distance h_q (1 +- eps): the
+ * reference's `> r` against a tree that still holds the parent is a coin toss on rounding).  Every other entry counts,
+ * expanded or not: this is the published algorithm.  The reference rebuilds its search tree from the not yet expanded
+ * seeds only, so later candidates are not tested against expanded boundary points; that is deliberately NOT reproduced.
+ *   Run.  Parents are expanded in queue order, candidates in s order.  Before each candidate the run ends if max_points
+ * points have been accepted (stop_reason 2).  A candidate is accepted iff it is inside and conflicts with no entry then in
+ * the queue, and is appended.  The run ends with stop_reason 1 when every queue entry has been expanded (the normal end:
+ * the front has died out).  n_candidates counts the candidates taken, n_inside those of them that were inside, n_parents
+ * the parents of which a candidate was taken (ceil(n_candidates / n)).  The device decides the candidates of a range of
+ * parents at once (batch parents per batch, 0 = the library chooses: every parent available; either way at most 2^20
+ * candidates, i.e. 2^20 / n parents, at least one); the batch changes
+ * time only, two calls return the same bits, and a smaller max_points returns a prefix.  n_seeds = 0 returns WTP_OK with
+ * no points and stop_reason 1.
+ *   WTP_ERR_ARG: n outside 1 .. 64; max_points < 1; seed >= 2^24; batch < 0 or > 2^24; kind WTP_SPACING_PER_POINT; a seed
+ * coordinate that is not finite; n_seeds < 0, or seeds NULL with n_seeds > 0; n_seeds + max_points >= 2^31 - 1 (the queue
+ * is indexed in int32; refused before the run starts); a spacing value that is not finite and > 0 at a seed (naming the
+ * seed) or at an accepted point (naming the smallest such candidate index; such a point is never expanded); a mesh of no
+ * area.  WTP_ERR_STATE and WTP_ERR_INTERNAL as for wtp_mesh_sample.
+ *   State.  The front shares the sampler's buffers: it voids a resident sample or fill and is voided by wtp_mesh_sample and
+ * wtp_mesh_fill, once the arguments have passed; each one's *_get* is WTP_ERR_STATE after that.  */
+typedef struct wtp_front_info {
+    int64_t n_points, n_parents, n_candidates, n_inside, n_seeds, batch; /* batch: parents in the last batch */
+    int32_t stop_reason;                                                 /* 1 the front died out, 2 max_points */
+    int32_t n_batches, rounds_max, host_syncs;
+    double r_min, r_max;                                                 /* h over the accepted points (0 when there are none) */
+} wtp_front_info;
+/* Fills the mesh of wtp_mesh_set from the seeds; the result stays on the device until the next wtp_mesh_front /
+ * wtp_mesh_fill / wtp_mesh_sample / wtp_mesh_set / wtp_mesh_clear.  seeds: host array of the mesh's dtype.  */
+int wtp_mesh_front(wtp_ctx* ctx, const wtp_spacing_desc* spacing, int64_t n, const void* seeds, int64_t n_seeds,
+                   int64_t max_points, uint64_t seed, int64_t batch, wtp_front_info* info);
+/* n_points rows, the seeds not among them (xyz_out n x 3 and h_out of the mesh's dtype); every output may be NULL.
+ * cand_out: the candidate index each point came from; parent_out: its parent's queue index (cand / n).  */
+int wtp_mesh_front_get(wtp_ctx* ctx, void* xyz_out, void* h_out, int64_t* cand_out, int32_t* parent_out);
+/* xyz and h into device memory.  */
+int wtp_mesh_front_get_dev(wtp_ctx* ctx, void* d_xyz_out, void* d_h_out);
+/* Read-out, no acceptance: the n candidates each of n_parents parent positions (host, n_parents x 3), parent p standing
+ * for queue entry first_parent + p (0 <= first_parent <= 2^31), as the rule above makes them with h evaluated at the given
+ * positions: xyz_out (n_parents n) x 3, inside_out one byte and r_out one value per candidate (host, may be NULL).  The
+ * candidates of a parent whose h is not finite and > 0 are returned at the parent's position with that h.  Leaves a
+ * resident result untouched.  */
+int wtp_mesh_front_candidates(wtp_ctx* ctx, const wtp_spacing_desc* spacing, uint64_t seed, const void* parents_xyz,
+                              int64_t n_parents, int64_t first_parent, int64_t n, void* xyz_out, uint8_t* inside_out,
+                              void* r_out);
 
 /* ---- consumers of the k-NN rows ------------------------------------
  * Replaces compute_normals(points; k) / update_normals! (src/normals.jl:15-69): per point the

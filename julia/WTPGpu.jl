@@ -96,6 +96,33 @@ function metrics(cloud; k::Int = 20)
             separation = st.nn_min, fill = st.nn_max, mesh_ratio = st.nn_min > 0 ? st.nn_max / st.nn_min : Inf)
 end
 
+# ---- the advancing front of discretize (src/discretization/algorithms/slak_kosec.jl:72-123) on the device -----------------
+# (include/wtp.h: wtp_mesh_front; the mesh is the one wtp_mesh_set holds)
+mutable struct FrontInfo
+    n_points::Int64; n_parents::Int64; n_candidates::Int64; n_inside::Int64; n_seeds::Int64; batch::Int64
+    stop_reason::Int32; n_batches::Int32; rounds_max::Int32; host_syncs::Int32
+    r_min::Float64; r_max::Float64
+    FrontInfo() = new(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0)
+end
+
+# sd: the SpacingDesc of a ConstantSpacing, LogLike or BoundaryLayerSpacing; seeds: the boundary points, of the mesh's
+# eltype T; n: candidates per expanded point (SlakKosec's n).  Returns (volume points as SVector{3,T}, their own spacing,
+# their parents' queue indices (1-based: 1 .. length(seeds) are the seeds), info).
+function front_volume(sd::SpacingDesc, seeds, ::Type{T}; n::Int = 10, max_points::Int = 10_000_000,
+                      seed::Integer = 0) where {T}
+    xs = isempty(seeds) ? SVector{3, T}[] : raw(seeds)
+    info = FrontInfo()
+    check(context(), ccall((:wtp_mesh_front, lib), Cint,
+        (Ptr{Cvoid}, Ref{SpacingDesc}, Int64, Ptr{Cvoid}, Int64, Int64, UInt64, Int64, Ref{FrontInfo}),
+        context(), sd, n, isempty(xs) ? C_NULL : xs, length(xs), max_points, UInt64(seed), 0, info))
+    m = info.n_points
+    vol = Vector{SVector{3, T}}(undef, m); hs = Vector{T}(undef, m); parent = Vector{Int32}(undef, m)
+    check(context(), ccall((:wtp_mesh_front_get, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}),
+        context(), vol, hs, C_NULL, parent))
+    info.stop_reason == 2 && @warn "discretization stopping early, reached max points ($max_points)"
+    return vol, hs, Int.(parent) .+ 1, info
+end
+
 # ---- the Bridson placement of discretize (src/discretization/algorithms/octree.jl:804-902) on the device ----------------
 # (include/wtp.h: wtp_mesh_fill; the mesh is the one wtp_mesh_set holds)
 mutable struct FillInfo

@@ -18,7 +18,8 @@ from .inside import isinside
 from .octree import TriangleOctree, has_consistent_normals, signed_volume
 from .normals import compute_normals, update_normals, orient_normals, split_surface, combine_surfaces
 from .limiter import gradient_limit_field
-from .sampling import sample_surface, fill_volume, discretize, generate_shadows, ShadowPoints
+from .sampling import (sample_surface, fill_volume, front_volume, SlakKosec, discretize, generate_shadows,
+                       ShadowPoints)
 from . import synth, stl, octree, sampling
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -92,6 +92,13 @@ class FillInfo(C.Structure):
                 ("host_syncs", C.c_int32), ("bbox_volume", C.c_double), ("r_min", C.c_double), ("r_max", C.c_double)]
 
 
+class FrontInfo(C.Structure):
+    """wtp_front_info: what wtp_mesh_front reports about a run."""
+    _fields_ = [("n_points", C.c_int64), ("n_parents", C.c_int64), ("n_candidates", C.c_int64), ("n_inside", C.c_int64),
+                ("n_seeds", C.c_int64), ("batch", C.c_int64), ("stop_reason", C.c_int32), ("n_batches", C.c_int32),
+                ("rounds_max", C.c_int32), ("host_syncs", C.c_int32), ("r_min", C.c_double), ("r_max", C.c_double)]
+
+
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                           C.POINTER(C.c_void_p), C.POINTER(C.c_int64))
@@ -150,6 +157,10 @@ SIGNATURES = {
     "wtp_mesh_fill_get": (_i, [_vp, _vp, _vp, _vp]),
     "wtp_mesh_fill_get_dev": (_i, [_vp, _vp, _vp]),
     "wtp_mesh_fill_darts": (_i, [_vp, C.POINTER(SpacingDesc), _d, C.c_uint64, _i64, _i64, _vp, _vp, _vp]),
+    "wtp_mesh_front": (_i, [_vp, C.POINTER(SpacingDesc), _i64, _vp, _i64, _i64, C.c_uint64, _i64, C.POINTER(FrontInfo)]),
+    "wtp_mesh_front_get": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "wtp_mesh_front_get_dev": (_i, [_vp, _vp, _vp]),
+    "wtp_mesh_front_candidates": (_i, [_vp, C.POINTER(SpacingDesc), C.c_uint64, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "wtp_relax_set_wall": (_i, [_vp, _i64, _d]),
     "wtp_relax_get_wall": (_i, [_vp, _vp, _vp, _vp, _i]),
     "wtp_relax_set_wall_flags": (_i, [_vp, _vp, _vp]),

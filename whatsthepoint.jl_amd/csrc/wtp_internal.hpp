@@ -366,10 +366,13 @@ struct MeshState {
 
 // Poisson-disk surface sampling (wtp_sample.hip): the accepted samples and their cell table stay on the device between
 // wtp_mesh_sample and the wtp_mesh_sample_get* calls; the batch buffers are reused by every batch and by the dart read-out.
-// wtp_mesh_fill runs in the same buffers (its seeds at the front of the accepted array), so one result is resident at a time.
+// wtp_mesh_fill and wtp_mesh_front run in the same buffers (their seeds at the front of the accepted array), so one result
+// is resident at a time.
 struct SampleState {
     bool valid = false;            // a result of the current mesh is resident ...
     bool fill = false;             // ... and it is wtp_mesh_fill's, behind n_seeds seed rows
+    bool front = false;            // ... or wtp_mesh_front's, likewise; `dart` then holds candidate indices
+    int front_per = 0;             // candidates per parent of that run
     int64_t n_seeds = 0;
     int dtype = -1;
     int64_t n = 0, cap = 0;        // samples held, rows the arrays below have room for

@@ -33,6 +33,13 @@
 // bounding box, of which only those inside the mesh (wtp_mesh_query's flag, wtp_mesh.hip) may be taken, and seed points
 // that occupy space from the start.  The seeds sit at the front of the accepted array and in its table; the counts the
 // stop rule carries are of accepted darts alone.  Everything from the cull to the insertion is the sampler's.
+//
+// The advancing front (wtp_mesh_front) is the run once more, over candidates that depend on what was
+// accepted: the accepted array, seeds first, is the queue, and candidate j = q n + s is thrown from queue entry q at its
+// spacing h_q.  A batch is the n candidates each of a range of parents that were all in the queue when it began, so its
+// candidates are known at launch and ordered as the serial loop takes them.  The conflict rule is one-sided (r_j alone)
+// and exempts the parent; the cull and the rounds are instantiated for it (kFront), the stop scan runs with a stall limit
+// it cannot reach, and the appended rows get their own h before the next batch can read them as parents.
 #include <climits>
 #include <cmath>
 
@@ -138,6 +145,12 @@ template <typename T> __device__ inline bool conflict(const Pt<T>& p, const Pt<T
     return ((dx * dx + dy * dy) + dz * dz) < m * m;
 }
 
+// the front's rule: p's radius alone; q's own spacing plays no part
+template <typename T> __device__ inline bool conflict_one_sided(const Pt<T>& p, const Pt<T>& q) {
+    const T dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
+    return ((dx * dx + dy * dy) + dz * dz) < p.w * p.w;
+}
+
 // Calls f(j, pts[j]) for every point j < count of the table that can be in conflict with p (and maybe others), until f
 // returns true.  A conflict has |fl(p.x - q.x)| < r_p on every axis, so q lies in a cell between those of the ball's
 // bounds, widened by the rounding of the bounds themselves.
@@ -213,6 +226,81 @@ __global__ void fill_gen_kernel(uint64_t seed, int64_t first, int64_t n, Box3<T>
 
 template <typename T> __device__ inline bool good_value(T v) { return v > (T)0 && v < Lim<T>::inf(); }
 
+// ---- the front's candidates (include/wtp.h, wtp_mesh_front) ---------------------------------------------------------------
+constexpr double front_factorial(int n) { return n <= 1 ? 1.0 : (double)n * front_factorial(n - 1); } // exact up to 19!
+template <typename T> struct FrontPoly { T s[9], c[9], quarter_pi; };                                  // S_1..S_9, C_1..C_9
+
+template <typename T> static FrontPoly<T> front_poly() {
+    FrontPoly<T> f;
+    for (int k = 1; k <= 9; ++k) {
+        const double sign = (k & 1) ? -1.0 : 1.0;
+        f.s[k - 1] = (T)(sign / front_factorial(2 * k + 1));
+        f.c[k - 1] = (T)(sign / front_factorial(2 * k));
+    }
+    f.quarter_pi = (T)(3.141592653589793 / 4.0);
+    return f;
+}
+
+// One thread per candidate i of the batch: candidate first + i, of parent par0 + i / per (a row of `parents`, w = h_q).
+// The gather is per-fold redundant within a wave; neighbouring lanes read the same 16 or 32 bytes, which the L1 serves
+// (DESIGN.md §8f.7).  A parent whose h is not finite and > 0 is never expanded: its candidates stay at its position
+// with its h as radius, which the cull reads as dead.
+template <typename T>
+__global__ void front_gen_kernel(uint64_t seed, int64_t first, int64_t n, const Pt<T>* __restrict__ parents, int64_t par0,
+                                 int32_t per, FrontPoly<T> poly, T* __restrict__ xyz, Pt<T>* __restrict__ pts) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const Pt<T> q = parents[par0 + i / per];
+        Pt<T> p = q;
+        if (good_value(q.w)) {
+            const uint64_t base = (seed << 40) + 2ull * (uint64_t)(first + i);
+            const T u = (T)((float)(sm_splitmix64(base) >> 40) * (1.0f / 16777216.0f));
+            const T v = (T)((float)(sm_splitmix64(base + 1) >> 40) * (1.0f / 16777216.0f));
+            const T z = (T)2 * u - (T)1;
+            const T rho = wsqrt((T)1 - z * z);
+            const T t = (T)8 * v;
+            const int o = (int)t; // 0 .. 7
+            const T f = t - (T)o;
+            const T g = (o & 1) ? (T)1 - f : f;
+            const T th = g * poly.quarter_pi;
+            const T x = th * th;
+            T as = poly.s[8], ac = poly.c[8];
+            for (int k = 7; k >= 0; --k) as = poly.s[k] + x * as, ac = poly.c[k] + x * ac;
+            const T s = th * ((T)1 + x * as);
+            const T c = (T)1 + x * ac;
+            T cl, sl;
+            switch (o) {
+                case 0: cl = c, sl = s; break;
+                case 1: cl = s, sl = c; break;
+                case 2: cl = -s, sl = c; break;
+                case 3: cl = -c, sl = s; break;
+                case 4: cl = -c, sl = -s; break;
+                case 5: cl = -s, sl = -c; break;
+                case 6: cl = s, sl = -c; break;
+                default: cl = c, sl = -s; break;
+            }
+            p.x = q.x + q.w * (rho * cl);
+            p.y = q.y + q.w * (rho * sl);
+            p.z = q.z + q.w * z;
+        }
+        xyz[3 * i] = p.x, xyz[3 * i + 1] = p.y, xyz[3 * i + 2] = p.z;
+        pts[i] = p;
+    }
+}
+
+// The rows the last batch appended get their own h as w (they held their parent's, the radius they were tested with); a
+// value that is not finite and > 0 is reported by the row's candidate index.
+template <typename T>
+__global__ void front_own_h_kernel(Pt<T>* __restrict__ rows, const int64_t* __restrict__ cand, const T* __restrict__ h,
+                                   int64_t n, SampleCtl* __restrict__ ctl) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const T hv = h[i];
+        rows[i].w = hv;
+        if (!good_value(hv)) atomicMin(&ctl->bad, (unsigned long long)cand[i]);
+    }
+}
+
 // r = T(factor) h; a spacing value that is not finite and > 0 is reported by the smallest dart index (report = false: the
 // cull reports it, for the darts that may be taken)
 template <typename T>
@@ -262,11 +350,14 @@ __global__ void sample_begin_kernel(SampleCtl* __restrict__ ctl) {
 }
 
 // ---- step 2: cull against the accepted samples; the live darts enter the batch's table ----------------------------------
-template <typename T>
+// kFront: the one-sided rule, never against the candidate's own parent (par0 + i / per), in the cell path and in the
+// linear scan alike
+template <typename T, bool kFront>
 __global__ void sample_cull_kernel(CellMap<T> m, const Pt<T>* __restrict__ b_pts, int32_t B, int32_t* __restrict__ st,
                                    Table acc, const int32_t* __restrict__ s_next, const Pt<T>* __restrict__ s_pts,
                                    int64_t n_acc, Table bt, int32_t* __restrict__ b_next,
-                                   const uint8_t* __restrict__ inside, int64_t first, SampleCtl* __restrict__ ctl) {
+                                   const uint8_t* __restrict__ inside, int64_t first, int32_t par0, int32_t per,
+                                   SampleCtl* __restrict__ ctl) {
     const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B) return;
     const Pt<T> p = b_pts[i];
@@ -275,14 +366,22 @@ __global__ void sample_cull_kernel(CellMap<T> m, const Pt<T>* __restrict__ b_pts
         if (!inside[i]) dead = true;
         else if (dead) atomicMin(&ctl->bad, (unsigned long long)(first + i));
     }
-    if (!dead)
-        for_near<T>(m, acc, s_next, s_pts, n_acc, p, [&](int32_t, const Pt<T>& q) { return dead = conflict<T>(p, q); });
+    if constexpr (kFront) {
+        const int32_t parent = par0 + i / per;
+        if (!dead)
+            for_near<T>(m, acc, s_next, s_pts, n_acc, p, [&](int32_t j, const Pt<T>& q) {
+                return dead = (j != parent && conflict_one_sided<T>(p, q));
+            });
+    } else {
+        if (!dead)
+            for_near<T>(m, acc, s_next, s_pts, n_acc, p, [&](int32_t, const Pt<T>& q) { return dead = conflict<T>(p, q); });
+    }
     st[i] = dead ? kCulled : 0;
     if (!dead) table_insert(bt, b_next, key_of(m, p), i);
 }
 
 // ---- step 3: one round.  g: position in the group; round: 1-based round of the batch -----------------------------------
-template <typename T>
+template <typename T, bool kFront>
 __global__ void sample_round_kernel(CellMap<T> m, const Pt<T>* __restrict__ b_pts, int32_t B, int32_t* __restrict__ st,
                                     Table bt, const int32_t* __restrict__ b_next, int g, int32_t round,
                                     SampleCtl* __restrict__ ctl) {
@@ -293,7 +392,7 @@ __global__ void sample_round_kernel(CellMap<T> m, const Pt<T>* __restrict__ b_pt
     bool rejected = false, pending = false;
     // the points of the table are the live darts; of a linear scan (count = i) the lower-numbered darts, culled ones too
     for_near<T>(m, bt, b_next, b_pts, (int64_t)B, p, [&](int32_t j, const Pt<T>& q) {
-        if (j >= i || !conflict<T>(p, q)) return false;
+        if (j >= i || !(kFront ? conflict_one_sided<T>(p, q) : conflict<T>(p, q))) return false;
         const int32_t s = __atomic_load_n(&st[j], __ATOMIC_RELAXED);
         if (s == 0 || (s >> 1) > round) pending = true; // undecided before this round
         else if (s & 1) rejected = true;
@@ -471,6 +570,7 @@ __global__ void sample_unpack_kernel(const Pt<T>* __restrict__ pts, int64_t n, T
 void sample_invalidate(wtp_ctx* ctx) {
     ctx->sample.valid = false;
     ctx->sample.fill = false;
+    ctx->sample.front = false;
     ctx->sample.n = 0;
     ctx->sample.n_seeds = 0;
 }
@@ -636,6 +736,107 @@ static int fill_seeds(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, c
     return sync(ctx); // `rows` leaves this scope
 }
 
+// The cell map, once a first batch of B points is in b_pts: cell edge sqrt(r_min r_max) of that batch (it changes time
+// only), cells over the mesh's box; the n_acc rows the accepted array already holds (seeds) enter its table now that
+// cells exist.  One host read.
+template <typename T>
+static int first_batch_map(wtp_ctx* ctx, int64_t B, int64_t n_acc, CellMap<T>* map_out, double* cell_edge) {
+    SampleState& S = ctx->sample;
+    SampleCtl* d_ctl = (SampleCtl*)S.ctl.p;
+    SampleCtl* pin = (SampleCtl*)ctx->host_pinned;
+    int rc;
+    hipLaunchKernelGGL(sample_range_kernel<T>, dim3(sm_stride_grid(B)), dim3(kSmThreads), 0, ctx->stream,
+                       (const Pt<T>*)S.b_pts.p, B, d_ctl);
+    WTP_HIP(ctx, hipMemcpyAsync(pin, d_ctl, sizeof(SampleCtl), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = sync(ctx))) return rc;
+    double ext = 0;
+    for (int a = 0; a < 3; ++a) ext = std::max(ext, ctx->mesh.bbox[3 + a] - ctx->mesh.bbox[a]);
+    double c = ext;
+    if (pin->rmin != kEmpty)
+        c = std::sqrt(__builtin_bit_cast(double, pin->rmin) * __builtin_bit_cast(double, pin->rmax));
+    c = std::min(std::max(c, ext / 1.0e6), ext > 0 ? ext : c); // at most 2^20 cells per axis, at least one
+    if (!(c > 0) || !std::isfinite(c)) c = 1;
+    CellMap<T> map{};
+    for (int a = 0; a < 3; ++a) {
+        map.org[a] = (T)ctx->mesh.bbox[a];
+        map.nc[a] = (int32_t)std::min(1048575.0, std::floor((ctx->mesh.bbox[3 + a] - ctx->mesh.bbox[a]) / c) + 1);
+    }
+    map.inv_c = (T)(1.0 / c);
+    *map_out = map;
+    *cell_edge = c;
+    if (n_acc > 0) {
+        hipLaunchKernelGGL(sample_rehash_kernel<T>, dim3(sm_stride_grid(n_acc)), dim3(kSmThreads), 0, ctx->stream, map,
+                           (const Pt<T>*)S.pts.p, table_view(S.table, S.tsz), (int32_t*)S.next.p, n_acc);
+        WTP_HIP(ctx, hipGetLastError());
+    }
+    return WTP_OK;
+}
+
+// what decide_batch needs to know of a batch whose points are in b_pts
+struct BatchArgs {
+    int64_t B, n_acc;          // points in the batch; rows of the accepted array (seeds included)
+    int64_t first, off;        // stream index of the batch's first point; seed rows at the front of the accepted array
+    int64_t max_points, stall_limit;
+    const uint8_t* inside;     // the domain test's flags (NULL: the surface sampler), counted into n_inside
+    const int32_t* tri;        // parent triangles to append (NULL: none)
+    int32_t par0, per;         // kFront: the batch's first parent and the candidates per parent
+};
+
+// Steps 2 to 4 for one batch: cull, rounds in groups of kGroup, and behind each group the stop scan, append, count,
+// finish and insert, all guarded by the group's last undecided count; one control-block read per group, left in the
+// pinned block for the caller.  kFront: the front's one-sided rule with the parent exempt.
+template <typename T, bool kFront>
+static int decide_batch(wtp_ctx* ctx, const CellMap<T>& map, const BatchArgs& a, int32_t* rounds_out) {
+    SampleState& S = ctx->sample;
+    SampleCtl* d_ctl = (SampleCtl*)S.ctl.p;
+    SampleCtl* pin = (SampleCtl*)ctx->host_pinned;
+    const Table acc = table_view(S.table, S.tsz), bt = table_view(S.b_table, S.b_tsz);
+    const int64_t B = a.B;
+    const int32_t Bi = (int32_t)B;
+    int rc;
+    WTP_HIP(ctx, hipMemsetAsync(S.b_table.p, 0xFF, 12 * (size_t)S.b_tsz, ctx->stream));
+    hipLaunchKernelGGL((sample_cull_kernel<T, kFront>), dim3(sm_grid(B)), dim3(kSmThreads), 0, ctx->stream, map,
+                       (const Pt<T>*)S.b_pts.p, Bi, (int32_t*)S.b_st.p, acc, (const int32_t*)S.next.p,
+                       (const Pt<T>*)S.pts.p, a.n_acc, bt, (int32_t*)S.b_next.p, a.inside, a.first, a.par0, a.per, d_ctl);
+    WTP_HIP(ctx, hipGetLastError());
+    int32_t round0 = 0;
+    for (;;) {
+        WTP_HIP(ctx, hipMemsetAsync(d_ctl->und, 0, sizeof(SampleCtl::und), ctx->stream));
+        for (int g = 0; g < kGroup; ++g)
+            hipLaunchKernelGGL((sample_round_kernel<T, kFront>), dim3(sm_grid(B)), dim3(kSmThreads), 0, ctx->stream, map,
+                               (const Pt<T>*)S.b_pts.p, Bi, (int32_t*)S.b_st.p, bt, (const int32_t*)S.b_next.p, g,
+                               round0 + g + 1, d_ctl);
+        int2* blk = (int2*)S.b_blk.p;
+        const int32_t nblk = scan_tiles(B);
+        hipLaunchKernelGGL(sample_scan_a_kernel, dim3(nblk), dim3(kSmThreads), 0, ctx->stream, (const int32_t*)S.b_st.p, Bi,
+                           blk, d_ctl);
+        hipLaunchKernelGGL(sample_scan_b_kernel, dim3(1), dim3(kSmThreads), 0, ctx->stream, blk, nblk, blk + nblk, d_ctl);
+        hipLaunchKernelGGL(sample_scan_c_kernel, dim3(nblk), dim3(kSmThreads), 0, ctx->stream, (const int32_t*)S.b_st.p, Bi,
+                           blk + nblk, (int32_t*)S.b_pos.p, (int32_t*)S.b_last.p, a.max_points, a.stall_limit, d_ctl);
+        hipLaunchKernelGGL(sample_append_kernel<T>, dim3(sm_grid(B)), dim3(kSmThreads), 0, ctx->stream,
+                           (const Pt<T>*)S.b_pts.p, a.tri, (const int32_t*)S.b_st.p, Bi, (const int32_t*)S.b_pos.p, a.first,
+                           a.off, (Pt<T>*)S.pts.p, (int32_t*)S.tri.p, (int64_t*)S.dart.p, d_ctl);
+        if (a.inside)
+            hipLaunchKernelGGL(fill_count_kernel, dim3(sm_grid(B)), dim3(kSmThreads), 0, ctx->stream, a.inside, Bi, d_ctl);
+        hipLaunchKernelGGL(sample_finish_kernel, dim3(1), dim3(1), 0, ctx->stream, (const int32_t*)S.b_pos.p,
+                           (const int32_t*)S.b_last.p, Bi, a.first, a.max_points, d_ctl);
+        hipLaunchKernelGGL(sample_insert_kernel<T>, dim3(sm_grid(B)), dim3(kSmThreads), 0, ctx->stream, map,
+                           (const Pt<T>*)S.pts.p, acc, (int32_t*)S.next.p, Bi, a.off, d_ctl);
+        WTP_HIP(ctx, hipGetLastError());
+        WTP_HIP(ctx, hipMemcpyAsync(pin, d_ctl, sizeof(SampleCtl), hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = sync(ctx))) return rc;
+        if (pin->und[kGroup - 1] == 0) {
+            int g = 0;
+            while (pin->und[g] != 0) ++g;
+            *rounds_out = round0 + g + 1;
+            return WTP_OK;
+        }
+        round0 += kGroup;
+        if (round0 >= B) return fail(ctx, WTP_ERR_INTERNAL, "a batch was not decided within as many rounds as it has points");
+    }
+}
+
+
 // what a run reports: the fields of wtp_sample_info and wtp_fill_info
 struct RunInfo {
     int64_t n_points, n_darts, n_inside, batch;
@@ -694,7 +895,7 @@ static int sample_run(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, i
             S.tsz = pow2_at_least(2 * S.cap); // buffers of an earlier call, or the seeds' own: the table is stale
             rehash = true;
         }
-        const Table acc = table_view(S.table, S.tsz), bt = table_view(S.b_table, S.b_tsz);
+        const Table acc = table_view(S.table, S.tsz);
         if (rehash) WTP_HIP(ctx, hipMemsetAsync(S.table.p, 0xFF, 12 * (size_t)S.tsz, ctx->stream));
         if (rehash && n > 0 && have_map) {
             hipLaunchKernelGGL(sample_rehash_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream, map,
@@ -703,75 +904,14 @@ static int sample_run(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, i
         }
         hipLaunchKernelGGL(sample_begin_kernel, dim3(1), dim3(1), 0, ctx->stream, d_ctl);
         if ((rc = enqueue_darts<T>(ctx, sp, factor, seed, first, B, fill))) return rc;
-        if (!have_map) { // the cell edge: sqrt(r_min r_max) of the first batch (it changes time only)
-            hipLaunchKernelGGL(sample_range_kernel<T>, dim3(sm_stride_grid(B)), dim3(kSmThreads), 0, ctx->stream,
-                               (const Pt<T>*)S.b_pts.p, B, d_ctl);
-            WTP_HIP(ctx, hipMemcpyAsync(pin, d_ctl, sizeof(SampleCtl), hipMemcpyDeviceToHost, ctx->stream));
-            if ((rc = sync(ctx))) return rc;
-            double ext = 0;
-            for (int a = 0; a < 3; ++a) ext = std::max(ext, ctx->mesh.bbox[3 + a] - ctx->mesh.bbox[a]);
-            double c = ext;
-            if (pin->rmin != kEmpty)
-                c = std::sqrt(__builtin_bit_cast(double, pin->rmin) * __builtin_bit_cast(double, pin->rmax));
-            c = std::min(std::max(c, ext / 1.0e6), ext > 0 ? ext : c); // at most 2^20 cells per axis, at least one
-            if (!(c > 0) || !std::isfinite(c)) c = 1;
-            for (int a = 0; a < 3; ++a) {
-                map.org[a] = (T)ctx->mesh.bbox[a];
-                map.nc[a] = (int32_t)std::min(1048575.0, std::floor((ctx->mesh.bbox[3 + a] - ctx->mesh.bbox[a]) / c) + 1);
-            }
-            map.inv_c = (T)(1.0 / c);
-            cell_edge = c;
+        if (!have_map) {
+            if ((rc = first_batch_map<T>(ctx, B, n, &map, &cell_edge))) return rc;
             have_map = true;
-            if (n > 0) { // the fill's seeds enter the table now that cells exist
-                hipLaunchKernelGGL(sample_rehash_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream, map,
-                                   (const Pt<T>*)S.pts.p, acc, (int32_t*)S.next.p, n);
-                WTP_HIP(ctx, hipGetLastError());
-            }
         }
-        WTP_HIP(ctx, hipMemsetAsync(S.b_table.p, 0xFF, 12 * (size_t)S.b_tsz, ctx->stream));
-        const int32_t Bi = (int32_t)B;
-        hipLaunchKernelGGL(sample_cull_kernel<T>, dim3(sm_grid(B)), dim3(kSmThreads), 0, ctx->stream, map,
-                           (const Pt<T>*)S.b_pts.p, Bi, (int32_t*)S.b_st.p, acc, (const int32_t*)S.next.p,
-                           (const Pt<T>*)S.pts.p, n, bt, (int32_t*)S.b_next.p,
-                           fill ? (const uint8_t*)S.b_in.p : (const uint8_t*)nullptr, first, d_ctl);
-        WTP_HIP(ctx, hipGetLastError());
-        int32_t round0 = 0, rounds = 0;
-        for (;;) {
-            WTP_HIP(ctx, hipMemsetAsync(d_ctl->und, 0, sizeof(h.und), ctx->stream));
-            for (int g = 0; g < kGroup; ++g)
-                hipLaunchKernelGGL(sample_round_kernel<T>, dim3(sm_grid(B)), dim3(kSmThreads), 0, ctx->stream, map,
-                                   (const Pt<T>*)S.b_pts.p, Bi, (int32_t*)S.b_st.p, bt, (const int32_t*)S.b_next.p, g,
-                                   round0 + g + 1, d_ctl);
-            int2* blk = (int2*)S.b_blk.p;
-            const int32_t nblk = scan_tiles(B);
-            hipLaunchKernelGGL(sample_scan_a_kernel, dim3(nblk), dim3(kSmThreads), 0, ctx->stream, (const int32_t*)S.b_st.p, Bi,
-                               blk, d_ctl);
-            hipLaunchKernelGGL(sample_scan_b_kernel, dim3(1), dim3(kSmThreads), 0, ctx->stream, blk, nblk, blk + nblk, d_ctl);
-            hipLaunchKernelGGL(sample_scan_c_kernel, dim3(nblk), dim3(kSmThreads), 0, ctx->stream, (const int32_t*)S.b_st.p, Bi,
-                               blk + nblk, (int32_t*)S.b_pos.p, (int32_t*)S.b_last.p, max_points, stall_limit, d_ctl);
-            hipLaunchKernelGGL(sample_append_kernel<T>, dim3(sm_grid(B)), dim3(kSmThreads), 0, ctx->stream,
-                               (const Pt<T>*)S.b_pts.p, fill ? (const int32_t*)nullptr : (const int32_t*)S.b_tri.p,
-                               (const int32_t*)S.b_st.p, Bi, (const int32_t*)S.b_pos.p, first, ns, (Pt<T>*)S.pts.p,
-                               (int32_t*)S.tri.p, (int64_t*)S.dart.p, d_ctl);
-            if (fill)
-                hipLaunchKernelGGL(fill_count_kernel, dim3(sm_grid(B)), dim3(kSmThreads), 0, ctx->stream,
-                                   (const uint8_t*)S.b_in.p, Bi, d_ctl);
-            hipLaunchKernelGGL(sample_finish_kernel, dim3(1), dim3(1), 0, ctx->stream, (const int32_t*)S.b_pos.p,
-                               (const int32_t*)S.b_last.p, Bi, first, max_points, d_ctl);
-            hipLaunchKernelGGL(sample_insert_kernel<T>, dim3(sm_grid(B)), dim3(kSmThreads), 0, ctx->stream, map,
-                               (const Pt<T>*)S.pts.p, acc, (int32_t*)S.next.p, Bi, ns, d_ctl);
-            WTP_HIP(ctx, hipGetLastError());
-            WTP_HIP(ctx, hipMemcpyAsync(pin, d_ctl, sizeof(SampleCtl), hipMemcpyDeviceToHost, ctx->stream));
-            if ((rc = sync(ctx))) return rc;
-            if (pin->und[kGroup - 1] == 0) {
-                int g = 0;
-                while (pin->und[g] != 0) ++g;
-                rounds = round0 + g + 1;
-                break;
-            }
-            round0 += kGroup;
-            if (round0 >= B) return fail(ctx, WTP_ERR_INTERNAL, "a batch was not decided within as many rounds as it has darts");
-        }
+        int32_t rounds = 0;
+        const BatchArgs args{B, n, first, ns, max_points, stall_limit, fill ? (const uint8_t*)S.b_in.p : (const uint8_t*)nullptr,
+                             fill ? (const int32_t*)nullptr : (const int32_t*)S.b_tri.p, 0, 1};
+        if ((rc = decide_batch<T, false>(ctx, map, args, &rounds))) return rc;
         ++n_batches;
         rounds_max = std::max(rounds_max, rounds);
         if (pin->stopped == 3) return fail(ctx, WTP_ERR_ARG, bad_spacing_text(pin->bad));
@@ -840,6 +980,196 @@ static int sample_darts(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor,
     return WTP_OK;
 }
 
+// ---- the advancing front ---------------------------------------------------------------------------------------------------
+struct FrontInfo {
+    int64_t n_points, n_parents, n_candidates, n_inside, batch;
+    int32_t stop_reason, n_batches, rounds_max, host_syncs;
+    double r_min, r_max;
+};
+
+// Candidates of the parents [par0, par0 + np) of `parents` (rows with w = h) into b_xyz, b_pts (w = r_j = h_q) and b_in.
+template <typename T>
+static int enqueue_candidates(wtp_ctx* ctx, uint64_t seed, const Pt<T>* parents, int64_t par0, int64_t first, int64_t B, int per) {
+    SampleState& S = ctx->sample;
+    hipLaunchKernelGGL(front_gen_kernel<T>, dim3(sm_stride_grid(B)), dim3(kSmThreads), 0, ctx->stream, seed, first, B, parents,
+                       par0, (int32_t)per, front_poly<T>(), (T*)S.b_xyz.p, (Pt<T>*)S.b_pts.p);
+    WTP_HIP(ctx, hipGetLastError());
+    return launch_mesh_inside<T>(ctx, (const T*)S.b_xyz.p, B, (uint8_t*)S.b_in.p);
+}
+
+// The run of wtp_mesh_front: parents in queue order, batches of whole parents that were in the queue when the batch began.
+template <typename T>
+static int front_run(wtp_ctx* ctx, const wtp_spacing_desc* sp, int per, const T* seeds, int64_t ns, int64_t max_points,
+                     uint64_t seed, int64_t batch, FrontInfo* info) {
+    SampleState& S = ctx->sample;
+    const int dtype = sizeof(T) == 4 ? WTP_F32 : WTP_F64;
+    const int64_t syncs0 = ctx->n_syncs;
+    const bool law = spacing_on_device(sp->kind);
+    int rc;
+    sample_invalidate(ctx);
+    *info = FrontInfo{};
+    info->stop_reason = 1;
+    if (ns == 0) { // nothing to expand: the front has died out before it began
+        S.dtype = S.dtype < 0 ? dtype : S.dtype;
+        S.front = true, S.front_per = per, S.valid = true;
+        return WTP_OK;
+    }
+    if (law && (rc = ensure_kd(ctx, sp, 3, dtype))) return rc;
+    if ((rc = ensure_pinned(ctx, sizeof(SampleCtl)))) return rc;
+    if (S.dtype != dtype) S.cap = 0, S.bcap = 0; // the rows have another size
+    // parents per batch: at most kBatchMax candidates, whatever `batch` asks for (the kernels run one thread per candidate
+    // of a grid of at most 2^20 blocks, and the batch changes time only)
+    const int64_t par_cap = std::max<int64_t>(kBatchMax / per, 1);
+    const int64_t par_max = batch > 0 ? std::min(batch, par_cap) : par_cap;
+    int64_t B = std::min(ns, par_max) * per;
+    if ((rc = ensure_batch<T>(ctx, pow2_at_least(std::max(B, kBatchFirst))))) return rc;
+    S.dtype = dtype;
+    {
+        bool replaced = false;
+        if ((rc = ensure_rows<T>(ctx, 0, ns + std::min(B, max_points), &replaced))) return rc;
+        if ((rc = fill_seeds<T>(ctx, sp, 1.0, seeds, ns))) return rc; // w = T(1) h = h, every one checked
+    }
+    SampleCtl h{};
+    h.bad = kEmpty, h.rmin = kEmpty, h.rmax = 0, h.end = INT_MAX;
+    SampleCtl* d_ctl = (SampleCtl*)S.ctl.p;
+    SampleCtl* pin = (SampleCtl*)ctx->host_pinned;
+    *pin = h;
+    WTP_HIP(ctx, hipMemcpyAsync(d_ctl, pin, sizeof(SampleCtl), hipMemcpyHostToDevice, ctx->stream));
+
+    CellMap<T> map{};
+    bool have_map = false, classes = false;
+    double cell_edge = 0;
+    int64_t q0 = 0, n = ns; // parents expanded so far; queue length (rows of the accepted array, seeds included)
+    int32_t n_batches = 0, rounds_max = 0;
+    for (;;) {
+        const int64_t q1 = std::min(n, q0 + par_max), first = q0 * per;
+        B = (q1 - q0) * per;
+        const int64_t room = std::min(B, max_points - (n - ns)); // rows the batch can append
+        const int64_t bwant = pow2_at_least(std::max(B, kBatchFirst));
+        if (bwant > S.bcap && (rc = sync(ctx))) return rc; // the last batch's law pass still reads the batch buffers
+        if ((rc = ensure_batch<T>(ctx, bwant))) return rc;
+        if (have_map && !classes) { // as the fill: once more candidates were tested than a class grid has cells
+            const int64_t cells = mesh_class_cells(ctx, cell_edge);
+            if (cells <= first && cells <= (int64_t(1) << 26)) {
+                if ((rc = mesh_ensure_classes(ctx, cell_edge))) return rc;
+                classes = true;
+            }
+        }
+        bool rehash = false;
+        if ((rc = ensure_rows<T>(ctx, n, n + room, &rehash))) return rc;
+        if (n_batches == 0) {
+            S.tsz = pow2_at_least(2 * S.cap); // buffers of an earlier call, or the seeds' own: the table is stale
+            rehash = true;
+        }
+        const Table acc = table_view(S.table, S.tsz);
+        if (rehash) WTP_HIP(ctx, hipMemsetAsync(S.table.p, 0xFF, 12 * (size_t)S.tsz, ctx->stream));
+        if (rehash && have_map) {
+            hipLaunchKernelGGL(sample_rehash_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream, map,
+                               (const Pt<T>*)S.pts.p, acc, (int32_t*)S.next.p, n);
+            WTP_HIP(ctx, hipGetLastError());
+        }
+        hipLaunchKernelGGL(sample_begin_kernel, dim3(1), dim3(1), 0, ctx->stream, d_ctl);
+        if ((rc = enqueue_candidates<T>(ctx, seed, (const Pt<T>*)S.pts.p, q0, first, B, per))) return rc;
+        if (!have_map) {
+            if ((rc = first_batch_map<T>(ctx, B, n, &map, &cell_edge))) return rc;
+            have_map = true;
+        }
+        int32_t rounds = 0;
+        // a stall limit no miss run can reach: only max_points ends the scan
+        const BatchArgs args{B, n, first, ns, max_points, (int64_t)LLONG_MAX, (const uint8_t*)S.b_in.p, (const int32_t*)nullptr,
+                             (int32_t)q0, (int32_t)per};
+        if ((rc = decide_batch<T, true>(ctx, map, args, &rounds))) return rc;
+        ++n_batches;
+        rounds_max = std::max(rounds_max, rounds);
+        // an accepted point of an earlier batch whose own h is bad (the rows of this batch are evaluated below)
+        if (pin->bad != kEmpty) return fail(ctx, WTP_ERR_ARG, "the spacing at the point accepted from candidate " + std::to_string(pin->bad) + " is not finite and > 0");
+        const int64_t n_new = pin->n_new;
+        if (n_new > room) return fail(ctx, WTP_ERR_INTERNAL, "a batch appended more rows than it had room for");
+        if (law && n_new > 0) { // step 7: the new rows' own h, before they can be parents
+            Pt<T>* rows = (Pt<T>*)S.pts.p + n;
+            if ((rc = sample_unpack<T>(ctx, rows, n_new, (T*)S.b_xyz.p, nullptr))) return rc;
+            if ((rc = launch_spacing_eval<T>(ctx, (const T*)S.b_xyz.p, n_new, 3, ctx->kd.nodes.p, ctx->kd.m, sp->kind, sp->p0,
+                                             sp->p1, sp->p2, (T*)S.b_h.p)))
+                return rc;
+            hipLaunchKernelGGL(front_own_h_kernel<T>, dim3(sm_stride_grid(n_new)), dim3(kSmThreads), 0, ctx->stream, rows,
+                               (const int64_t*)S.dart.p + n, (const T*)S.b_h.p, n_new, d_ctl);
+            WTP_HIP(ctx, hipGetLastError());
+        }
+        n += n_new;
+        q0 = q1;
+        if (pin->stopped) break;  // max_points
+        if (q0 == n) break;       // nothing was appended and every entry has been expanded: the front has died out
+    }
+    // h over the accepted points
+    h = *pin;
+    WTP_HIP(ctx, hipMemcpyAsync(pin, d_ctl, sizeof(SampleCtl), hipMemcpyDeviceToHost, ctx->stream)); // the last rows' bad values
+    if ((rc = sync(ctx))) return rc;
+    if (pin->bad != kEmpty) return fail(ctx, WTP_ERR_ARG, "the spacing at the point accepted from candidate " + std::to_string(pin->bad) + " is not finite and > 0");
+    pin->rmin = kEmpty, pin->rmax = 0;
+    WTP_HIP(ctx, hipMemcpyAsync(d_ctl, pin, sizeof(SampleCtl), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(sample_range_kernel<T>, dim3(sm_stride_grid(n - ns)), dim3(kSmThreads), 0, ctx->stream,
+                       (const Pt<T>*)S.pts.p + ns, n - ns, d_ctl);
+    WTP_HIP(ctx, hipGetLastError());
+    WTP_HIP(ctx, hipMemcpyAsync(pin, d_ctl, sizeof(SampleCtl), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = sync(ctx))) return rc;
+    S.n = n - ns;
+    S.n_seeds = ns;
+    S.front = true, S.front_per = per;
+    S.valid = true;
+    info->n_points = n - ns;
+    info->n_candidates = h.n_darts;
+    info->n_parents = (h.n_darts + per - 1) / per;
+    info->n_inside = (int64_t)h.n_inside;
+    info->batch = B / per;
+    info->stop_reason = h.stopped ? 2 : 1;
+    info->n_batches = n_batches;
+    info->rounds_max = rounds_max;
+    info->host_syncs = (int32_t)(ctx->n_syncs - syncs0);
+    info->r_min = pin->rmin != kEmpty ? __builtin_bit_cast(double, pin->rmin) : 0.0;
+    info->r_max = __builtin_bit_cast(double, pin->rmax);
+    return WTP_OK;
+}
+
+// wtp_mesh_front_candidates: the candidates of np parent positions (host), parent p being queue entry first_parent + p
+template <typename T>
+static int front_candidates(wtp_ctx* ctx, const wtp_spacing_desc* sp, uint64_t seed, const T* parents, int64_t np,
+                            int64_t first_parent, int per, T* xyz_out, uint8_t* inside_out, T* r_out) {
+    SampleState& S = ctx->sample;
+    const int dtype = sizeof(T) == 4 ? WTP_F32 : WTP_F64;
+    const bool law = spacing_on_device(sp->kind);
+    int rc;
+    if (law && (rc = ensure_kd(ctx, sp, 3, dtype))) return rc;
+    if (S.dtype != dtype) S.cap = 0, S.bcap = 0, S.dtype = dtype; // (a result of another dtype died with its mesh)
+    const int64_t chunk = std::min(np, std::max<int64_t>(kReadChunk / per, 1)); // parents per piece
+    if ((rc = ensure_batch<T>(ctx, std::max(chunk * per, S.bcap)))) return rc;
+    DevBuf par; // per piece: xyz (3 T), h (T), rows (Pt)
+    if ((rc = ensure(ctx, par, (sizeof(T) * 4 + sizeof(Pt<T>)) * (size_t)chunk))) return rc;
+    T* d_xyz = (T*)par.p;
+    T* d_h = d_xyz + 3 * chunk;
+    Pt<T>* d_rows = (Pt<T>*)(d_h + chunk);
+    for (int64_t done = 0; done < np; done += chunk) {
+        const int64_t m = std::min(chunk, np - done), B = m * per;
+        WTP_HIP(ctx, hipMemcpyAsync(d_xyz, parents + 3 * done, sizeof(T) * 3 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+        if (law && (rc = launch_spacing_eval<T>(ctx, d_xyz, m, 3, ctx->kd.nodes.p, ctx->kd.m, sp->kind, sp->p0, sp->p1, sp->p2, d_h)))
+            return rc;
+        hipLaunchKernelGGL(sample_radius_kernel<T>, dim3(sm_stride_grid(m)), dim3(kSmThreads), 0, ctx->stream, (const T*)d_xyz,
+                           law ? (const T*)d_h : (const T*)nullptr, (T)sp->constant, (T)1, (int64_t)0, m, d_rows, false,
+                           (SampleCtl*)nullptr);
+        WTP_HIP(ctx, hipGetLastError());
+        if ((rc = enqueue_candidates<T>(ctx, seed, d_rows, 0, (first_parent + done) * per, B, per))) return rc;
+        const int64_t o = done * per;
+        if (xyz_out)
+            WTP_HIP(ctx, hipMemcpyAsync(xyz_out + 3 * o, S.b_xyz.p, sizeof(T) * 3 * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
+        if (inside_out) WTP_HIP(ctx, hipMemcpyAsync(inside_out + o, S.b_in.p, (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
+        if (r_out) {
+            if ((rc = sample_unpack<T>(ctx, S.b_pts.p, B, nullptr, (T*)S.b_h.p))) return rc;
+            WTP_HIP(ctx, hipMemcpyAsync(r_out + o, S.b_h.p, sizeof(T) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        if ((rc = sync(ctx))) return rc; // `par` is freed only after the last piece has been read
+    }
+    return WTP_OK;
+}
+
 } // namespace wtp
 
 using namespace wtp;
@@ -895,7 +1225,7 @@ static int rows_to_host(wtp_ctx* ctx, int64_t first, void* xyz_out, void* r_out)
 WTP_API int wtp_mesh_sample_get(wtp_ctx* ctx, void* xyz_out, int32_t* tri_out, void* r_out, int64_t* dart_out) {
     if (!ctx) return WTP_ERR_ARG;
     SampleState& S = ctx->sample;
-    if (!S.valid || S.fill) return fail(ctx, WTP_ERR_STATE, "no sample: call wtp_mesh_sample first");
+    if (!S.valid || S.fill || S.front) return fail(ctx, WTP_ERR_STATE, "no sample: call wtp_mesh_sample first");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)S.n;
     int rc;
@@ -918,7 +1248,7 @@ static int rows_to_dev(wtp_ctx* ctx, int64_t first, void* d_xyz_out, void* d_r_o
 WTP_API int wtp_mesh_sample_get_dev(wtp_ctx* ctx, void* d_xyz_out, int32_t* d_tri_out, void* d_r_out) {
     if (!ctx) return WTP_ERR_ARG;
     SampleState& S = ctx->sample;
-    if (!S.valid || S.fill) return fail(ctx, WTP_ERR_STATE, "no sample: call wtp_mesh_sample first");
+    if (!S.valid || S.fill || S.front) return fail(ctx, WTP_ERR_STATE, "no sample: call wtp_mesh_sample first");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     const int rc = rows_to_dev(ctx, 0, d_xyz_out, d_r_out);
     if (rc) return rc;
@@ -972,7 +1302,7 @@ WTP_API int wtp_mesh_fill(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double 
 WTP_API int wtp_mesh_fill_get(wtp_ctx* ctx, void* xyz_out, void* r_out, int64_t* dart_out) {
     if (!ctx) return WTP_ERR_ARG;
     SampleState& S = ctx->sample;
-    if (!S.valid || !S.fill) return fail(ctx, WTP_ERR_STATE, "no fill: call wtp_mesh_fill first");
+    if (!S.valid || !S.fill || S.front) return fail(ctx, WTP_ERR_STATE, "no fill: call wtp_mesh_fill first");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     int rc;
     if ((xyz_out || r_out) && (rc = rows_to_host(ctx, S.n_seeds, xyz_out, r_out))) return rc;
@@ -984,7 +1314,7 @@ WTP_API int wtp_mesh_fill_get(wtp_ctx* ctx, void* xyz_out, void* r_out, int64_t*
 WTP_API int wtp_mesh_fill_get_dev(wtp_ctx* ctx, void* d_xyz_out, void* d_r_out) {
     if (!ctx) return WTP_ERR_ARG;
     SampleState& S = ctx->sample;
-    if (!S.valid || !S.fill) return fail(ctx, WTP_ERR_STATE, "no fill: call wtp_mesh_fill first");
+    if (!S.valid || !S.fill || S.front) return fail(ctx, WTP_ERR_STATE, "no fill: call wtp_mesh_fill first");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     const int rc = rows_to_dev(ctx, S.n_seeds, d_xyz_out, d_r_out);
     if (rc) return rc;
@@ -1001,5 +1331,87 @@ WTP_API int wtp_mesh_fill_darts(wtp_ctx* ctx, const wtp_spacing_desc* spacing, d
     return by_dtype(ctx->mesh.dtype, [&](auto t) {
         using T = decltype(t);
         return sample_darts<T>(ctx, spacing, factor, seed, first, n, true, (T*)xyz_out, nullptr, inside_out, (T*)r_out);
+    });
+}
+
+// ---- the advancing front -------------------------------------------------------------------------------------------------
+static int check_front_args(wtp_ctx* ctx, const wtp_spacing_desc* spacing, int64_t n, uint64_t seed) {
+    const int rc = check_sample_args(ctx, spacing, 1.0, seed);
+    if (rc) return rc;
+    if (n < 1 || n > 64) return fail(ctx, WTP_ERR_ARG, "n (candidates per parent) must be in [1, 64]");
+    return WTP_OK;
+}
+
+WTP_API int wtp_mesh_front(wtp_ctx* ctx, const wtp_spacing_desc* spacing, int64_t n, const void* seeds, int64_t n_seeds,
+                           int64_t max_points, uint64_t seed, int64_t batch, wtp_front_info* info) {
+    if (!ctx) return WTP_ERR_ARG;
+    int rc = check_front_args(ctx, spacing, n, seed);
+    if (rc) return rc;
+    if (max_points < 1) return fail(ctx, WTP_ERR_ARG, "max_points must be positive");
+    if (batch < 0 || batch > (int64_t(1) << 24)) return fail(ctx, WTP_ERR_ARG, "batch must be in [0, 2^24]");
+    if (n_seeds < 0) return fail(ctx, WTP_ERR_ARG, "n_seeds must not be negative");
+    if (n_seeds > 0 && !seeds) return fail(ctx, WTP_ERR_ARG, "seeds is NULL");
+    // the queue holds at most n_seeds + max_points rows, indexed in int32: refused here, not in the middle of a run
+    if (n_seeds >= (int64_t(1) << 31) || max_points >= (int64_t(1) << 31) || n_seeds + max_points >= (int64_t(1) << 31) - 1)
+        return fail(ctx, WTP_ERR_ARG, "n_seeds + max_points exceed the int32 index space of the queue");
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    FrontInfo fi{};
+    rc = by_dtype(ctx->mesh.dtype, [&](auto t) {
+        using T = decltype(t);
+        return front_run<T>(ctx, spacing, (int)n, (const T*)seeds, n_seeds, max_points, seed, batch, &fi);
+    });
+    if (rc || !info) return rc;
+    info->n_points = fi.n_points, info->n_parents = fi.n_parents, info->n_candidates = fi.n_candidates;
+    info->n_inside = fi.n_inside, info->n_seeds = n_seeds, info->batch = fi.batch;
+    info->stop_reason = fi.stop_reason;
+    info->n_batches = fi.n_batches, info->rounds_max = fi.rounds_max, info->host_syncs = fi.host_syncs;
+    info->r_min = fi.r_min, info->r_max = fi.r_max;
+    return WTP_OK;
+}
+
+WTP_API int wtp_mesh_front_get(wtp_ctx* ctx, void* xyz_out, void* h_out, int64_t* cand_out, int32_t* parent_out) {
+    if (!ctx) return WTP_ERR_ARG;
+    SampleState& S = ctx->sample;
+    if (!S.valid || !S.front) return fail(ctx, WTP_ERR_STATE, "no front: call wtp_mesh_front first");
+    if (S.n == 0) return WTP_OK;
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if ((xyz_out || h_out) && (rc = rows_to_host(ctx, S.n_seeds, xyz_out, h_out))) return rc;
+    std::vector<int64_t> cand;
+    int64_t* c = cand_out;
+    if (parent_out && !c) cand.resize((size_t)S.n), c = cand.data();
+    if (c) WTP_HIP(ctx, hipMemcpyAsync(c, (const int64_t*)S.dart.p + S.n_seeds, 8 * (size_t)S.n, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = sync(ctx))) return rc;
+    if (parent_out)
+        for (int64_t i = 0; i < S.n; ++i) parent_out[i] = (int32_t)(c[i] / S.front_per); // candidate j = q n + s
+    return WTP_OK;
+}
+
+WTP_API int wtp_mesh_front_get_dev(wtp_ctx* ctx, void* d_xyz_out, void* d_h_out) {
+    if (!ctx) return WTP_ERR_ARG;
+    SampleState& S = ctx->sample;
+    if (!S.valid || !S.front) return fail(ctx, WTP_ERR_STATE, "no front: call wtp_mesh_front first");
+    if (S.n == 0) return WTP_OK;
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    const int rc = rows_to_dev(ctx, S.n_seeds, d_xyz_out, d_h_out);
+    if (rc) return rc;
+    return sync(ctx);
+}
+
+WTP_API int wtp_mesh_front_candidates(wtp_ctx* ctx, const wtp_spacing_desc* spacing, uint64_t seed, const void* parents_xyz,
+                                      int64_t n_parents, int64_t first_parent, int64_t n, void* xyz_out, uint8_t* inside_out,
+                                      void* r_out) {
+    if (!ctx) return WTP_ERR_ARG;
+    int rc = check_front_args(ctx, spacing, n, seed);
+    if (rc) return rc;
+    if (n_parents < 0 || first_parent < 0 || n_parents > (int64_t(1) << 31) || first_parent > (int64_t(1) << 31))
+        return fail(ctx, WTP_ERR_ARG, "bad parent range");
+    if (n_parents == 0) return WTP_OK;
+    if (!parents_xyz) return fail(ctx, WTP_ERR_ARG, "parents_xyz is NULL");
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    return by_dtype(ctx->mesh.dtype, [&](auto t) {
+        using T = decltype(t);
+        return front_candidates<T>(ctx, spacing, seed, (const T*)parents_xyz, n_parents, first_parent, (int)n, (T*)xyz_out,
+                                   inside_out, (T*)r_out);
     });
 }

@@ -454,6 +454,66 @@ class Context:
         del keep
         return xyz, inside.astype(bool), r
 
+    # ---- advancing-front fill of the mesh's volume (discretize's SlakKosec; wtp_mesh_front) ------------------------------
+    def _seed_rows(self, seeds):
+        if seeds is None or not len(seeds):
+            return None
+        s = np.ascontiguousarray(seeds, dtype=self._mesh_dtype())
+        if s.ndim != 2 or s.shape[1] != 3:
+            raise L.WtpArgumentError("seeds must have shape (n, 3)")
+        return s
+
+    def mesh_front(self, spacing, n: int = 10, seeds=None, max_points: int = 10_000_000, seed: int = 0, batch: int = 0,
+                   spacing_desc=None):
+        """wtp_mesh_front on the mesh of mesh_set: the serial advancing front over the seeded stream, n candidates per
+        queue entry, decided in batches of parents on the device.  seeds: (m, 3) points, the head of the queue (converted
+        to the mesh's dtype), or None.  Returns the info dict; the points stay on the device (mesh_front_get)."""
+        sd, keep = (spacing_desc, None) if spacing_desc is not None else self._sample_spacing(spacing)
+        s = self._seed_rows(seeds)
+        info = L.FrontInfo()
+        rc = self._lib.wtp_mesh_front(self._h, C.byref(sd), int(n), _vp(s), 0 if s is None else len(s), int(max_points),
+                                      C.c_uint64(int(seed)), int(batch), C.byref(info))
+        L.check(self._h, rc)
+        del keep
+        return {name: getattr(info, name) for name, _ in L.FrontInfo._fields_}
+
+    def mesh_front_get(self, n: int, want=("xyz", "h", "cand", "parent")):
+        """The n = info['n_points'] points of the last mesh_front as a dict of host arrays (mesh dtype): xyz, their own
+        h, the candidate index each came from and its parent's queue index."""
+        dt = self._mesh_dtype()
+        out = {}
+        if "xyz" in want:
+            out["xyz"] = np.empty((n, 3), dtype=dt)
+        if "h" in want:
+            out["h"] = np.empty(n, dtype=dt)
+        if "cand" in want:
+            out["cand"] = np.empty(n, dtype=np.int64)
+        if "parent" in want:
+            out["parent"] = np.empty(n, dtype=np.int32)
+        rc = self._lib.wtp_mesh_front_get(self._h, _vp(out.get("xyz")), _vp(out.get("h")), _vp(out.get("cand")),
+                                          _vp(out.get("parent")))
+        L.check(self._h, rc)
+        return out
+
+    def mesh_front_get_dev(self, d_xyz_ptr: int = 0, d_h_ptr: int = 0):
+        """wtp_mesh_front_get_dev: the points into device arrays given as addresses (0 = absent)."""
+        rc = self._lib.wtp_mesh_front_get_dev(self._h, C.c_void_p(d_xyz_ptr or None), C.c_void_p(d_h_ptr or None))
+        L.check(self._h, rc)
+
+    def mesh_front_candidates(self, spacing, seed: int, parents, first_parent: int = 0, n: int = 10):
+        """wtp_mesh_front_candidates: the n candidates each of the given parent positions, parent p standing for queue
+        entry first_parent + p, as the front makes them: (xyz, inside, r), len(parents) * n rows."""
+        sd, keep = self._sample_spacing(spacing)
+        dt = self._mesh_dtype()
+        par = np.ascontiguousarray(parents, dtype=dt).reshape(-1, 3)
+        m = len(par) * int(n)
+        xyz, inside, r = np.empty((m, 3), dtype=dt), np.zeros(m, dtype=np.uint8), np.empty(m, dtype=dt)
+        rc = self._lib.wtp_mesh_front_candidates(self._h, C.byref(sd), C.c_uint64(int(seed)), _vp(par), len(par),
+                                                 int(first_parent), int(n), _vp(xyz), _vp(inside), _vp(r))
+        L.check(self._h, rc)
+        del keep
+        return xyz, inside.astype(bool), r
+
     def set_stream(self, stream_handle=None):
         """Run the library on a caller-owned HIP stream (handle as an int; 0 = the device's default
         stream, which is torch's current stream unless the caller switched); None = own stream."""

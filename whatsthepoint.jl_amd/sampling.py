@@ -1,6 +1,6 @@
 """Preprocessing that makes points: `sample_surface` / `PointBoundary.from_mesh` (src/surface_sampling.jl),
-`fill_volume` / `discretize` (the Bridson placement of src/discretization/algorithms/octree.jl) and `generate_shadows`
-(src/shadow.jl).
+`fill_volume` / `discretize` (the Bridson placement of src/discretization/algorithms/octree.jl), `front_volume` /
+`discretize(alg=SlakKosec())` (src/discretization/algorithms/slak_kosec.jl) and `generate_shadows` (src/shadow.jl).
 
 `sample_surface` is graded Poisson-disk dart throwing on the continuous mesh surface.  The reference draws
 its darts from `rand`; here they come from the library's counter-based stream (include/wtp.h,
@@ -9,7 +9,11 @@ wtp_mesh_sample), and the result is the serial loop over that stream, decided in
 triangles' normals and divides the area shares.
 
 `fill_volume` is the same run over darts uniform in the mesh's bounding box, of which those inside the mesh may be
-taken, with the boundary points as seeds that occupy space from the start (include/wtp.h, wtp_mesh_fill)."""
+taken, with the boundary points as seeds that occupy space from the start (include/wtp.h, wtp_mesh_fill).
+
+`front_volume` is the advancing front of Slak & Kosec: the boundary points head a queue, every queue entry throws n
+candidates at its own spacing, and a candidate inside the mesh that keeps that spacing from every entry joins the queue
+(include/wtp.h, wtp_mesh_front)."""
 from __future__ import annotations
 
 import warnings
@@ -122,21 +126,81 @@ def fill_volume(mesh, spacing, *, seeds=None, factor: float = 0.75, max_points: 
     return vol
 
 
-def discretize(boundary, spacing, mesh, *, factor: float = 0.75, max_points: int = 10_000_000, stall_limit: int = 2000,
-               seed: int = synth.SEED, ctx=None):
-    """discretize(bnd, spacing; alg = Orthtree(mesh; spacing, placement = :bridson), max_points) -> PointCloud(boundary,
-    volume): the boundary's points are the seeds of fill_volume; the boundary itself is returned unchanged."""
+class SlakKosec:
+    """SlakKosec(n = 10) (src/discretization/algorithms/slak_kosec.jl:59-67): the advancing front with n candidates per
+    expanded point, for discretize(..., alg=SlakKosec(n)).  The mesh is discretize's own argument."""
+
+    def __init__(self, n: int = 10):
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= 64:
+            raise WtpArgumentError("SlakKosec takes 1 to 64 candidates per point")
+        self.n = int(n)
+
+    def __repr__(self):
+        return f"SlakKosec(n={self.n})"
+
+
+def front_volume(mesh, spacing, *, seeds, n: int = 10, max_points: int = 10_000_000, seed: int = synth.SEED,
+                 batch: int = 0, ctx=None):
+    """Advancing-front points inside a closed triangle mesh -> PointVolume: the placement of
+    discretize(bnd, spacing; alg = SlakKosec(octree)) (src/discretization/algorithms/slak_kosec.jl:72-123).
+
+    mesh as for fill_volume.  seeds ((m, 3), the boundary points) head the queue and are not returned; every queue entry
+    throws n candidates onto the sphere of its own spacing, and a candidate inside the mesh that is farther than that
+    spacing from every entry but its parent joins the queue.  Unlike the reference, expanded boundary points keep
+    counting (include/wtp.h).  seed and batch (parents per batch) as for sample_surface.  The returned volume carries the
+    run's wtp_front_info as `front_info`, the points' own spacing as `front_h` and their parents' queue indices as
+    `front_parent`."""
+    from .cloud import PointVolume
+
+    if not max_points > 0:
+        raise WtpArgumentError("max_points must be positive")
+    n = SlakKosec(n).n
+    law = _sampler_spacing(spacing)
+    mesh = _as_octree(mesh, ctx, True)
+    c = mesh._resident(ctx)
+    info = c.mesh_front(law, n, seeds, max_points, int(seed) & 0xFFFFFF, batch)
+    m = int(info["n_points"])
+    if m == 0:
+        raise WtpArgumentError("the advancing front produced no points — check the seeds, spacing vs domain size and "
+                               "mesh orientation")
+    if info["stop_reason"] == 2:
+        warnings.warn(f"discretization stopping early, reached max points ({max_points})")
+    got = c.mesh_front_get(m, want=("xyz", "h", "parent"))
+    vol = PointVolume(got["xyz"])
+    vol.front_info, vol.front_h, vol.front_parent = info, got["h"], got["parent"]
+    return vol
+
+
+_EXTRAS = {"fill": ("fill_info", "fill_r"), "front": ("front_info", "front_h", "front_parent")}
+
+
+def discretize(boundary, spacing, mesh, *, alg=None, factor: float = None, max_points: int = 10_000_000,
+               stall_limit: int = None, seed: int = synth.SEED, ctx=None):
+    """discretize(bnd, spacing; alg, max_points) -> PointCloud(boundary, volume); the boundary itself is returned
+    unchanged.  alg = None: Orthtree(mesh; spacing, placement = :bridson), the boundary's points being the seeds of
+    fill_volume (factor 0.75, stall_limit 2000 unless given).  alg = SlakKosec(n): the advancing front from the boundary's
+    points (front_volume), which has no factor and no stall_limit."""
     from .cloud import PointBoundary, PointCloud
 
+    if alg is not None and not isinstance(alg, SlakKosec):
+        raise WtpArgumentError(f"alg must be None or SlakKosec(n), not {type(alg).__name__}")
+    if alg is not None and (factor is not None or stall_limit is not None):
+        raise WtpArgumentError("factor and stall_limit do not apply to SlakKosec: the front tests at the spacing itself "
+                               "and ends when no point is left to expand")
     if not isinstance(boundary, PointBoundary):
         boundary = PointBoundary(boundary)
-    vol = fill_volume(mesh, spacing, seeds=boundary.points(), factor=factor, max_points=max_points,
-                      stall_limit=stall_limit, seed=seed, ctx=ctx)
+    if alg is None:
+        vol = fill_volume(mesh, spacing, seeds=boundary.points(), factor=0.75 if factor is None else factor,
+                          max_points=max_points, stall_limit=2000 if stall_limit is None else stall_limit, seed=seed,
+                          ctx=ctx)
+    else:
+        vol = front_volume(mesh, spacing, seeds=boundary.points(), n=alg.n, max_points=max_points, seed=seed, ctx=ctx)
     bp = boundary.points()
     if vol.points().dtype != bp.dtype:  # the cloud keeps the boundary's type (the mesh's decided the run)
-        info, r = vol.fill_info, vol.fill_r
+        extras = {k: getattr(vol, k) for k in _EXTRAS["fill" if alg is None else "front"]}
         vol = type(vol)(vol.points().astype(bp.dtype))
-        vol.fill_info, vol.fill_r = info, r
+        for k, v in extras.items():
+            setattr(vol, k, v)
     return PointCloud(boundary, vol)
 
 
