@@ -309,6 +309,55 @@ def test_front_fill_and_sample_void_one_another(wtp, ctx):
             assert np.array_equal(s, sample0)
 
 
+def test_runs_in_turn_on_one_context_equal_those_on_fresh_contexts(wtp, ctx):
+    """Sample, front, fill and front again share one run-begin path and one set of buffers, also across a change of the
+    mesh's dtype: each call returns the bytes and the counts of the same call on a context that has run nothing else."""
+    import surface_sampling_cases as Sc
+    import volume_fill_cases as Vc
+
+    def sample(c, dtype):
+        case = Sc.CASES["cube_f075"]
+        sp = wtp.sampling._sampler_spacing(Sc.library_spacing(wtp, "cube_f075", dtype))
+        info = c.mesh_sample(sp, case["factor"], Sc.max_points_of(case), case["stall_limit"], Sc.SEED, 0)
+        got = c.mesh_sample_get(info["n_points"])
+        return [info[k] for k in ("n_points", "n_darts", "stop_reason")], [got[k].tobytes() for k in ("xyz", "tri", "r", "dart")]
+
+    def fill(c, dtype):
+        case = Vc.CASES["cube_seeds"]
+        sp = wtp.sampling._sampler_spacing(Vc.library_spacing(wtp, "cube_seeds", dtype))
+        info = c.mesh_fill(sp, case["factor"], Vc.seeds_of("cube_seeds", dtype)[0], Vc.max_points_of(case), case["stall_limit"],
+                           Vc.SEED, 0)
+        got = c.mesh_fill_get(info["n_points"])
+        return [info[k] for k in ("n_points", "n_darts", "stop_reason")], [got[k].tobytes() for k in ("xyz", "r", "dart")]
+
+    def front(batch):
+        def run(c, dtype):
+            case = Fc.CASES["grid8"]
+            sp = wtp.sampling._sampler_spacing(Fc.library_spacing(wtp, "grid8", dtype))
+            info, got = _front(c, case, sp, Fc.seeds_of("grid8", dtype), batch=batch)
+            return [info[k] for k in ("n_points", "n_candidates", "stop_reason")], [got[k].tobytes() for k in ("xyz", "h", "cand", "parent")]
+        return run
+
+    def mesh(dtype):                                                      # the three cases stand on the same cube
+        v, t = Fc.mesh_of("grid8", dtype)
+        for other in (Sc.mesh_of("cube_f075", dtype), Vc.mesh_of("cube_seeds", dtype)):
+            assert np.array_equal(other[0], v) and np.array_equal(other[1], t)
+        return v, t
+
+    steps = [(F32, sample), (F32, front(0)), (F32, fill), (F32, front(7)), (F64, front(0)), (F64, sample)]
+    resident = None
+    for i, (dtype, run) in enumerate(steps):
+        if dtype != resident:
+            ctx.mesh_set(*mesh(dtype))
+            resident = dtype
+        counts, data = run(ctx, dtype)
+        with wtp.Context(0) as fresh:
+            fresh.mesh_set(*mesh(dtype))
+            fresh_counts, fresh_data = run(fresh, dtype)
+        assert counts[0] > 50 and counts == fresh_counts, i
+        assert data == fresh_data, i
+
+
 # ---- device read-out -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", Fc.DTYPES)
 def test_get_dev_equals_get(wtp, ctx, dtype):

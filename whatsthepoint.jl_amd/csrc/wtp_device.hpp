@@ -15,6 +15,9 @@ template <> struct Lim<double> {
     static __device__ __host__ constexpr double inf() { return __builtin_huge_val(); }
 };
 
+// a spacing or a radius one can sample with: finite and > 0 (wtp_sample.hip, wtp_sample_streams.hip)
+template <typename T> __device__ inline bool good_value(T v) { return v > (T)0 && v < Lim<T>::inf(); }
+
 __device__ inline float wsqrt(float x) { return __builtin_sqrtf(x); } // correctly rounded (IEEE), like Julia sqrt
 __device__ inline double wsqrt(double x) { return __builtin_sqrt(x); }
 __device__ inline float wfloor(float x) { return floorf(x); }

@@ -364,15 +364,15 @@ struct MeshState {
     double total_area = 0;         // cum[nt - 1]
 };
 
-// Poisson-disk surface sampling (wtp_sample.hip): the accepted samples and their cell table stay on the device between
-// wtp_mesh_sample and the wtp_mesh_sample_get* calls; the batch buffers are reused by every batch and by the dart read-out.
-// wtp_mesh_fill and wtp_mesh_front run in the same buffers (their seeds at the front of the accepted array), so one result
-// is resident at a time.
+// Poisson-disk surface sampling (wtp_sample.hip; its streams: wtp_sample_streams.hip): the accepted samples and their cell
+// table stay on the device between wtp_mesh_sample and the wtp_mesh_sample_get* calls; the batch buffers are reused by
+// every batch and by the dart read-out.  wtp_mesh_fill and wtp_mesh_front run in the same buffers (their seeds at the
+// front of the accepted array), so one result is resident at a time.
+enum class SampleKind { none, sample, fill, front };
 struct SampleState {
-    bool valid = false;            // a result of the current mesh is resident ...
-    bool fill = false;             // ... and it is wtp_mesh_fill's, behind n_seeds seed rows
-    bool front = false;            // ... or wtp_mesh_front's, likewise; `dart` then holds candidate indices
-    int front_per = 0;             // candidates per parent of that run
+    SampleKind kind = SampleKind::none; // the run whose result of the current mesh is resident; fill's and front's lie
+                                   // behind n_seeds seed rows, and front's `dart` holds candidate indices
+    int front_per = 0;             // candidates per parent of a resident front
     int64_t n_seeds = 0;
     int dtype = -1;
     int64_t n = 0, cap = 0;        // samples held, rows the arrays below have room for
@@ -384,6 +384,22 @@ struct SampleState {
     DevBuf b_in;                   // wtp_mesh_fill: the domain test's flag per dart
     int64_t b_tsz = 0;
     DevBuf ctl;                    // one SampleCtl
+};
+
+// A run's control block on the device: the kernels of a batch update it, the host reads it once per group of rounds.
+constexpr int kSampleGroup = 8;    // rounds per group
+struct SampleCtl {
+    unsigned long long bad;        // smallest dart index with a bad spacing value (~0: none)
+    unsigned long long rmin, rmax; // bits of the smallest / largest r (as double) a range pass saw
+    long long n;                   // samples accepted so far
+    long long miss;                // rejected darts in a row so far
+    long long n_darts;             // darts taken so far
+    int32_t stopped;               // 0 running, 1 the run ended, 3 a dart the run took has a bad spacing value
+    int32_t reason;
+    int32_t end;                   // batch-local index of the first dart the run does not take (INT_MAX: none)
+    int32_t n_new;                 // samples the batch appended
+    int32_t und[kSampleGroup];     // darts left undecided by each round of the group
+    unsigned long long n_inside;   // wtp_mesh_fill: darts taken so far that were inside the mesh
 };
 
 struct KdTree {
@@ -694,6 +710,25 @@ int launch_normal_graph_apply(wtp_ctx* ctx, T* d_nrm, int64_t n, int dim, const 
                               unsigned long long* d_ctl);
 // wtp_sample.hip: a new or cleared mesh voids the resident sample
 void sample_invalidate(wtp_ctx* ctx);
+// The host-level seam between wtp_sample.hip, which decides a batch from the batch buffers, and wtp_sample_streams.hip,
+// which fills them.  Of wtp_sample.hip: the batch buffers for B points; rows {x, y, z, r} into xyz and r (NULL: absent).
+constexpr int kSmThreads = 256;
+inline int sm_stride_grid(int64_t n) { return grid_for(n, kSmThreads, 8192); }
+template <typename T> int ensure_batch(wtp_ctx* ctx, int64_t B);
+template <typename T> int sample_unpack(wtp_ctx* ctx, const void* pts, int64_t n, T* d_xyz, T* d_r);
+// Of wtp_sample_streams.hip: a batch of darts or candidates, the seeds, the front's own-h pass, the streams' read-outs.
+template <typename T>
+int enqueue_darts(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, uint64_t seed, int64_t first, int64_t n, bool fill);
+template <typename T>
+int enqueue_candidates(wtp_ctx* ctx, uint64_t seed, const Pt<T>* parents, int64_t par0, int64_t first, int64_t B, int per);
+template <typename T> int fill_seeds(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, const T* seeds, int64_t ns);
+template <typename T> int front_own_h(wtp_ctx* ctx, const wtp_spacing_desc* sp, int64_t n, int64_t n_new);
+template <typename T>
+int sample_darts(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, uint64_t seed, int64_t first, int64_t n, bool fill,
+                 T* xyz_out, int32_t* tri_out, uint8_t* inside_out, T* r_out);
+template <typename T>
+int front_candidates(wtp_ctx* ctx, const wtp_spacing_desc* sp, uint64_t seed, const T* parents, int64_t np, int64_t first_parent,
+                     int per, T* xyz_out, uint8_t* inside_out, T* r_out);
 // wtp_mesh_query's inside flag for n device points of the mesh's own type (wtp_mesh.hip): the domain test of wtp_mesh_fill
 template <typename T> int launch_mesh_inside(wtp_ctx* ctx, const T* d_xyz, int64_t n, uint8_t* d_inside);
 // the mesh's inside/outside class grid with cells of about `cell` (kept if one about as fine exists), and the number of

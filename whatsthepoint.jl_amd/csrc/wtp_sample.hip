@@ -8,7 +8,8 @@
 // the serial loop over that stream is the definition of the result; this file computes it in batches of B consecutive
 // darts.  Dart throwing in a fixed order is the greedy maximal independent set under fixed priorities, and that set is
 // reached by rounds of "decide every dart whose lower-numbered conflicting darts are all decided":
-//   1. generate      one thread per dart: triangle by binary search of the area sums (double), position and r in T;
+//   1. generate      one thread per dart: triangle by binary search of the area sums (double), position and r in T
+//                    (wtp_sample_streams.hip, as are the darts and candidates of the other two streams below);
 //   2. cull          a dart in conflict with an accepted sample is dead; the live ones enter the batch's cell table;
 //   3. rounds        an undecided dart is rejected if a lower-numbered conflicting dart was accepted in an EARLIER round,
 //                    accepted if all of them were rejected earlier (Jacobi: a word per dart holds the round of its
@@ -40,6 +41,11 @@
 // candidates are known at launch and ordered as the serial loop takes them.  The conflict rule is one-sided (r_j alone)
 // and exempts the parent; the cull and the rounds are instantiated for it (kFront), the stop scan runs with a stall limit
 // it cannot reach, and the appended rows get their own h before the next batch can read them as parents.
+//
+// This file is the core: the cell table, cull, rounds, stop scan, append and insert, decide_batch over them, and the
+// driver.  A run is run_begin, then per batch batch_prepare, the stream's points (wtp_sample_streams.hip) and
+// decide_batch, then run_finish; sample_run and front_run hold what differs between the streams: how a batch is sized,
+// the rows it needs room for, who wants the class grid, the front's own-h pass and its stop reasons.
 #include <climits>
 #include <cmath>
 
@@ -47,30 +53,14 @@
 
 namespace wtp {
 
-static constexpr int kSmThreads = 256;
-static constexpr int kGroup = 8;                       // rounds per host read-back
+static constexpr int kGroup = kSampleGroup;            // rounds per host read-back
 static constexpr int kScanItems = 8;                   // darts per thread of the stop scan
 static constexpr int kTile = kSmThreads * kScanItems;  // darts per block of the stop scan
 static constexpr int64_t kBatchFirst = 4096, kBatchMax = 1 << 20; // batch = 0: doubled from / up to
-static constexpr int64_t kReadChunk = 1 << 18;         // wtp_mesh_sample_darts works in pieces of this many darts
 static constexpr unsigned long long kEmpty = ~0ull;
 
 // dart states: 0 undecided, else ((round of the decision + 1) << 1) | accepted; culled darts count as round 0
 static constexpr int32_t kCulled = 2;
-
-struct SampleCtl {
-    unsigned long long bad;        // smallest dart index with a bad spacing value (~0: none)
-    unsigned long long rmin, rmax; // bits of the smallest / largest r (as double) a range pass saw
-    long long n;                   // samples accepted so far
-    long long miss;                // rejected darts in a row so far
-    long long n_darts;             // darts taken so far
-    int32_t stopped;               // 0 running, 1 the run ended, 3 a dart the run took has a bad spacing value
-    int32_t reason;
-    int32_t end;                   // batch-local index of the first dart the run does not take (INT_MAX: none)
-    int32_t n_new;                 // samples the batch appended
-    int32_t und[kGroup];           // darts left undecided by each round of the group
-    unsigned long long n_inside;   // wtp_mesh_fill: darts taken so far that were inside the mesh
-};
 
 template <typename T> struct CellMap {
     T org[3];
@@ -88,13 +78,6 @@ struct Table {
     uint32_t mask;
     int32_t shift;
 };
-
-__device__ inline uint64_t sm_splitmix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 template <typename T> __device__ inline int cell_of(const CellMap<T>& m, T v, int a) {
     const T s = (v - m.org[a]) * m.inv_c; // monotone in v; anything outside the box piles into the edge cells
@@ -180,140 +163,6 @@ __device__ inline void for_near(const CellMap<T>& m, const Table& t, const int32
                     j = next[j];
                 }
             }
-}
-
-// ---- step 1: the darts ---------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void sample_gen_kernel(uint64_t seed, int64_t first, int64_t n, const T* __restrict__ corners,
-                                  const double* __restrict__ cum, int32_t nt, double total_area, T* __restrict__ xyz,
-                                  int32_t* __restrict__ tri) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint64_t base = (seed << 40) + 3ull * (uint64_t)(first + i);
-        const uint64_t w0 = sm_splitmix64(base), w1 = sm_splitmix64(base + 1), w2 = sm_splitmix64(base + 2);
-        const double x = ((double)(w0 >> 11) * 0x1p-53) * total_area;
-        int32_t lo = 0, hi = nt; // first index with cum >= x (searchsortedfirst), then the clamp
-        for (int it = 0; it < 32 && lo < hi; ++it) {
-            const int32_t mid = lo + ((hi - lo) >> 1);
-            if (cum[mid] < x) lo = mid + 1;
-            else hi = mid;
-        }
-        const int32_t t = lo < nt - 1 ? lo : nt - 1;
-        const T u = (T)((float)(w1 >> 40) * (1.0f / 16777216.0f));
-        const T v = (T)((float)(w2 >> 40) * (1.0f / 16777216.0f));
-        const T su = wsqrt(u);
-        const T a = (T)1 - su, b = su * ((T)1 - v), c = su * v;
-        const T* k = corners + 9 * (int64_t)t;
-        for (int d = 0; d < 3; ++d) xyz[3 * i + d] = (a * k[d] + b * k[3 + d]) + c * k[6 + d];
-        tri[i] = t;
-    }
-}
-
-// the volume fill's darts: point j of wtp_gen_uniform_dev's dim-3 stream, scaled into the box [lo, hi]
-template <typename T> struct Box3 { T lo[3], hi[3]; };
-
-template <typename T>
-__global__ void fill_gen_kernel(uint64_t seed, int64_t first, int64_t n, Box3<T> box, T* __restrict__ xyz) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint64_t base = (seed << 40) + 3ull * (uint64_t)(first + i);
-        for (int a = 0; a < 3; ++a) {
-            const T u = (T)((float)(sm_splitmix64(base + a) >> 40) * (1.0f / 16777216.0f));
-            xyz[3 * i + a] = box.lo[a] + u * (box.hi[a] - box.lo[a]);
-        }
-    }
-}
-
-template <typename T> __device__ inline bool good_value(T v) { return v > (T)0 && v < Lim<T>::inf(); }
-
-// ---- the front's candidates (include/wtp.h, wtp_mesh_front) ---------------------------------------------------------------
-constexpr double front_factorial(int n) { return n <= 1 ? 1.0 : (double)n * front_factorial(n - 1); } // exact up to 19!
-template <typename T> struct FrontPoly { T s[9], c[9], quarter_pi; };                                  // S_1..S_9, C_1..C_9
-
-template <typename T> static FrontPoly<T> front_poly() {
-    FrontPoly<T> f;
-    for (int k = 1; k <= 9; ++k) {
-        const double sign = (k & 1) ? -1.0 : 1.0;
-        f.s[k - 1] = (T)(sign / front_factorial(2 * k + 1));
-        f.c[k - 1] = (T)(sign / front_factorial(2 * k));
-    }
-    f.quarter_pi = (T)(3.141592653589793 / 4.0);
-    return f;
-}
-
-// One thread per candidate i of the batch: candidate first + i, of parent par0 + i / per (a row of `parents`, w = h_q).
-// The gather is per-fold redundant within a wave; neighbouring lanes read the same 16 or 32 bytes, which the L1 serves
-// (DESIGN.md §8f.7).  A parent whose h is not finite and > 0 is never expanded: its candidates stay at its position
-// with its h as radius, which the cull reads as dead.
-template <typename T>
-__global__ void front_gen_kernel(uint64_t seed, int64_t first, int64_t n, const Pt<T>* __restrict__ parents, int64_t par0,
-                                 int32_t per, FrontPoly<T> poly, T* __restrict__ xyz, Pt<T>* __restrict__ pts) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const Pt<T> q = parents[par0 + i / per];
-        Pt<T> p = q;
-        if (good_value(q.w)) {
-            const uint64_t base = (seed << 40) + 2ull * (uint64_t)(first + i);
-            const T u = (T)((float)(sm_splitmix64(base) >> 40) * (1.0f / 16777216.0f));
-            const T v = (T)((float)(sm_splitmix64(base + 1) >> 40) * (1.0f / 16777216.0f));
-            const T z = (T)2 * u - (T)1;
-            const T rho = wsqrt((T)1 - z * z);
-            const T t = (T)8 * v;
-            const int o = (int)t; // 0 .. 7
-            const T f = t - (T)o;
-            const T g = (o & 1) ? (T)1 - f : f;
-            const T th = g * poly.quarter_pi;
-            const T x = th * th;
-            T as = poly.s[8], ac = poly.c[8];
-            for (int k = 7; k >= 0; --k) as = poly.s[k] + x * as, ac = poly.c[k] + x * ac;
-            const T s = th * ((T)1 + x * as);
-            const T c = (T)1 + x * ac;
-            T cl, sl;
-            switch (o) {
-                case 0: cl = c, sl = s; break;
-                case 1: cl = s, sl = c; break;
-                case 2: cl = -s, sl = c; break;
-                case 3: cl = -c, sl = s; break;
-                case 4: cl = -c, sl = -s; break;
-                case 5: cl = -s, sl = -c; break;
-                case 6: cl = s, sl = -c; break;
-                default: cl = c, sl = -s; break;
-            }
-            p.x = q.x + q.w * (rho * cl);
-            p.y = q.y + q.w * (rho * sl);
-            p.z = q.z + q.w * z;
-        }
-        xyz[3 * i] = p.x, xyz[3 * i + 1] = p.y, xyz[3 * i + 2] = p.z;
-        pts[i] = p;
-    }
-}
-
-// The rows the last batch appended get their own h as w (they held their parent's, the radius they were tested with); a
-// value that is not finite and > 0 is reported by the row's candidate index.
-template <typename T>
-__global__ void front_own_h_kernel(Pt<T>* __restrict__ rows, const int64_t* __restrict__ cand, const T* __restrict__ h,
-                                   int64_t n, SampleCtl* __restrict__ ctl) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const T hv = h[i];
-        rows[i].w = hv;
-        if (!good_value(hv)) atomicMin(&ctl->bad, (unsigned long long)cand[i]);
-    }
-}
-
-// r = T(factor) h; a spacing value that is not finite and > 0 is reported by the smallest dart index (report = false: the
-// cull reports it, for the darts that may be taken)
-template <typename T>
-__global__ void sample_radius_kernel(const T* __restrict__ xyz, const T* __restrict__ h, T h_const, T factor, int64_t first,
-                                     int64_t n, Pt<T>* __restrict__ pts, bool report, SampleCtl* __restrict__ ctl) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const T hv = h ? h[i] : h_const;
-        Pt<T> p;
-        p.x = xyz[3 * i], p.y = xyz[3 * i + 1], p.z = xyz[3 * i + 2], p.w = factor * hv;
-        pts[i] = p;
-        if (report && !(good_value(hv) && good_value(p.w))) atomicMin(&ctl->bad, (unsigned long long)(first + i));
-    }
 }
 
 // smallest and largest good r of pts[0, n) into ctl (integer atomics on the bits of positive doubles)
@@ -568,9 +417,7 @@ __global__ void sample_unpack_kernel(const Pt<T>* __restrict__ pts, int64_t n, T
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 void sample_invalidate(wtp_ctx* ctx) {
-    ctx->sample.valid = false;
-    ctx->sample.fill = false;
-    ctx->sample.front = false;
+    ctx->sample.kind = SampleKind::none;
     ctx->sample.n = 0;
     ctx->sample.n_seeds = 0;
 }
@@ -595,7 +442,7 @@ static Table table_view(const DevBuf& b, int64_t tsz) {
 static int32_t scan_tiles(int64_t B) { return (int32_t)((B + 1 + kTile - 1) / kTile); }
 
 // the batch buffers, for B darts
-template <typename T> static int ensure_batch(wtp_ctx* ctx, int64_t B) {
+template <typename T> int ensure_batch(wtp_ctx* ctx, int64_t B) {
     SampleState& S = ctx->sample;
     int rc;
     if ((rc = ensure(ctx, S.ctl, sizeof(SampleCtl)))) return rc;
@@ -630,41 +477,6 @@ static int grow_keep(wtp_ctx* ctx, DevBuf& b, size_t keep, size_t bytes) {
 }
 
 static int sm_grid(int64_t n) { return grid_for(n, kSmThreads, 1 << 20); }
-static int sm_stride_grid(int64_t n) { return grid_for(n, kSmThreads, 8192); }
-
-// darts first .. first + n - 1 into the batch buffers: b_xyz, b_tri, b_pts (r = factor h); bad values into ctl->bad.
-// fill: the volume fill's darts instead, b_in (inside the mesh) in place of b_tri, and bad values left to the cull.
-template <typename T>
-static int enqueue_darts(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, uint64_t seed, int64_t first, int64_t n,
-                         bool fill) {
-    SampleState& S = ctx->sample;
-    const MeshState& M = ctx->mesh;
-    if (fill) {
-        Box3<T> box;
-        for (int a = 0; a < 3; ++a) box.lo[a] = (T)M.bbox[a], box.hi[a] = (T)M.bbox[3 + a];
-        hipLaunchKernelGGL(fill_gen_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream, seed, first, n, box,
-                           (T*)S.b_xyz.p);
-        WTP_HIP(ctx, hipGetLastError());
-        const int rc = launch_mesh_inside<T>(ctx, (const T*)S.b_xyz.p, n, (uint8_t*)S.b_in.p);
-        if (rc) return rc;
-    } else {
-        hipLaunchKernelGGL(sample_gen_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream, seed, first, n,
-                           (const T*)M.corners.p, (const double*)M.cum.p, (int32_t)M.nt, M.total_area, (T*)S.b_xyz.p,
-                           (int32_t*)S.b_tri.p);
-        WTP_HIP(ctx, hipGetLastError());
-    }
-    const bool law = spacing_on_device(sp->kind);
-    if (law) {
-        const int rc = launch_spacing_eval<T>(ctx, (const T*)S.b_xyz.p, n, 3, ctx->kd.nodes.p, ctx->kd.m, sp->kind, sp->p0,
-                                              sp->p1, sp->p2, (T*)S.b_h.p);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(sample_radius_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream,
-                       (const T*)S.b_xyz.p, law ? (const T*)S.b_h.p : (const T*)nullptr, (T)sp->constant, (T)factor, first, n,
-                       (Pt<T>*)S.b_pts.p, !fill, (SampleCtl*)S.ctl.p);
-    WTP_HIP(ctx, hipGetLastError());
-    return WTP_OK;
-}
 
 static int check_sample_args(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, uint64_t seed) {
     if (ctx->mesh.nt < 1) return fail(ctx, WTP_ERR_STATE, "no mesh: call wtp_mesh_set first");
@@ -705,37 +517,6 @@ template <typename T> static int ensure_rows(wtp_ctx* ctx, int64_t keep, int64_t
     return WTP_OK;
 }
 
-// The fill's seeds into the front of the accepted array: r = T(factor) h(seed), every one checked.
-template <typename T>
-static int fill_seeds(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, const T* seeds, int64_t ns) {
-    SampleState& S = ctx->sample;
-    for (int64_t i = 0; i < 3 * ns; ++i)
-        if (!std::isfinite(seeds[i])) return fail(ctx, WTP_ERR_ARG, "seed " + std::to_string(i / 3) + " has a coordinate that is not finite");
-    std::vector<T> h((size_t)ns, (T)sp->constant);
-    int rc;
-    if (spacing_on_device(sp->kind)) {
-        if ((rc = ensure(ctx, ctx->scratch, sizeof(T) * 4 * (size_t)ns))) return rc;
-        T* d_xyz = (T*)ctx->scratch.p;
-        T* d_h = d_xyz + 3 * ns;
-        WTP_HIP(ctx, hipMemcpyAsync(d_xyz, seeds, sizeof(T) * 3 * (size_t)ns, hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = launch_spacing_eval<T>(ctx, d_xyz, ns, 3, ctx->kd.nodes.p, ctx->kd.m, sp->kind, sp->p0, sp->p1, sp->p2, d_h)))
-            return rc;
-        WTP_HIP(ctx, hipMemcpyAsync(h.data(), d_h, sizeof(T) * (size_t)ns, hipMemcpyDeviceToHost, ctx->stream));
-        if ((rc = sync(ctx))) return rc;
-    }
-    std::vector<Pt<T>> rows((size_t)ns);
-    const T f = (T)factor;
-    for (int64_t i = 0; i < ns; ++i) {
-        Pt<T> p;
-        p.x = seeds[3 * i], p.y = seeds[3 * i + 1], p.z = seeds[3 * i + 2], p.w = f * h[i];
-        if (!(h[i] > 0 && std::isfinite(h[i]) && p.w > 0 && std::isfinite(p.w)))
-            return fail(ctx, WTP_ERR_ARG, "the spacing at seed " + std::to_string(i) + " is not finite and > 0");
-        rows[i] = p;
-    }
-    WTP_HIP(ctx, hipMemcpyAsync(S.pts.p, rows.data(), sizeof(Pt<T>) * (size_t)ns, hipMemcpyHostToDevice, ctx->stream));
-    return sync(ctx); // `rows` leaves this scope
-}
-
 // The cell map, once a first batch of B points is in b_pts: cell edge sqrt(r_min r_max) of that batch (it changes time
 // only), cells over the mesh's box; the n_acc rows the accepted array already holds (seeds) enter its table now that
 // cells exist.  One host read.
@@ -772,6 +553,16 @@ static int first_batch_map(wtp_ctx* ctx, int64_t B, int64_t n_acc, CellMap<T>* m
     return WTP_OK;
 }
 
+// what a run carries from batch to batch
+template <typename T> struct Run {
+    CellMap<T> map{};          // made by the first batch (first_batch_map)
+    bool have_map = false, classes = false;
+    double cell_edge = 0;
+    int64_t n = 0, ns = 0;     // rows of the accepted array, the ns seeds at its front included
+    int32_t n_batches = 0, rounds_max = 0;
+    int64_t syncs0 = 0;
+};
+
 // what decide_batch needs to know of a batch whose points are in b_pts
 struct BatchArgs {
     int64_t B, n_acc;          // points in the batch; rows of the accepted array (seeds included)
@@ -784,16 +575,21 @@ struct BatchArgs {
 
 // Steps 2 to 4 for one batch: cull, rounds in groups of kGroup, and behind each group the stop scan, append, count,
 // finish and insert, all guarded by the group's last undecided count; one control-block read per group, left in the
-// pinned block for the caller.  kFront: the front's one-sided rule with the parent exempt.
-template <typename T, bool kFront>
-static int decide_batch(wtp_ctx* ctx, const CellMap<T>& map, const BatchArgs& a, int32_t* rounds_out) {
+// pinned block for the caller.  The run's first batch makes the cell map first; a decided batch counts into the run.
+// kFront: the front's one-sided rule with the parent exempt.
+template <typename T, bool kFront> static int decide_batch(wtp_ctx* ctx, Run<T>& run, const BatchArgs& a) {
     SampleState& S = ctx->sample;
     SampleCtl* d_ctl = (SampleCtl*)S.ctl.p;
     SampleCtl* pin = (SampleCtl*)ctx->host_pinned;
+    int rc;
+    if (!run.have_map) {
+        if ((rc = first_batch_map<T>(ctx, a.B, run.n, &run.map, &run.cell_edge))) return rc;
+        run.have_map = true;
+    }
+    const CellMap<T>& map = run.map;
     const Table acc = table_view(S.table, S.tsz), bt = table_view(S.b_table, S.b_tsz);
     const int64_t B = a.B;
     const int32_t Bi = (int32_t)B;
-    int rc;
     WTP_HIP(ctx, hipMemsetAsync(S.b_table.p, 0xFF, 12 * (size_t)S.b_tsz, ctx->stream));
     hipLaunchKernelGGL((sample_cull_kernel<T, kFront>), dim3(sm_grid(B)), dim3(kSmThreads), 0, ctx->stream, map,
                        (const Pt<T>*)S.b_pts.p, Bi, (int32_t*)S.b_st.p, acc, (const int32_t*)S.next.p,
@@ -828,7 +624,8 @@ static int decide_batch(wtp_ctx* ctx, const CellMap<T>& map, const BatchArgs& a,
         if (pin->und[kGroup - 1] == 0) {
             int g = 0;
             while (pin->und[g] != 0) ++g;
-            *rounds_out = round0 + g + 1;
+            ++run.n_batches;
+            run.rounds_max = std::max(run.rounds_max, round0 + g + 1);
             return WTP_OK;
         }
         round0 += kGroup;
@@ -836,360 +633,236 @@ static int decide_batch(wtp_ctx* ctx, const CellMap<T>& map, const BatchArgs& a,
     }
 }
 
-
-// what a run reports: the fields of wtp_sample_info and wtp_fill_info
+// what a run reports: the fields the three public info structs share (n_darts: the front's candidates)
 struct RunInfo {
     int64_t n_points, n_darts, n_inside, batch;
     int32_t stop_reason, n_batches, rounds_max, host_syncs;
     double r_min, r_max;
 };
 
-// The run of wtp_mesh_sample (fill = false) or wtp_mesh_fill (fill = true, with ns seeds in the mesh's type).
+// Run begin, up to the control block's upload: nothing is resident any more, the law's tree, batch buffers for B darts
+// of the mesh's type, and the ns seeds (r = T(factor) h, every one checked) in front of an accepted array with room for
+// `room` more rows.
 template <typename T>
-static int sample_run(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, int64_t max_points, int64_t stall_limit,
-                      uint64_t seed, int64_t batch, bool fill, const T* seeds, int64_t ns, RunInfo* info) {
+static int run_begin(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, const T* seeds, int64_t ns, int64_t B, int64_t room,
+                     Run<T>* run) {
     SampleState& S = ctx->sample;
     const int dtype = sizeof(T) == 4 ? WTP_F32 : WTP_F64;
-    const int64_t syncs0 = ctx->n_syncs;
     int rc;
+    run->syncs0 = ctx->n_syncs;
+    run->n = run->ns = ns;
     sample_invalidate(ctx);
     if (spacing_on_device(sp->kind) && (rc = ensure_kd(ctx, sp, 3, dtype))) return rc;
     if ((rc = ensure_pinned(ctx, sizeof(SampleCtl)))) return rc;
     if (S.dtype != dtype) S.cap = 0, S.bcap = 0; // the rows have another size
-    int64_t B = batch > 0 ? batch : kBatchFirst;
     if ((rc = ensure_batch<T>(ctx, B))) return rc;
     S.dtype = dtype;
     if (ns > 0) {
         bool replaced = false;
-        if (ns + B >= (int64_t(1) << 31) - 1) return fail(ctx, WTP_ERR_ARG, "seeds + batch exceed the int32 index space");
-        if ((rc = ensure_rows<T>(ctx, 0, ns + B, &replaced))) return rc;
+        if (ns + room >= (int64_t(1) << 31) - 1) return fail(ctx, WTP_ERR_ARG, "seeds + batch exceed the int32 index space");
+        if ((rc = ensure_rows<T>(ctx, 0, ns + room, &replaced))) return rc;
         if ((rc = fill_seeds<T>(ctx, sp, factor, seeds, ns))) return rc;
     }
-    SampleCtl h{};
-    h.bad = kEmpty, h.rmin = kEmpty, h.rmax = 0, h.end = INT_MAX;
+    SampleCtl* pin = (SampleCtl*)ctx->host_pinned;
+    *pin = SampleCtl{};
+    pin->bad = kEmpty, pin->rmin = kEmpty, pin->rmax = 0, pin->end = INT_MAX;
+    WTP_HIP(ctx, hipMemcpyAsync(S.ctl.p, pin, sizeof(SampleCtl), hipMemcpyHostToDevice, ctx->stream));
+    return WTP_OK;
+}
+
+// Before a batch's points are generated (`first`: the stream index of its first point): the class grid if the run wants
+// one (want_classes) and has by now walked the mesh's tree for more points than a grid of its cell size has cells (an
+// exact test per cell; from here on the points of cells wholly inside or outside skip the walk); room for `room` more
+// rows; the accepted table emptied and refilled where it is stale or was replaced; the control block's batch fields.
+template <typename T> static int batch_prepare(wtp_ctx* ctx, Run<T>& run, int64_t first, int64_t room, bool want_classes) {
+    SampleState& S = ctx->sample;
+    int rc;
+    if (want_classes && run.have_map && !run.classes) {
+        const int64_t cells = mesh_class_cells(ctx, run.cell_edge);
+        if (cells <= first && cells <= (int64_t(1) << 26)) {
+            if ((rc = mesh_ensure_classes(ctx, run.cell_edge))) return rc;
+            run.classes = true;
+        }
+    }
+    bool rehash = false;
+    if ((rc = ensure_rows<T>(ctx, run.n, run.n + room, &rehash))) return rc;
+    if (run.n_batches == 0) {
+        S.tsz = pow2_at_least(2 * S.cap); // buffers of an earlier call, or the seeds' own: the table is stale
+        rehash = true;
+    }
+    if (rehash) WTP_HIP(ctx, hipMemsetAsync(S.table.p, 0xFF, 12 * (size_t)S.tsz, ctx->stream));
+    if (rehash && run.n > 0 && run.have_map) {
+        hipLaunchKernelGGL(sample_rehash_kernel<T>, dim3(sm_stride_grid(run.n)), dim3(kSmThreads), 0, ctx->stream, run.map,
+                           (const Pt<T>*)S.pts.p, table_view(S.table, S.tsz), (int32_t*)S.next.p, run.n);
+        WTP_HIP(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(sample_begin_kernel, dim3(1), dim3(1), 0, ctx->stream, (SampleCtl*)S.ctl.p);
+    return WTP_OK;
+}
+
+// Run finish, from the last group's control block in the pinned block: r over the rows behind the seeds (one pass, one
+// read), the result resident as `kind`, and the info fields every run reports (stop_reason as the stop scan left it).
+template <typename T> static int run_finish(wtp_ctx* ctx, const Run<T>& run, SampleKind kind, RunInfo* info) {
+    SampleState& S = ctx->sample;
     SampleCtl* d_ctl = (SampleCtl*)S.ctl.p;
     SampleCtl* pin = (SampleCtl*)ctx->host_pinned;
-    *pin = h;
-    WTP_HIP(ctx, hipMemcpyAsync(d_ctl, pin, sizeof(SampleCtl), hipMemcpyHostToDevice, ctx->stream));
-
-    CellMap<T> map{};
-    bool have_map = false, classes = false;
-    double cell_edge = 0;
-    int64_t first = 0, n = ns; // n: rows of the accepted array, the fill's seeds included
-    int32_t n_batches = 0, rounds_max = 0;
-    for (;;) {
-        if (n + B >= (int64_t(1) << 31) - 1) return fail(ctx, WTP_ERR_ARG, "samples + batch exceed the int32 index space");
-        if ((rc = ensure_batch<T>(ctx, B))) return rc;
-        // The fill has by now walked the mesh's tree for more darts than a class grid of its cell size has cells: build
-        // one (an exact test per cell), and from here on the darts of cells wholly inside or outside skip the walk.
-        if (fill && have_map && !classes) {
-            const int64_t cells = mesh_class_cells(ctx, cell_edge);
-            if (cells <= first && cells <= (int64_t(1) << 26)) {
-                if ((rc = mesh_ensure_classes(ctx, cell_edge))) return rc;
-                classes = true;
-            }
-        }
-        bool rehash = false;
-        if ((rc = ensure_rows<T>(ctx, n, n + B, &rehash))) return rc;
-        if (n_batches == 0) {
-            S.tsz = pow2_at_least(2 * S.cap); // buffers of an earlier call, or the seeds' own: the table is stale
-            rehash = true;
-        }
-        const Table acc = table_view(S.table, S.tsz);
-        if (rehash) WTP_HIP(ctx, hipMemsetAsync(S.table.p, 0xFF, 12 * (size_t)S.tsz, ctx->stream));
-        if (rehash && n > 0 && have_map) {
-            hipLaunchKernelGGL(sample_rehash_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream, map,
-                               (const Pt<T>*)S.pts.p, acc, (int32_t*)S.next.p, n);
-            WTP_HIP(ctx, hipGetLastError());
-        }
-        hipLaunchKernelGGL(sample_begin_kernel, dim3(1), dim3(1), 0, ctx->stream, d_ctl);
-        if ((rc = enqueue_darts<T>(ctx, sp, factor, seed, first, B, fill))) return rc;
-        if (!have_map) {
-            if ((rc = first_batch_map<T>(ctx, B, n, &map, &cell_edge))) return rc;
-            have_map = true;
-        }
-        int32_t rounds = 0;
-        const BatchArgs args{B, n, first, ns, max_points, stall_limit, fill ? (const uint8_t*)S.b_in.p : (const uint8_t*)nullptr,
-                             fill ? (const int32_t*)nullptr : (const int32_t*)S.b_tri.p, 0, 1};
-        if ((rc = decide_batch<T, false>(ctx, map, args, &rounds))) return rc;
-        ++n_batches;
-        rounds_max = std::max(rounds_max, rounds);
-        if (pin->stopped == 3) return fail(ctx, WTP_ERR_ARG, bad_spacing_text(pin->bad));
-        n = ns + pin->n;
-        if (pin->stopped) break;
-        first += B;
-        if (batch == 0) B = std::min(2 * B, kBatchMax);
-    }
-    // r over the samples
-    h = *pin;
+    const SampleCtl h = *pin;
+    const int64_t n_new = run.n - run.ns;
+    int rc;
     pin->rmin = kEmpty, pin->rmax = 0;
     WTP_HIP(ctx, hipMemcpyAsync(d_ctl, pin, sizeof(SampleCtl), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(sample_range_kernel<T>, dim3(sm_stride_grid(n - ns)), dim3(kSmThreads), 0, ctx->stream,
-                       (const Pt<T>*)S.pts.p + ns, n - ns, d_ctl);
+    hipLaunchKernelGGL(sample_range_kernel<T>, dim3(sm_stride_grid(n_new)), dim3(kSmThreads), 0, ctx->stream,
+                       (const Pt<T>*)S.pts.p + run.ns, n_new, d_ctl);
     WTP_HIP(ctx, hipGetLastError());
     WTP_HIP(ctx, hipMemcpyAsync(pin, d_ctl, sizeof(SampleCtl), hipMemcpyDeviceToHost, ctx->stream));
     if ((rc = sync(ctx))) return rc;
-    S.n = n - ns;
-    S.n_seeds = ns;
-    S.fill = fill;
-    S.valid = true;
-    info->n_points = n - ns;
+    S.n = n_new;
+    S.n_seeds = run.ns;
+    S.kind = kind;
+    info->n_points = n_new;
     info->n_darts = h.n_darts;
     info->n_inside = (int64_t)h.n_inside;
-    info->batch = B;
     info->stop_reason = h.reason;
-    info->n_batches = n_batches;
-    info->rounds_max = rounds_max;
-    info->host_syncs = (int32_t)(ctx->n_syncs - syncs0);
+    info->n_batches = run.n_batches;
+    info->rounds_max = run.rounds_max;
+    info->host_syncs = (int32_t)(ctx->n_syncs - run.syncs0);
     info->r_min = pin->rmin != kEmpty ? __builtin_bit_cast(double, pin->rmin) : 0.0;
     info->r_max = __builtin_bit_cast(double, pin->rmax);
     return WTP_OK;
 }
 
+// The run of wtp_mesh_sample (fill = false) or wtp_mesh_fill (fill = true, with ns seeds in the mesh's type): batches of
+// consecutive darts, doubled from kBatchFirst to kBatchMax unless `batch` fixes their size.
 template <typename T>
-static int sample_unpack(wtp_ctx* ctx, const void* pts, int64_t n, T* d_xyz, T* d_r) {
+static int sample_run(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, int64_t max_points, int64_t stall_limit,
+                      uint64_t seed, int64_t batch, bool fill, const T* seeds, int64_t ns, RunInfo* info) {
+    SampleState& S = ctx->sample;
+    Run<T> run;
+    int64_t B = batch > 0 ? batch : kBatchFirst, first = 0;
+    int rc;
+    if ((rc = run_begin<T>(ctx, sp, factor, seeds, ns, B, B, &run))) return rc;
+    const SampleCtl* pin = (const SampleCtl*)ctx->host_pinned; // decide_batch leaves the last group's control block there
+    for (;;) {
+        if (run.n + B >= (int64_t(1) << 31) - 1) return fail(ctx, WTP_ERR_ARG, "samples + batch exceed the int32 index space");
+        if ((rc = ensure_batch<T>(ctx, B))) return rc;
+        if ((rc = batch_prepare<T>(ctx, run, first, B, fill))) return rc; // only the fill tests darts against the mesh
+        if ((rc = enqueue_darts<T>(ctx, sp, factor, seed, first, B, fill))) return rc;
+        const BatchArgs args{B, run.n, first, ns, max_points, stall_limit, fill ? (const uint8_t*)S.b_in.p : (const uint8_t*)nullptr,
+                             fill ? (const int32_t*)nullptr : (const int32_t*)S.b_tri.p, 0, 1};
+        if ((rc = decide_batch<T, false>(ctx, run, args))) return rc;
+        if (pin->stopped == 3) return fail(ctx, WTP_ERR_ARG, bad_spacing_text(pin->bad));
+        run.n = ns + pin->n;
+        if (pin->stopped) break;
+        first += B;
+        if (batch == 0) B = std::min(2 * B, kBatchMax);
+    }
+    info->batch = B;
+    return run_finish<T>(ctx, run, fill ? SampleKind::fill : SampleKind::sample, info);
+}
+
+// The run of wtp_mesh_front: parents in queue order, batches of whole parents that were in the queue when the batch began.
+template <typename T>
+static int front_run(wtp_ctx* ctx, const wtp_spacing_desc* sp, int per, const T* seeds, int64_t ns, int64_t max_points,
+                     uint64_t seed, int64_t batch, RunInfo* info) {
+    SampleState& S = ctx->sample;
+    const int dtype = sizeof(T) == 4 ? WTP_F32 : WTP_F64;
+    const bool law = spacing_on_device(sp->kind);
+    const auto bad_h = [&](unsigned long long cand) {
+        return fail(ctx, WTP_ERR_ARG, "the spacing at the point accepted from candidate " + std::to_string(cand) + " is not finite and > 0");
+    };
+    int rc;
+    *info = RunInfo{};
+    info->stop_reason = 1;
+    if (ns == 0) { // nothing to expand: the front has died out before it began
+        sample_invalidate(ctx);
+        S.dtype = S.dtype < 0 ? dtype : S.dtype;
+        S.kind = SampleKind::front, S.front_per = per;
+        return WTP_OK;
+    }
+    // parents per batch: at most kBatchMax candidates, whatever `batch` asks for (the kernels run one thread per candidate
+    // of a grid of at most 2^20 blocks, and the batch changes time only)
+    const int64_t par_cap = std::max<int64_t>(kBatchMax / per, 1);
+    const int64_t par_max = batch > 0 ? std::min(batch, par_cap) : par_cap;
+    int64_t B = std::min(ns, par_max) * per;
+    Run<T> run;
+    if ((rc = run_begin<T>(ctx, sp, 1.0, seeds, ns, pow2_at_least(std::max(B, kBatchFirst)), std::min(B, max_points), &run)))
+        return rc; // (factor 1: a seed's w = T(1) h = h)
+    SampleCtl* pin = (SampleCtl*)ctx->host_pinned; // decide_batch leaves the last group's control block there
+    int64_t q0 = 0; // parents expanded so far; run.n is the queue's length
+    for (;;) {
+        const int64_t q1 = std::min(run.n, q0 + par_max), first = q0 * per;
+        B = (q1 - q0) * per;
+        const int64_t room = std::min(B, max_points - (run.n - ns)); // rows the batch can append
+        const int64_t bwant = pow2_at_least(std::max(B, kBatchFirst));
+        if (bwant > S.bcap && (rc = sync(ctx))) return rc; // the last batch's law pass still reads the batch buffers
+        if ((rc = ensure_batch<T>(ctx, bwant))) return rc;
+        if ((rc = batch_prepare<T>(ctx, run, first, room, true))) return rc;
+        if ((rc = enqueue_candidates<T>(ctx, seed, (const Pt<T>*)S.pts.p, q0, first, B, per))) return rc;
+        // a stall limit no miss run can reach: only max_points ends the scan
+        const BatchArgs args{B, run.n, first, ns, max_points, (int64_t)LLONG_MAX, (const uint8_t*)S.b_in.p, (const int32_t*)nullptr,
+                             (int32_t)q0, (int32_t)per};
+        if ((rc = decide_batch<T, true>(ctx, run, args))) return rc;
+        // an accepted point of an earlier batch whose own h is bad (the rows of this batch are evaluated below)
+        if (pin->bad != kEmpty) return bad_h(pin->bad);
+        const int64_t n_new = pin->n_new;
+        if (n_new > room) return fail(ctx, WTP_ERR_INTERNAL, "a batch appended more rows than it had room for");
+        if (law && n_new > 0 && (rc = front_own_h<T>(ctx, sp, run.n, n_new))) return rc;
+        run.n += n_new;
+        q0 = q1;
+        if (pin->stopped) break;  // max_points
+        if (q0 == run.n) break;   // nothing was appended and every entry has been expanded: the front has died out
+    }
+    WTP_HIP(ctx, hipMemcpyAsync(pin, S.ctl.p, sizeof(SampleCtl), hipMemcpyDeviceToHost, ctx->stream)); // the last rows' bad values
+    if ((rc = sync(ctx))) return rc;
+    if (pin->bad != kEmpty) return bad_h(pin->bad);
+    if ((rc = run_finish<T>(ctx, run, SampleKind::front, info))) return rc;
+    S.front_per = per;
+    info->batch = B / per;
+    info->stop_reason = info->stop_reason ? 2 : 1; // max_points ended the scan, or the front has died out
+    return WTP_OK;
+}
+
+template <typename T> int sample_unpack(wtp_ctx* ctx, const void* pts, int64_t n, T* d_xyz, T* d_r) {
     hipLaunchKernelGGL(sample_unpack_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream, (const Pt<T>*)pts, n,
                        d_xyz, d_r);
     WTP_HIP(ctx, hipGetLastError());
     return WTP_OK;
 }
 
-template <typename T>
-static int sample_darts(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, uint64_t seed, int64_t first, int64_t n,
-                        bool fill, T* xyz_out, int32_t* tri_out, uint8_t* inside_out, T* r_out) {
-    SampleState& S = ctx->sample;
-    const int dtype = sizeof(T) == 4 ? WTP_F32 : WTP_F64;
-    int rc;
-    if (spacing_on_device(sp->kind) && (rc = ensure_kd(ctx, sp, 3, dtype))) return rc;
-    if (S.dtype != dtype) S.cap = 0, S.bcap = 0, S.dtype = dtype; // (a sample of another dtype died with its mesh)
-    const int64_t chunk = std::min(n, kReadChunk);
-    if ((rc = ensure_batch<T>(ctx, std::max(chunk, S.bcap)))) return rc;
-    for (int64_t done = 0; done < n; done += chunk) {
-        const int64_t m = std::min(chunk, n - done);
-        if ((rc = enqueue_darts<T>(ctx, sp, factor, seed, first + done, m, fill))) return rc;
-        if (xyz_out)
-            WTP_HIP(ctx, hipMemcpyAsync(xyz_out + 3 * done, S.b_xyz.p, sizeof(T) * 3 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-        if (tri_out) WTP_HIP(ctx, hipMemcpyAsync(tri_out + done, S.b_tri.p, 4 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-        if (inside_out) WTP_HIP(ctx, hipMemcpyAsync(inside_out + done, S.b_in.p, (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-        if (r_out) {
-            if ((rc = sample_unpack<T>(ctx, S.b_pts.p, m, nullptr, (T*)S.b_h.p))) return rc;
-            WTP_HIP(ctx, hipMemcpyAsync(r_out + done, S.b_h.p, sizeof(T) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if ((rc = sync(ctx))) return rc;
-    }
-    return WTP_OK;
-}
-
-// ---- the advancing front ---------------------------------------------------------------------------------------------------
-struct FrontInfo {
-    int64_t n_points, n_parents, n_candidates, n_inside, batch;
-    int32_t stop_reason, n_batches, rounds_max, host_syncs;
-    double r_min, r_max;
-};
-
-// Candidates of the parents [par0, par0 + np) of `parents` (rows with w = h) into b_xyz, b_pts (w = r_j = h_q) and b_in.
-template <typename T>
-static int enqueue_candidates(wtp_ctx* ctx, uint64_t seed, const Pt<T>* parents, int64_t par0, int64_t first, int64_t B, int per) {
-    SampleState& S = ctx->sample;
-    hipLaunchKernelGGL(front_gen_kernel<T>, dim3(sm_stride_grid(B)), dim3(kSmThreads), 0, ctx->stream, seed, first, B, parents,
-                       par0, (int32_t)per, front_poly<T>(), (T*)S.b_xyz.p, (Pt<T>*)S.b_pts.p);
-    WTP_HIP(ctx, hipGetLastError());
-    return launch_mesh_inside<T>(ctx, (const T*)S.b_xyz.p, B, (uint8_t*)S.b_in.p);
-}
-
-// The run of wtp_mesh_front: parents in queue order, batches of whole parents that were in the queue when the batch began.
-template <typename T>
-static int front_run(wtp_ctx* ctx, const wtp_spacing_desc* sp, int per, const T* seeds, int64_t ns, int64_t max_points,
-                     uint64_t seed, int64_t batch, FrontInfo* info) {
-    SampleState& S = ctx->sample;
-    const int dtype = sizeof(T) == 4 ? WTP_F32 : WTP_F64;
-    const int64_t syncs0 = ctx->n_syncs;
-    const bool law = spacing_on_device(sp->kind);
-    int rc;
-    sample_invalidate(ctx);
-    *info = FrontInfo{};
-    info->stop_reason = 1;
-    if (ns == 0) { // nothing to expand: the front has died out before it began
-        S.dtype = S.dtype < 0 ? dtype : S.dtype;
-        S.front = true, S.front_per = per, S.valid = true;
-        return WTP_OK;
-    }
-    if (law && (rc = ensure_kd(ctx, sp, 3, dtype))) return rc;
-    if ((rc = ensure_pinned(ctx, sizeof(SampleCtl)))) return rc;
-    if (S.dtype != dtype) S.cap = 0, S.bcap = 0; // the rows have another size
-    // parents per batch: at most kBatchMax candidates, whatever `batch` asks for (the kernels run one thread per candidate
-    // of a grid of at most 2^20 blocks, and the batch changes time only)
-    const int64_t par_cap = std::max<int64_t>(kBatchMax / per, 1);
-    const int64_t par_max = batch > 0 ? std::min(batch, par_cap) : par_cap;
-    int64_t B = std::min(ns, par_max) * per;
-    if ((rc = ensure_batch<T>(ctx, pow2_at_least(std::max(B, kBatchFirst))))) return rc;
-    S.dtype = dtype;
-    {
-        bool replaced = false;
-        if ((rc = ensure_rows<T>(ctx, 0, ns + std::min(B, max_points), &replaced))) return rc;
-        if ((rc = fill_seeds<T>(ctx, sp, 1.0, seeds, ns))) return rc; // w = T(1) h = h, every one checked
-    }
-    SampleCtl h{};
-    h.bad = kEmpty, h.rmin = kEmpty, h.rmax = 0, h.end = INT_MAX;
-    SampleCtl* d_ctl = (SampleCtl*)S.ctl.p;
-    SampleCtl* pin = (SampleCtl*)ctx->host_pinned;
-    *pin = h;
-    WTP_HIP(ctx, hipMemcpyAsync(d_ctl, pin, sizeof(SampleCtl), hipMemcpyHostToDevice, ctx->stream));
-
-    CellMap<T> map{};
-    bool have_map = false, classes = false;
-    double cell_edge = 0;
-    int64_t q0 = 0, n = ns; // parents expanded so far; queue length (rows of the accepted array, seeds included)
-    int32_t n_batches = 0, rounds_max = 0;
-    for (;;) {
-        const int64_t q1 = std::min(n, q0 + par_max), first = q0 * per;
-        B = (q1 - q0) * per;
-        const int64_t room = std::min(B, max_points - (n - ns)); // rows the batch can append
-        const int64_t bwant = pow2_at_least(std::max(B, kBatchFirst));
-        if (bwant > S.bcap && (rc = sync(ctx))) return rc; // the last batch's law pass still reads the batch buffers
-        if ((rc = ensure_batch<T>(ctx, bwant))) return rc;
-        if (have_map && !classes) { // as the fill: once more candidates were tested than a class grid has cells
-            const int64_t cells = mesh_class_cells(ctx, cell_edge);
-            if (cells <= first && cells <= (int64_t(1) << 26)) {
-                if ((rc = mesh_ensure_classes(ctx, cell_edge))) return rc;
-                classes = true;
-            }
-        }
-        bool rehash = false;
-        if ((rc = ensure_rows<T>(ctx, n, n + room, &rehash))) return rc;
-        if (n_batches == 0) {
-            S.tsz = pow2_at_least(2 * S.cap); // buffers of an earlier call, or the seeds' own: the table is stale
-            rehash = true;
-        }
-        const Table acc = table_view(S.table, S.tsz);
-        if (rehash) WTP_HIP(ctx, hipMemsetAsync(S.table.p, 0xFF, 12 * (size_t)S.tsz, ctx->stream));
-        if (rehash && have_map) {
-            hipLaunchKernelGGL(sample_rehash_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream, map,
-                               (const Pt<T>*)S.pts.p, acc, (int32_t*)S.next.p, n);
-            WTP_HIP(ctx, hipGetLastError());
-        }
-        hipLaunchKernelGGL(sample_begin_kernel, dim3(1), dim3(1), 0, ctx->stream, d_ctl);
-        if ((rc = enqueue_candidates<T>(ctx, seed, (const Pt<T>*)S.pts.p, q0, first, B, per))) return rc;
-        if (!have_map) {
-            if ((rc = first_batch_map<T>(ctx, B, n, &map, &cell_edge))) return rc;
-            have_map = true;
-        }
-        int32_t rounds = 0;
-        // a stall limit no miss run can reach: only max_points ends the scan
-        const BatchArgs args{B, n, first, ns, max_points, (int64_t)LLONG_MAX, (const uint8_t*)S.b_in.p, (const int32_t*)nullptr,
-                             (int32_t)q0, (int32_t)per};
-        if ((rc = decide_batch<T, true>(ctx, map, args, &rounds))) return rc;
-        ++n_batches;
-        rounds_max = std::max(rounds_max, rounds);
-        // an accepted point of an earlier batch whose own h is bad (the rows of this batch are evaluated below)
-        if (pin->bad != kEmpty) return fail(ctx, WTP_ERR_ARG, "the spacing at the point accepted from candidate " + std::to_string(pin->bad) + " is not finite and > 0");
-        const int64_t n_new = pin->n_new;
-        if (n_new > room) return fail(ctx, WTP_ERR_INTERNAL, "a batch appended more rows than it had room for");
-        if (law && n_new > 0) { // step 7: the new rows' own h, before they can be parents
-            Pt<T>* rows = (Pt<T>*)S.pts.p + n;
-            if ((rc = sample_unpack<T>(ctx, rows, n_new, (T*)S.b_xyz.p, nullptr))) return rc;
-            if ((rc = launch_spacing_eval<T>(ctx, (const T*)S.b_xyz.p, n_new, 3, ctx->kd.nodes.p, ctx->kd.m, sp->kind, sp->p0,
-                                             sp->p1, sp->p2, (T*)S.b_h.p)))
-                return rc;
-            hipLaunchKernelGGL(front_own_h_kernel<T>, dim3(sm_stride_grid(n_new)), dim3(kSmThreads), 0, ctx->stream, rows,
-                               (const int64_t*)S.dart.p + n, (const T*)S.b_h.p, n_new, d_ctl);
-            WTP_HIP(ctx, hipGetLastError());
-        }
-        n += n_new;
-        q0 = q1;
-        if (pin->stopped) break;  // max_points
-        if (q0 == n) break;       // nothing was appended and every entry has been expanded: the front has died out
-    }
-    // h over the accepted points
-    h = *pin;
-    WTP_HIP(ctx, hipMemcpyAsync(pin, d_ctl, sizeof(SampleCtl), hipMemcpyDeviceToHost, ctx->stream)); // the last rows' bad values
-    if ((rc = sync(ctx))) return rc;
-    if (pin->bad != kEmpty) return fail(ctx, WTP_ERR_ARG, "the spacing at the point accepted from candidate " + std::to_string(pin->bad) + " is not finite and > 0");
-    pin->rmin = kEmpty, pin->rmax = 0;
-    WTP_HIP(ctx, hipMemcpyAsync(d_ctl, pin, sizeof(SampleCtl), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(sample_range_kernel<T>, dim3(sm_stride_grid(n - ns)), dim3(kSmThreads), 0, ctx->stream,
-                       (const Pt<T>*)S.pts.p + ns, n - ns, d_ctl);
-    WTP_HIP(ctx, hipGetLastError());
-    WTP_HIP(ctx, hipMemcpyAsync(pin, d_ctl, sizeof(SampleCtl), hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = sync(ctx))) return rc;
-    S.n = n - ns;
-    S.n_seeds = ns;
-    S.front = true, S.front_per = per;
-    S.valid = true;
-    info->n_points = n - ns;
-    info->n_candidates = h.n_darts;
-    info->n_parents = (h.n_darts + per - 1) / per;
-    info->n_inside = (int64_t)h.n_inside;
-    info->batch = B / per;
-    info->stop_reason = h.stopped ? 2 : 1;
-    info->n_batches = n_batches;
-    info->rounds_max = rounds_max;
-    info->host_syncs = (int32_t)(ctx->n_syncs - syncs0);
-    info->r_min = pin->rmin != kEmpty ? __builtin_bit_cast(double, pin->rmin) : 0.0;
-    info->r_max = __builtin_bit_cast(double, pin->rmax);
-    return WTP_OK;
-}
-
-// wtp_mesh_front_candidates: the candidates of np parent positions (host), parent p being queue entry first_parent + p
-template <typename T>
-static int front_candidates(wtp_ctx* ctx, const wtp_spacing_desc* sp, uint64_t seed, const T* parents, int64_t np,
-                            int64_t first_parent, int per, T* xyz_out, uint8_t* inside_out, T* r_out) {
-    SampleState& S = ctx->sample;
-    const int dtype = sizeof(T) == 4 ? WTP_F32 : WTP_F64;
-    const bool law = spacing_on_device(sp->kind);
-    int rc;
-    if (law && (rc = ensure_kd(ctx, sp, 3, dtype))) return rc;
-    if (S.dtype != dtype) S.cap = 0, S.bcap = 0, S.dtype = dtype; // (a result of another dtype died with its mesh)
-    const int64_t chunk = std::min(np, std::max<int64_t>(kReadChunk / per, 1)); // parents per piece
-    if ((rc = ensure_batch<T>(ctx, std::max(chunk * per, S.bcap)))) return rc;
-    DevBuf par; // per piece: xyz (3 T), h (T), rows (Pt)
-    if ((rc = ensure(ctx, par, (sizeof(T) * 4 + sizeof(Pt<T>)) * (size_t)chunk))) return rc;
-    T* d_xyz = (T*)par.p;
-    T* d_h = d_xyz + 3 * chunk;
-    Pt<T>* d_rows = (Pt<T>*)(d_h + chunk);
-    for (int64_t done = 0; done < np; done += chunk) {
-        const int64_t m = std::min(chunk, np - done), B = m * per;
-        WTP_HIP(ctx, hipMemcpyAsync(d_xyz, parents + 3 * done, sizeof(T) * 3 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-        if (law && (rc = launch_spacing_eval<T>(ctx, d_xyz, m, 3, ctx->kd.nodes.p, ctx->kd.m, sp->kind, sp->p0, sp->p1, sp->p2, d_h)))
-            return rc;
-        hipLaunchKernelGGL(sample_radius_kernel<T>, dim3(sm_stride_grid(m)), dim3(kSmThreads), 0, ctx->stream, (const T*)d_xyz,
-                           law ? (const T*)d_h : (const T*)nullptr, (T)sp->constant, (T)1, (int64_t)0, m, d_rows, false,
-                           (SampleCtl*)nullptr);
-        WTP_HIP(ctx, hipGetLastError());
-        if ((rc = enqueue_candidates<T>(ctx, seed, d_rows, 0, (first_parent + done) * per, B, per))) return rc;
-        const int64_t o = done * per;
-        if (xyz_out)
-            WTP_HIP(ctx, hipMemcpyAsync(xyz_out + 3 * o, S.b_xyz.p, sizeof(T) * 3 * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
-        if (inside_out) WTP_HIP(ctx, hipMemcpyAsync(inside_out + o, S.b_in.p, (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
-        if (r_out) {
-            if ((rc = sample_unpack<T>(ctx, S.b_pts.p, B, nullptr, (T*)S.b_h.p))) return rc;
-            WTP_HIP(ctx, hipMemcpyAsync(r_out + o, S.b_h.p, sizeof(T) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if ((rc = sync(ctx))) return rc; // `par` is freed only after the last piece has been read
-    }
-    return WTP_OK;
-}
+#define INST(T)                                            \
+    template int ensure_batch<T>(wtp_ctx*, int64_t);       \
+    template int sample_unpack<T>(wtp_ctx*, const void*, int64_t, T*, T*);
+INST(float)
+INST(double)
+#undef INST
 
 } // namespace wtp
 
 using namespace wtp;
 #define WTP_API extern "C"
 
+// max_points, batch and the seeds (wtp_mesh_sample takes none)
+static int check_size_args(wtp_ctx* ctx, int64_t max_points, int64_t batch, const void* seeds, int64_t n_seeds) {
+    if (max_points < 1) return fail(ctx, WTP_ERR_ARG, "max_points must be positive");
+    if (batch < 0 || batch > (int64_t(1) << 24)) return fail(ctx, WTP_ERR_ARG, "batch must be in [0, 2^24]");
+    if (n_seeds < 0) return fail(ctx, WTP_ERR_ARG, "n_seeds must not be negative");
+    if (n_seeds > 0 && !seeds) return fail(ctx, WTP_ERR_ARG, "seeds is NULL");
+    return WTP_OK;
+}
+
 // the argument rows wtp_mesh_sample and wtp_mesh_fill share
 static int check_run_args(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, int64_t max_points, int64_t stall_limit,
-                          uint64_t seed, int64_t batch) {
+                          uint64_t seed, int64_t batch, const void* seeds, int64_t n_seeds) {
     const int rc = check_sample_args(ctx, spacing, factor, seed);
     if (rc) return rc;
     if (stall_limit < 1) return fail(ctx, WTP_ERR_ARG, "stall_limit must be positive");
-    if (max_points < 1) return fail(ctx, WTP_ERR_ARG, "max_points must be positive");
-    if (batch < 0 || batch > (int64_t(1) << 24)) return fail(ctx, WTP_ERR_ARG, "batch must be in [0, 2^24]");
-    return WTP_OK;
+    return check_size_args(ctx, max_points, batch, seeds, n_seeds);
 }
 
 WTP_API int wtp_mesh_sample(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, int64_t max_points,
                             int64_t stall_limit, uint64_t seed, int64_t batch, wtp_sample_info* info) {
     if (!ctx) return WTP_ERR_ARG;
-    int rc = check_run_args(ctx, spacing, factor, max_points, stall_limit, seed, batch);
+    int rc = check_run_args(ctx, spacing, factor, max_points, stall_limit, seed, batch, nullptr, 0);
     if (rc) return rc;
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     RunInfo ri{};
@@ -1205,53 +878,51 @@ WTP_API int wtp_mesh_sample(wtp_ctx* ctx, const wtp_spacing_desc* spacing, doubl
     return WTP_OK;
 }
 
-// xyz and r of the resident rows [first, first + n) into host arrays, through the context's scratch block
-static int rows_to_host(wtp_ctx* ctx, int64_t first, void* xyz_out, void* r_out) {
-    SampleState& S = ctx->sample;
-    const size_t ts = tsize(S.dtype), n = (size_t)S.n;
-    int rc;
-    if ((rc = ensure(ctx, ctx->scratch, ts * 4 * n))) return rc;
-    char* d = (char*)ctx->scratch.p;
-    rc = by_dtype(S.dtype, [&](auto t) {
-        using T = decltype(t);
-        return sample_unpack<T>(ctx, (const Pt<T>*)S.pts.p + first, S.n, (T*)d, (T*)(d + ts * 3 * n));
-    });
-    if (rc) return rc;
-    if (xyz_out) WTP_HIP(ctx, hipMemcpyAsync(xyz_out, d, ts * 3 * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (r_out) WTP_HIP(ctx, hipMemcpyAsync(r_out, d + ts * 3 * n, ts * n, hipMemcpyDeviceToHost, ctx->stream));
+// is a result of kind k resident?  `missing`: what to say if not
+static int check_resident(wtp_ctx* ctx, SampleKind k, const char* missing) {
+    if (!ctx) return WTP_ERR_ARG;
+    if (ctx->sample.kind != k) return fail(ctx, WTP_ERR_STATE, missing);
     return WTP_OK;
 }
 
-WTP_API int wtp_mesh_sample_get(wtp_ctx* ctx, void* xyz_out, int32_t* tri_out, void* r_out, int64_t* dart_out) {
-    if (!ctx) return WTP_ERR_ARG;
+// xyz and r of the resident rows behind the seeds, into host arrays (through the context's scratch block) or, dev, into
+// device arrays; either may be absent
+static int rows_out(wtp_ctx* ctx, bool dev, void* xyz_out, void* r_out) {
     SampleState& S = ctx->sample;
-    if (!S.valid || S.fill || S.front) return fail(ctx, WTP_ERR_STATE, "no sample: call wtp_mesh_sample first");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n = (size_t)S.n;
+    if (!xyz_out && !r_out) return WTP_OK;
+    const size_t ts = tsize(S.dtype), n = (size_t)S.n;
     int rc;
-    if ((xyz_out || r_out) && (rc = rows_to_host(ctx, 0, xyz_out, r_out))) return rc;
-    if (tri_out) WTP_HIP(ctx, hipMemcpyAsync(tri_out, S.tri.p, 4 * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (dart_out) WTP_HIP(ctx, hipMemcpyAsync(dart_out, S.dart.p, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (!dev && (rc = ensure(ctx, ctx->scratch, ts * 4 * n))) return rc;
+    char* d_xyz = dev ? (char*)xyz_out : (char*)ctx->scratch.p;
+    char* d_r = dev ? (char*)r_out : d_xyz + ts * 3 * n;
+    rc = by_dtype(S.dtype, [&](auto t) {
+        using T = decltype(t);
+        return sample_unpack<T>(ctx, (const Pt<T>*)S.pts.p + S.n_seeds, S.n, (T*)d_xyz, (T*)d_r);
+    });
+    if (rc || dev) return rc;
+    if (xyz_out) WTP_HIP(ctx, hipMemcpyAsync(xyz_out, d_xyz, ts * 3 * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (r_out) WTP_HIP(ctx, hipMemcpyAsync(r_out, d_r, ts * n, hipMemcpyDeviceToHost, ctx->stream));
+    return WTP_OK;
+}
+
+static const char kNoSample[] = "no sample: call wtp_mesh_sample first";
+static const char kNoFill[] = "no fill: call wtp_mesh_fill first";
+static const char kNoFront[] = "no front: call wtp_mesh_front first";
+
+WTP_API int wtp_mesh_sample_get(wtp_ctx* ctx, void* xyz_out, int32_t* tri_out, void* r_out, int64_t* dart_out) {
+    int rc = check_resident(ctx, SampleKind::sample, kNoSample);
+    if (rc || (rc = rows_out(ctx, false, xyz_out, r_out))) return rc;
+    const SampleState& S = ctx->sample;
+    if (tri_out) WTP_HIP(ctx, hipMemcpyAsync(tri_out, S.tri.p, 4 * (size_t)S.n, hipMemcpyDeviceToHost, ctx->stream));
+    if (dart_out) WTP_HIP(ctx, hipMemcpyAsync(dart_out, S.dart.p, 8 * (size_t)S.n, hipMemcpyDeviceToHost, ctx->stream));
     return sync(ctx);
 }
 
-// xyz and r of the resident rows from `first` on into device arrays
-static int rows_to_dev(wtp_ctx* ctx, int64_t first, void* d_xyz_out, void* d_r_out) {
-    SampleState& S = ctx->sample;
-    if (!d_xyz_out && !d_r_out) return WTP_OK;
-    return by_dtype(S.dtype, [&](auto t) {
-        using T = decltype(t);
-        return sample_unpack<T>(ctx, (const Pt<T>*)S.pts.p + first, S.n, (T*)d_xyz_out, (T*)d_r_out);
-    });
-}
-
 WTP_API int wtp_mesh_sample_get_dev(wtp_ctx* ctx, void* d_xyz_out, int32_t* d_tri_out, void* d_r_out) {
-    if (!ctx) return WTP_ERR_ARG;
-    SampleState& S = ctx->sample;
-    if (!S.valid || S.fill || S.front) return fail(ctx, WTP_ERR_STATE, "no sample: call wtp_mesh_sample first");
-    WTP_HIP(ctx, hipSetDevice(ctx->device));
-    const int rc = rows_to_dev(ctx, 0, d_xyz_out, d_r_out);
-    if (rc) return rc;
+    int rc = check_resident(ctx, SampleKind::sample, kNoSample);
+    if (rc || (rc = rows_out(ctx, true, d_xyz_out, d_r_out))) return rc;
+    const SampleState& S = ctx->sample;
     if (d_tri_out) WTP_HIP(ctx, hipMemcpyAsync(d_tri_out, S.tri.p, 4 * (size_t)S.n, hipMemcpyDeviceToDevice, ctx->stream));
     return sync(ctx);
 }
@@ -1278,10 +949,8 @@ WTP_API int wtp_mesh_sample_darts(wtp_ctx* ctx, const wtp_spacing_desc* spacing,
 WTP_API int wtp_mesh_fill(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, const void* seeds, int64_t n_seeds,
                           int64_t max_points, int64_t stall_limit, uint64_t seed, int64_t batch, wtp_fill_info* info) {
     if (!ctx) return WTP_ERR_ARG;
-    int rc = check_run_args(ctx, spacing, factor, max_points, stall_limit, seed, batch);
+    int rc = check_run_args(ctx, spacing, factor, max_points, stall_limit, seed, batch, seeds, n_seeds);
     if (rc) return rc;
-    if (n_seeds < 0) return fail(ctx, WTP_ERR_ARG, "n_seeds must not be negative");
-    if (n_seeds > 0 && !seeds) return fail(ctx, WTP_ERR_ARG, "seeds is NULL");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     RunInfo ri{};
     rc = by_dtype(ctx->mesh.dtype, [&](auto t) {
@@ -1300,24 +969,17 @@ WTP_API int wtp_mesh_fill(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double 
 }
 
 WTP_API int wtp_mesh_fill_get(wtp_ctx* ctx, void* xyz_out, void* r_out, int64_t* dart_out) {
-    if (!ctx) return WTP_ERR_ARG;
-    SampleState& S = ctx->sample;
-    if (!S.valid || !S.fill || S.front) return fail(ctx, WTP_ERR_STATE, "no fill: call wtp_mesh_fill first");
-    WTP_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    if ((xyz_out || r_out) && (rc = rows_to_host(ctx, S.n_seeds, xyz_out, r_out))) return rc;
+    int rc = check_resident(ctx, SampleKind::fill, kNoFill);
+    if (rc || (rc = rows_out(ctx, false, xyz_out, r_out))) return rc;
+    const SampleState& S = ctx->sample;
     if (dart_out)
         WTP_HIP(ctx, hipMemcpyAsync(dart_out, (const int64_t*)S.dart.p + S.n_seeds, 8 * (size_t)S.n, hipMemcpyDeviceToHost, ctx->stream));
     return sync(ctx);
 }
 
 WTP_API int wtp_mesh_fill_get_dev(wtp_ctx* ctx, void* d_xyz_out, void* d_r_out) {
-    if (!ctx) return WTP_ERR_ARG;
-    SampleState& S = ctx->sample;
-    if (!S.valid || !S.fill || S.front) return fail(ctx, WTP_ERR_STATE, "no fill: call wtp_mesh_fill first");
-    WTP_HIP(ctx, hipSetDevice(ctx->device));
-    const int rc = rows_to_dev(ctx, S.n_seeds, d_xyz_out, d_r_out);
-    if (rc) return rc;
+    int rc = check_resident(ctx, SampleKind::fill, kNoFill);
+    if (rc || (rc = rows_out(ctx, true, d_xyz_out, d_r_out))) return rc;
     return sync(ctx);
 }
 
@@ -1346,37 +1008,29 @@ WTP_API int wtp_mesh_front(wtp_ctx* ctx, const wtp_spacing_desc* spacing, int64_
                            int64_t max_points, uint64_t seed, int64_t batch, wtp_front_info* info) {
     if (!ctx) return WTP_ERR_ARG;
     int rc = check_front_args(ctx, spacing, n, seed);
-    if (rc) return rc;
-    if (max_points < 1) return fail(ctx, WTP_ERR_ARG, "max_points must be positive");
-    if (batch < 0 || batch > (int64_t(1) << 24)) return fail(ctx, WTP_ERR_ARG, "batch must be in [0, 2^24]");
-    if (n_seeds < 0) return fail(ctx, WTP_ERR_ARG, "n_seeds must not be negative");
-    if (n_seeds > 0 && !seeds) return fail(ctx, WTP_ERR_ARG, "seeds is NULL");
+    if (rc || (rc = check_size_args(ctx, max_points, batch, seeds, n_seeds))) return rc;
     // the queue holds at most n_seeds + max_points rows, indexed in int32: refused here, not in the middle of a run
     if (n_seeds >= (int64_t(1) << 31) || max_points >= (int64_t(1) << 31) || n_seeds + max_points >= (int64_t(1) << 31) - 1)
         return fail(ctx, WTP_ERR_ARG, "n_seeds + max_points exceed the int32 index space of the queue");
     WTP_HIP(ctx, hipSetDevice(ctx->device));
-    FrontInfo fi{};
+    RunInfo ri{};
     rc = by_dtype(ctx->mesh.dtype, [&](auto t) {
         using T = decltype(t);
-        return front_run<T>(ctx, spacing, (int)n, (const T*)seeds, n_seeds, max_points, seed, batch, &fi);
+        return front_run<T>(ctx, spacing, (int)n, (const T*)seeds, n_seeds, max_points, seed, batch, &ri);
     });
     if (rc || !info) return rc;
-    info->n_points = fi.n_points, info->n_parents = fi.n_parents, info->n_candidates = fi.n_candidates;
-    info->n_inside = fi.n_inside, info->n_seeds = n_seeds, info->batch = fi.batch;
-    info->stop_reason = fi.stop_reason;
-    info->n_batches = fi.n_batches, info->rounds_max = fi.rounds_max, info->host_syncs = fi.host_syncs;
-    info->r_min = fi.r_min, info->r_max = fi.r_max;
+    info->n_points = ri.n_points, info->n_parents = (ri.n_darts + n - 1) / n, info->n_candidates = ri.n_darts;
+    info->n_inside = ri.n_inside, info->n_seeds = n_seeds, info->batch = ri.batch;
+    info->stop_reason = ri.stop_reason;
+    info->n_batches = ri.n_batches, info->rounds_max = ri.rounds_max, info->host_syncs = ri.host_syncs;
+    info->r_min = ri.r_min, info->r_max = ri.r_max;
     return WTP_OK;
 }
 
 WTP_API int wtp_mesh_front_get(wtp_ctx* ctx, void* xyz_out, void* h_out, int64_t* cand_out, int32_t* parent_out) {
-    if (!ctx) return WTP_ERR_ARG;
-    SampleState& S = ctx->sample;
-    if (!S.valid || !S.front) return fail(ctx, WTP_ERR_STATE, "no front: call wtp_mesh_front first");
-    if (S.n == 0) return WTP_OK;
-    WTP_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    if ((xyz_out || h_out) && (rc = rows_to_host(ctx, S.n_seeds, xyz_out, h_out))) return rc;
+    int rc = check_resident(ctx, SampleKind::front, kNoFront);
+    if (rc || ctx->sample.n == 0 || (rc = rows_out(ctx, false, xyz_out, h_out))) return rc;
+    const SampleState& S = ctx->sample;
     std::vector<int64_t> cand;
     int64_t* c = cand_out;
     if (parent_out && !c) cand.resize((size_t)S.n), c = cand.data();
@@ -1388,13 +1042,8 @@ WTP_API int wtp_mesh_front_get(wtp_ctx* ctx, void* xyz_out, void* h_out, int64_t
 }
 
 WTP_API int wtp_mesh_front_get_dev(wtp_ctx* ctx, void* d_xyz_out, void* d_h_out) {
-    if (!ctx) return WTP_ERR_ARG;
-    SampleState& S = ctx->sample;
-    if (!S.valid || !S.front) return fail(ctx, WTP_ERR_STATE, "no front: call wtp_mesh_front first");
-    if (S.n == 0) return WTP_OK;
-    WTP_HIP(ctx, hipSetDevice(ctx->device));
-    const int rc = rows_to_dev(ctx, S.n_seeds, d_xyz_out, d_h_out);
-    if (rc) return rc;
+    int rc = check_resident(ctx, SampleKind::front, kNoFront);
+    if (rc || ctx->sample.n == 0 || (rc = rows_out(ctx, true, d_xyz_out, d_h_out))) return rc;
     return sync(ctx);
 }
 

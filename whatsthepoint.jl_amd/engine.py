@@ -358,6 +358,12 @@ class Context:
         sd.kind, sd.constant = L.WTP_SPACING_CONSTANT, float(spacing)
         return sd, None
 
+    def _out_arrays(self, n: int, want, spec):
+        """Empty host arrays of n rows for the names of `spec` that `want` holds; spec: name -> dtype, None standing for
+        the mesh's, and "xyz" being (n, 3)."""
+        dt = self._mesh_dtype()
+        return {k: np.empty((n, 3) if k == "xyz" else n, dtype=d or dt) for k, d in spec.items() if k in want}
+
     def mesh_sample(self, spacing, factor: float = 0.75, max_points: int = 10_000_000, stall_limit: int = 2000,
                     seed: int = 0, batch: int = 0, spacing_desc=None):
         """wtp_mesh_sample on the mesh of mesh_set: the serial dart thrower over the seeded stream, decided in batches on
@@ -369,20 +375,11 @@ class Context:
                                        C.c_uint64(int(seed)), int(batch), C.byref(info))
         L.check(self._h, rc)
         del keep
-        return {name: getattr(info, name) for name, _ in L.SampleInfo._fields_}
+        return _info_dict(info)
 
     def mesh_sample_get(self, n: int, want=("xyz", "tri", "r", "dart")):
         """The n = info['n_points'] samples of the last mesh_sample as a dict of host arrays (mesh dtype)."""
-        dt = self._mesh_dtype()
-        out = {}
-        if "xyz" in want:
-            out["xyz"] = np.empty((n, 3), dtype=dt)
-        if "tri" in want:
-            out["tri"] = np.empty(n, dtype=np.int32)
-        if "r" in want:
-            out["r"] = np.empty(n, dtype=dt)
-        if "dart" in want:
-            out["dart"] = np.empty(n, dtype=np.int64)
+        out = self._out_arrays(n, want, dict(xyz=None, tri=np.int32, r=None, dart=np.int64))
         rc = self._lib.wtp_mesh_sample_get(self._h, _vp(out.get("xyz")), _vp(out.get("tri")), _vp(out.get("r")),
                                            _vp(out.get("dart")))
         L.check(self._h, rc)
@@ -412,28 +409,17 @@ class Context:
         box, decided in batches on the device.  seeds: (n, 3) points that occupy space from the start (converted to the
         mesh's dtype), or None.  Returns the info dict; the points stay on the device (mesh_fill_get)."""
         sd, keep = (spacing_desc, None) if spacing_desc is not None else self._sample_spacing(spacing)
-        s = None
-        if seeds is not None and len(seeds):
-            s = np.ascontiguousarray(seeds, dtype=self._mesh_dtype())
-            if s.ndim != 2 or s.shape[1] != 3:
-                raise L.WtpArgumentError("seeds must have shape (n, 3)")
+        s = self._seed_rows(seeds)
         info = L.FillInfo()
         rc = self._lib.wtp_mesh_fill(self._h, C.byref(sd), float(factor), _vp(s), 0 if s is None else len(s), int(max_points),
                                      int(stall_limit), C.c_uint64(int(seed)), int(batch), C.byref(info))
         L.check(self._h, rc)
         del keep
-        return {name: getattr(info, name) for name, _ in L.FillInfo._fields_}
+        return _info_dict(info)
 
     def mesh_fill_get(self, n: int, want=("xyz", "r", "dart")):
         """The n = info['n_points'] points of the last mesh_fill as a dict of host arrays (mesh dtype)."""
-        dt = self._mesh_dtype()
-        out = {}
-        if "xyz" in want:
-            out["xyz"] = np.empty((n, 3), dtype=dt)
-        if "r" in want:
-            out["r"] = np.empty(n, dtype=dt)
-        if "dart" in want:
-            out["dart"] = np.empty(n, dtype=np.int64)
+        out = self._out_arrays(n, want, dict(xyz=None, r=None, dart=np.int64))
         rc = self._lib.wtp_mesh_fill_get(self._h, _vp(out.get("xyz")), _vp(out.get("r")), _vp(out.get("dart")))
         L.check(self._h, rc)
         return out
@@ -475,21 +461,12 @@ class Context:
                                       C.c_uint64(int(seed)), int(batch), C.byref(info))
         L.check(self._h, rc)
         del keep
-        return {name: getattr(info, name) for name, _ in L.FrontInfo._fields_}
+        return _info_dict(info)
 
     def mesh_front_get(self, n: int, want=("xyz", "h", "cand", "parent")):
         """The n = info['n_points'] points of the last mesh_front as a dict of host arrays (mesh dtype): xyz, their own
         h, the candidate index each came from and its parent's queue index."""
-        dt = self._mesh_dtype()
-        out = {}
-        if "xyz" in want:
-            out["xyz"] = np.empty((n, 3), dtype=dt)
-        if "h" in want:
-            out["h"] = np.empty(n, dtype=dt)
-        if "cand" in want:
-            out["cand"] = np.empty(n, dtype=np.int64)
-        if "parent" in want:
-            out["parent"] = np.empty(n, dtype=np.int32)
+        out = self._out_arrays(n, want, dict(xyz=None, h=None, cand=np.int64, parent=np.int32))
         rc = self._lib.wtp_mesh_front_get(self._h, _vp(out.get("xyz")), _vp(out.get("h")), _vp(out.get("cand")),
                                           _vp(out.get("parent")))
         L.check(self._h, rc)
@@ -565,6 +542,11 @@ class Context:
         rc = self._lib.wtp_gen_uniform_dev(self._h, C.c_uint64(seed), first, n, dim, _dtype_code(dtype),
                                            C.c_void_p(d_out_ptr))
         L.check(self._h, rc)
+
+
+def _info_dict(info):
+    """A ctypes info struct as the dict the mesh_* runs return."""
+    return {name: getattr(info, name) for name, _ in type(info)._fields_}
 
 
 def _law_desc(law: dict, dtype, dim: int):

@@ -5,8 +5,8 @@
 `sample_surface` is graded Poisson-disk dart throwing on the continuous mesh surface.  The reference draws
 its darts from `rand`; here they come from the library's counter-based stream (include/wtp.h,
 wtp_mesh_sample), and the result is the serial loop over that stream, decided in batches on the device
-(csrc/wtp_sample.hip).  There is no CPU path: the host only checks arguments, looks up the parent
-triangles' normals and divides the area shares.
+(csrc/wtp_sample.hip, csrc/wtp_sample_streams.hip).  There is no CPU path: the host only checks arguments, looks
+up the parent triangles' normals and divides the area shares.
 
 `fill_volume` is the same run over darts uniform in the mesh's bounding box, of which those inside the mesh may be
 taken, with the boundary points as seeds that occupy space from the start (include/wtp.h, wtp_mesh_fill).
@@ -37,6 +37,13 @@ def _sampler_spacing(spacing):
                            f"ConstantSpacing, LogLike or BoundaryLayerSpacing, not {type(spacing).__name__}")
 
 
+def _check_positive(**args):
+    """The first of the named arguments, in the order given, that is not > 0 is the error."""
+    for name, value in args.items():
+        if not value > 0:
+            raise WtpArgumentError(f"{name} must be positive")
+
+
 def sample_surface(mesh, spacing, *, factor: float = 0.75, max_points: int = 10_000_000, stall_limit: int = 2000,
                    seed: int = synth.SEED, batch: int = 0, ctx=None):
     """sample_surface(mesh, spacing; factor, max_points, stall_limit) -> PointSurface (src/surface_sampling.jl:34-104).
@@ -48,20 +55,10 @@ def sample_surface(mesh, spacing, *, factor: float = 0.75, max_points: int = 10_
     changes time only.  The returned surface carries the run's wtp_sample_info as `sample_info`, the samples' r as
     `sample_r` and their parent triangles as `sample_tri`."""
     from .cloud import PointSurface
-    from .octree import TriangleOctree
 
-    if not factor > 0:
-        raise WtpArgumentError("factor must be positive")
-    if not stall_limit > 0:
-        raise WtpArgumentError("stall_limit must be positive")
-    if not max_points > 0:
-        raise WtpArgumentError("max_points must be positive")
+    _check_positive(factor=factor, stall_limit=stall_limit, max_points=max_points)
     law = _sampler_spacing(spacing)
-    if not isinstance(mesh, TriangleOctree):
-        vertices, triangles = mesh
-        mesh = TriangleOctree(vertices, triangles, classify_leaves=False, verify_orientation=False, ctx=ctx)
-    if len(mesh) == 0:
-        raise WtpArgumentError("mesh has no elements")
+    mesh = _as_octree(mesh, ctx, False)
     c = mesh._resident(ctx)
     info = c.mesh_sample(law, factor, max_points, stall_limit, int(seed) & 0xFFFFFF, batch)
     n = int(info["n_points"])
@@ -103,12 +100,7 @@ def fill_volume(mesh, spacing, *, seeds=None, factor: float = 0.75, max_points: 
     bbox_volume * n_inside / n_darts added) and the points' r as `fill_r`."""
     from .cloud import PointVolume
 
-    if not factor > 0:
-        raise WtpArgumentError("factor must be positive")
-    if not stall_limit > 0:
-        raise WtpArgumentError("stall_limit must be positive")
-    if not max_points > 0:
-        raise WtpArgumentError("max_points must be positive")
+    _check_positive(factor=factor, stall_limit=stall_limit, max_points=max_points)
     law = _sampler_spacing(spacing)
     mesh = _as_octree(mesh, ctx, True)
     c = mesh._resident(ctx)
@@ -152,8 +144,7 @@ def front_volume(mesh, spacing, *, seeds, n: int = 10, max_points: int = 10_000_
     `front_parent`."""
     from .cloud import PointVolume
 
-    if not max_points > 0:
-        raise WtpArgumentError("max_points must be positive")
+    _check_positive(max_points=max_points)
     n = SlakKosec(n).n
     law = _sampler_spacing(spacing)
     mesh = _as_octree(mesh, ctx, True)
