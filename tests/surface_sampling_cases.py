@@ -10,7 +10,13 @@ The model, in the mesh's type T unless said otherwise:
   serial() darts in order; a dart is accepted iff ((dx dx + dy dy) + dz dz) < m m, m = min(r_p, r_q), holds for no
            accepted q; before each dart the run ends at max_points accepted (2) or stall_limit misses in a row (1)
   batched() the library's batch algorithm in plain Python: cull against the accepted set, Jacobi rounds over the
-           batch's live darts, stop scan in dart order; reports the largest round count of a batch"""
+           batch's live darts, stop scan in dart order; reports the largest round count of a batch.  The library
+           always decides a whole batch, so the round count is the library's when the model is given the darts of
+           whole batches (whole_batches); batch = 0 is the library's own schedule (batch_sizes)
+
+EDGE_CASES are the cases of test_gpu_sampler_edges.py: runs that end on a batch or tile seam of the stop scan, a batch
+that needs more than one group of rounds, and meshes whose cell map is degenerate.  case_of() finds a case of either
+table."""
 from __future__ import annotations
 
 import functools
@@ -38,6 +44,20 @@ def cube_with_zero_area_triangles():
     v, t = cube()
     flat = np.array([(0, 1, 1)], dtype=np.int32)  # two corners coincide: area 0, the running sum is flat there
     return v, np.concatenate([flat, t[:6], flat, t[6:]])
+
+
+def plate(shift=0.0):
+    """The unit square in the plane z = 0 as two triangles: a bounding box without height."""
+    v = np.array([(0, 0, 0), (1, 0, 0), (1, 1, 0), (0, 1, 0)], dtype=F64) + shift
+    return v, np.array([(0, 1, 2), (0, 2, 3)], dtype=np.int32)
+
+
+def cube_stretched():
+    """The cube and, behind its triangles, one of area 0 whose corners lie 3e5 away: it is never picked, and the box it
+    stretches is so much longer than any r that the cell edge is the box's 1e-6 floor, 0.3."""
+    v, t = cube()
+    far = np.array([(3e5, 0, 0), (3e5, 1, 0)], dtype=F64)
+    return np.concatenate([v, far]), np.concatenate([t, np.array([(8, 8, 9)], dtype=np.int32)])
 
 
 def one_triangle():
@@ -82,9 +102,37 @@ CASES = {
     "box": dict(mesh=box, spacing=("const", 1.8), factor=0.75, stall_limit=2000, horizon=48000),  # 1253 / 41922
 }
 
+# Measured with serial() / batched(); Float32 and Float64 agree wherever both run.
+EDGE_CASES = {
+    # r = 0.02: dart 2047 is accepted as sample 1686 and dart 4095 as sample 2849, so max_points = 1686 / 2849 end the
+    # run at n_darts = 2048 / 4096, the seams of the stop scan's tiles of 2048 positions.  The seed was searched for that.
+    "cube_fine": dict(mesh=cube, spacing=("const", 0.02), factor=1.0, stall_limit=2000, max_points=2849, seed=3483607,
+                      horizon=8192),  # 2849 / 4096
+    # a batch of 16384 darts at r = 0.05 needs more rounds than the library runs in one group (8): 10 for the first batch.
+    # 1339 samples come from the first batch and sample 1400 is dart 25875, so max_points = 1380 ends the run inside the
+    # second batch
+    "cube_r005": dict(mesh=cube, spacing=("const", 0.05), factor=1.0, stall_limit=2000, max_points=1380, batch=16384,
+                      horizon=32768, dtypes=[F32]),  # 1380 / 22422, rounds_max 10
+    # a box without height: one layer of cells (nc[2] = 1)
+    "plate": dict(mesh=plate, spacing=("const", 0.05), factor=0.75, stall_limit=2000, horizon=16384),  # 469 / 14960
+    "plate_far": dict(mesh=lambda: plate(1000.0), spacing=("const", 0.05), factor=0.75, stall_limit=2000, horizon=16384,
+                      dtypes=[F32]),  # 469 / 14960
+    # cube_f075's darts in a box of 3e5: ext / 1e6 = 0.3 > r = 0.1125 sets the cell edge
+    "cube_stretched": dict(mesh=cube_stretched, spacing=("const", 0.15), factor=0.75, stall_limit=2000,
+                           horizon=20000),  # 299 / 17394
+}
+
+
+def case_of(name):
+    return CASES[name] if name in CASES else EDGE_CASES[name]
+
 
 def case_dtypes(name):
-    return CASES[name].get("dtypes", DTYPES)
+    return case_of(name).get("dtypes", DTYPES)
+
+
+def seed_of(case):
+    return case.get("seed", SEED)
 
 
 def max_points_of(case):
@@ -93,13 +141,13 @@ def max_points_of(case):
 
 @functools.lru_cache(maxsize=None)
 def mesh_of(name, dtype):
-    v, t = CASES[name]["mesh"]()
+    v, t = case_of(name)["mesh"]()
     return np.ascontiguousarray(v.astype(dtype)), np.ascontiguousarray(t)
 
 
 def library_spacing(wtp, name, dtype):
     """The case's spacing as the package takes it."""
-    sp = CASES[name]["spacing"]
+    sp = case_of(name)["spacing"]
     if sp[0] == "const":
         return sp[1]
     if sp[0] == "bl":
@@ -155,9 +203,10 @@ def law_h(sp, c):
     return p0 + (p1 - p0) * sig
 
 
-def darts(name, dtype, first, n, seed=SEED):
-    """Darts first .. first + n - 1 of the case: (xyz (n, 3) dtype, tri int32, r dtype)."""
-    case = CASES[name]
+def darts(name, dtype, first, n, seed=None):
+    """Darts first .. first + n - 1 of the case (seed: the case's own unless given): (xyz (n, 3) dtype, tri int32, r dtype)."""
+    case = case_of(name)
+    seed = seed_of(case) if seed is None else seed
     T = np.dtype(dtype).type
     v, t = mesh_of(name, dtype)
     cum, total = areas_of(name, dtype)
@@ -230,41 +279,69 @@ def _lower_conflicts(xyz, r):
     return np.concatenate(rows), np.concatenate(cols)
 
 
-def batched(xyz, r, max_points, stall_limit, batch):
-    """The same run decided in batches of `batch` darts: (accepted, n_darts, stop_reason, rounds_max)."""
+BATCH_FIRST, BATCH_MAX = 4096, 1 << 20  # batch = 0: the library doubles its batches from / up to these
+
+
+def batch_sizes(batch):
+    """The sizes of a run's batches, without end: `batch` every time, or the library's own schedule at batch = 0."""
+    B = batch if batch > 0 else BATCH_FIRST
+    while True:
+        yield B
+        if batch == 0:
+            B = min(2 * B, BATCH_MAX)
+
+
+def whole_batches(n_darts, batch):
+    """(n_batches, darts in them) of a run of n_darts darts: a run that ends at position B of a batch ends in that batch."""
+    k = total = 0
+    for B in batch_sizes(batch):
+        k, total = k + 1, total + B
+        if total >= n_darts:
+            return k, total
+
+
+def jacobi_rounds(rows, cols, n, B):
+    """The rounds over n live darts with the conflict pairs cols < rows: (accepted bool (n,), rounds).  0 undecided,
+    1 accepted, 2 rejected; a round reads the states the previous one left."""
+    st = np.zeros(n, dtype=np.int8)
+    rounds = 0
+    while True:
+        rounds += 1
+        prev = st[cols]
+        by_acc = np.bincount(rows[prev == 1], minlength=n) > 0
+        pending = np.bincount(rows[prev == 0], minlength=n) > 0
+        und = st == 0
+        st[und & by_acc] = 2
+        st[und & ~by_acc & ~pending] = 1
+        if not (st == 0).any():
+            return st == 1, rounds
+        if rounds > B:
+            raise AssertionError("a batch needs at most as many rounds as it has darts")
+
+
+def batched_run(xyz, r, max_points, stall_limit, batch):
+    """The same run decided in batches of `batch` darts (0: the library's schedule): dict(acc, n_darts, stop_reason,
+    rounds_max, n_batches)."""
     n = len(xyz)
     acc = np.zeros(0, dtype=np.int64)
-    misses, first, rounds_max = 0, 0, 0
-    while True:
+    misses, first, rounds_max, n_batches = 0, 0, 0, 0
+    for size in batch_sizes(batch):
         if first >= n:
             raise ValueError(f"the run needs more than {n} darts")
-        B = min(batch, n - first)  # (a short last batch only when the darts run out: the run must end inside it)
+        B = min(size, n - first)  # (a short last batch only when the darts run out: the run must end inside it)
         bx, br = xyz[first:first + B], r[first:first + B]
         # cull against the accepted set
         live = np.ones(B, dtype=bool)
-        for i in range(B):
-            if len(acc) and _conflicts(xyz[acc], r[acc], bx[i], br[i]).any():
+        ax, ar = xyz[acc], r[acc]
+        for i in range(B if len(acc) else 0):
+            if _conflicts(ax, ar, bx[i], br[i]).any():
                 live[i] = False
         ids = np.nonzero(live)[0]
         rows, cols = _lower_conflicts(bx[ids], br[ids])
-        # Jacobi rounds: 0 undecided, 1 accepted, 2 rejected; a round reads the states the previous one left
-        st = np.zeros(len(ids), dtype=np.int8)
-        rounds = 0
-        while True:
-            rounds += 1
-            prev = st[cols]
-            by_acc = np.bincount(rows[prev == 1], minlength=len(ids)) > 0
-            pending = np.bincount(rows[prev == 0], minlength=len(ids)) > 0
-            und = st == 0
-            st[und & by_acc] = 2
-            st[und & ~by_acc & ~pending] = 1
-            if not (st == 0).any():
-                break
-            if rounds > B:
-                raise AssertionError("a batch needs at most as many rounds as it has darts")
-        rounds_max = max(rounds_max, rounds)
+        taken_by_rounds, rounds = jacobi_rounds(rows, cols, len(ids), B)
+        n_batches, rounds_max = n_batches + 1, max(rounds_max, rounds)
         flag = np.zeros(B, dtype=bool)
-        flag[ids[st == 1]] = True
+        flag[ids[taken_by_rounds]] = True
         # stop scan in dart order, position B included
         taken, new, reason = B, [], 0
         for i in range(B + 1):
@@ -283,14 +360,20 @@ def batched(xyz, r, max_points, stall_limit, batch):
                 misses += 1
         acc = np.concatenate([acc, np.array(new, dtype=np.int64)])
         if reason:
-            return acc, first + taken, reason, rounds_max
+            return dict(acc=acc, n_darts=first + taken, stop_reason=reason, rounds_max=rounds_max, n_batches=n_batches)
         first += B
+
+
+def batched(xyz, r, max_points, stall_limit, batch):
+    """batched_run() as (accepted, n_darts, stop_reason, rounds_max)."""
+    b = batched_run(xyz, r, max_points, stall_limit, batch)
+    return b["acc"], b["n_darts"], b["stop_reason"], b["rounds_max"]
 
 
 @functools.lru_cache(maxsize=None)
 def model_run(name, dtype):
     """(xyz, tri, r of the case's horizon of darts, accepted, n_darts, stop_reason) by serial(), computed once."""
-    case = CASES[name]
+    case = case_of(name)
     xyz, tri, r = darts(name, dtype, 0, case["horizon"])
     acc, n_darts, reason = serial(xyz, r, max_points_of(case), case["stall_limit"])
     for a in (xyz, tri, r, acc):

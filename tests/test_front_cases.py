@@ -33,6 +33,22 @@ def test_batches_equal_the_serial_loop(name, dtype):
         assert 1 <= got["rounds_max"] <= (batch * case["n"] if batch else got["n_candidates"])
 
 
+@pytest.mark.parametrize("name,want", [("grid8", {1: (487, 3), 7: (70, 4), 0: (6, 6)}),
+                                       ("grid12_bl", {1: (1241, 3), 7: (178, 8), 0: (7, 9)}),
+                                       ("centre", {1: (235, 4), 7: (37, 5), 0: (12, 5)})])
+def test_batches_and_rounds_of_the_model(name, want):
+    """(n_batches, rounds_max) by batch, as measured (Float32 and Float64 agree): what test_gpu_sampler_edges.py holds the
+    library's counts against.  grid12_bl with every parent available needs more rounds than one group of 8."""
+    case = Fc.CASES[name]
+    for dtype in Fc.DTYPES:
+        for batch, (n_batches, rounds_max) in want.items():
+            got = Fc.batched(Fc.seeds_of(name, dtype), case["n"], Fc.max_points_of(case), Fc.model_source(name, dtype), batch)
+            assert (got["n_batches"], got["rounds_max"]) == (n_batches, rounds_max), (dtype, batch)
+            if batch == 1:
+                assert got["n_batches"] == got["n_parents"]
+    assert want[0][1] <= 8 or name == "grid12_bl"
+
+
 @pytest.mark.parametrize("n,batch", Fc.ODD_BATCHES)
 def test_candidate_batches_of_63_64_and_65(n, batch):
     assert n * batch in (63, 64, 65)

@@ -55,8 +55,9 @@ def test_darts_equal_the_model(wtp, ctx, name, dtype, first):
 @pytest.mark.parametrize("name,dtype", ALL, ids=IDS)
 def test_accepted_set_equals_the_serial_loop_over_the_librarys_darts(wtp, ctx, name, dtype):
     case, sp = _set(wtp, ctx, name, dtype)
-    xyz, tri, r = ctx.mesh_sample_darts(sp, case["factor"], S.SEED, 0, case["horizon"])
-    acc, n_darts, reason = S.serial(xyz, r, S.max_points_of(case), case["stall_limit"])
+    n = S.whole_batches(case["horizon"], 0)[1]                          # the darts of every batch a run within the horizon decides
+    xyz, tri, r = ctx.mesh_sample_darts(sp, case["factor"], S.SEED, 0, n)
+    acc, n_darts, reason = S.serial(xyz[:case["horizon"]], r[:case["horizon"]], S.max_points_of(case), case["stall_limit"])
     info, got = _sample(ctx, case, sp)
     print(f"{name} {np.dtype(dtype).name}: n_points={info['n_points']} n_darts={info['n_darts']} batches={info['n_batches']} "
           f"rounds_max={info['rounds_max']} host_syncs={info['host_syncs']}")
@@ -65,6 +66,11 @@ def test_accepted_set_equals_the_serial_loop_over_the_librarys_darts(wtp, ctx, n
     assert np.array_equal(got["xyz"], xyz[acc]) and np.array_equal(got["tri"], tri[acc]) and np.array_equal(got["r"], r[acc])
     assert info["r_min"] == float(r[acc].min()) and info["r_max"] == float(r[acc].max())
     assert info["total_area"] == S.areas_of(name, dtype)[1]
+    # batch = 0 is the schedule of S.batch_sizes: the batch model over the same whole batches counts the same batches and rounds
+    nb, whole = S.whole_batches(n_darts, 0)
+    b = S.batched_run(xyz[:whole], r[:whole], S.max_points_of(case), case["stall_limit"], 0)
+    assert np.array_equal(b["acc"], acc) and b["n_batches"] == nb
+    assert (info["n_batches"], info["rounds_max"]) == (b["n_batches"], b["rounds_max"])
     if name == "one_triangle":
         assert info["n_points"] == 1 and info["n_darts"] == 1 + case["stall_limit"] and info["stop_reason"] == 1
     if name == "cube_stall3":

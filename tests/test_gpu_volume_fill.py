@@ -64,9 +64,11 @@ def test_darts_equal_the_model(wtp, ctx, name, dtype, first):
 @pytest.mark.parametrize("name,dtype", ALL, ids=IDS)
 def test_accepted_set_equals_the_serial_loop_over_the_librarys_darts(wtp, ctx, name, dtype):
     case, sp, seeds = _set(wtp, ctx, name, dtype)
-    xyz, inside, r = ctx.mesh_fill_darts(sp, case["factor"], V.SEED, 0, case["horizon"])
+    h = case["horizon"]
+    n = V.whole_batches(h, 0)[1]                                        # the darts of every batch a run within the horizon decides
+    xyz, inside, r = ctx.mesh_fill_darts(sp, case["factor"], V.SEED, 0, n)
     sr = _seed_r(ctx, case, sp, seeds, dtype)
-    acc, n_darts, reason, n_in = V.serial(xyz, inside, r, seeds, sr, V.max_points_of(case), case["stall_limit"])
+    acc, n_darts, reason, n_in = V.serial(xyz[:h], inside[:h], r[:h], seeds, sr, V.max_points_of(case), case["stall_limit"])
     info, got = _fill(ctx, case, sp, seeds)
     print(f"{name} {np.dtype(dtype).name}: n_points={info['n_points']} n_darts={info['n_darts']} n_inside={info['n_inside']} "
           f"batches={info['n_batches']} rounds_max={info['rounds_max']} host_syncs={info['host_syncs']}")
@@ -78,6 +80,11 @@ def test_accepted_set_equals_the_serial_loop_over_the_librarys_darts(wtp, ctx, n
     else:
         assert info["r_min"] == 0.0 and info["r_max"] == 0.0         # WTP_OK with no point at the ABI
     assert info["bbox_volume"] == V.bbox_volume(name, dtype)
+    # batch = 0 is the schedule of V.batch_sizes: the batch model over the same whole batches counts the same batches and rounds
+    nb, whole = V.whole_batches(n_darts, 0)
+    b = V.batched_run(xyz[:whole], inside[:whole], r[:whole], seeds, sr, V.max_points_of(case), case["stall_limit"], 0)
+    assert np.array_equal(b["acc"], acc) and b["n_inside"] == n_in and b["n_batches"] == nb
+    assert (info["n_batches"], info["rounds_max"]) == (b["n_batches"], b["rounds_max"])
     if case["spacing"][0] == "const" and len(V.mesh_of(name, dtype)[1]) <= 12:   # the model's own counts (12 triangles)
         assert (len(acc), n_darts, n_in) == (len(V.model_run(name, dtype)[3]),) + V.model_run(name, dtype)[4:7:2]
     if name == "cube_const10":

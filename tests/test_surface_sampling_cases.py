@@ -10,7 +10,7 @@ F32, F64 = S.F32, S.F64
 
 
 def _run(name, dtype=F32):
-    case = S.CASES[name]
+    case = S.case_of(name)
     xyz, tri, r, acc, n_darts, reason = S.model_run(name, dtype)
     return case, xyz, tri, r, acc, n_darts, reason
 
@@ -98,6 +98,89 @@ def test_case_properties():
     assert not np.isin(tri0, [0, 7]).any() and np.array_equal(xyz0, xyz1) and np.array_equal(acc0, acc1) and nd0 == nd1
     _, _, _, _, acc, _, _ = _run("box")
     assert 1000 <= len(acc) <= 2000
+
+
+# ---- the edge cases of test_gpu_sampler_edges.py: the numbers its runs rely on -------------------------------------------
+def test_whole_batches_and_the_schedule_of_batch_0():
+    assert S.whole_batches(2048, 2048) == (1, 2048)                   # a run that ends at position B ends in that batch
+    assert S.whole_batches(2049, 2048) == (2, 4096) and S.whole_batches(1, 7) == (1, 7)
+    assert S.whole_batches(4096, 0) == (1, 4096) and S.whole_batches(4097, 0) == (2, 4096 + 8192)
+    # batch = 0 doubles from 4096 up to 2^20: the ninth batch is the first of 2^20 darts, and it ends at dart 4096 * 511
+    assert S.whole_batches(4096 * 511, 0) == (9, 4096 * 511) and S.whole_batches(4096 * 511 + 1, 0) == (10, 4096 * 511 + 2 ** 20)
+    sizes = S.batch_sizes(0)
+    assert [next(sizes) for _ in range(11)] == [4096 << k for k in range(8)] + [2 ** 20] * 3
+    # the schedule changes neither the result nor, given whole batches of darts, what a fixed batch of its size computes
+    case, xyz, tri, r, acc, n_darts, reason = _run("cube_f075")
+    nb, nd = S.whole_batches(n_darts, 0)
+    assert (nb, nd) == (3, 4096 + 8192 + 16384) and nd > case["horizon"]
+    wx, _, wr = S.darts("cube_f075", F32, 0, nd)
+    b = S.batched_run(wx, wr, S.max_points_of(case), case["stall_limit"], 0)
+    assert np.array_equal(b["acc"], acc) and (b["n_darts"], b["stop_reason"], b["n_batches"]) == (n_darts, reason, 3)
+    assert b["rounds_max"] == 7                                       # measured: one group of the library's rounds
+
+
+@pytest.mark.parametrize("dtype", S.DTYPES)
+def test_cube_fine_accepts_the_darts_in_front_of_the_tile_seams(dtype):
+    case, xyz, tri, r, acc, n_darts, reason = _run("cube_fine", dtype)
+    assert case["max_points"] == 2849 and (len(acc), n_darts, reason) == (2849, 4096, 2)
+    assert acc[1685] == 2047 and acc[2848] == 4095                  # sample 1686 is dart 2047, sample 2849 is dart 4095
+    got, nd, why = S.serial(xyz, r, 1686, case["stall_limit"])
+    assert np.array_equal(got, acc[:1686]) and (nd, why) == (2048, 2)
+    for max_points, batch in ((1686, 2048), (1686, 2047), (1686, 4096), (2849, 4096)):
+        nb, whole = S.whole_batches(2048 if max_points == 1686 else 4096, batch)
+        b = S.batched_run(xyz[:whole], r[:whole], max_points, case["stall_limit"], batch)
+        assert np.array_equal(b["acc"], acc[:max_points]) and b["n_batches"] == nb and b["stop_reason"] == 2
+        assert b["n_darts"] == (2048 if max_points == 1686 else 4096)
+
+
+@pytest.mark.parametrize("name", ["cube_max37", "cube_stall3", "one_triangle"])
+def test_batches_that_end_with_the_run(name):
+    case, xyz, tri, r, acc, n_darts, reason = _run(name)
+    batches = [n_darts - 1, n_darts, n_darts + 1] + ([1, 7, 10, 25] if name == "one_triangle" else [])
+    for batch in batches:
+        nb, whole = S.whole_batches(n_darts, batch)
+        assert nb == -(-n_darts // batch)
+        wx, _, wr = (xyz, tri, r) if whole <= case["horizon"] else S.darts(name, F32, 0, whole)
+        b = S.batched_run(wx[:whole], wr[:whole], S.max_points_of(case), case["stall_limit"], batch)
+        assert np.array_equal(b["acc"], acc) and (b["n_darts"], b["stop_reason"], b["n_batches"]) == (n_darts, reason, nb)
+    if name == "one_triangle":                                        # whole batches that accept nothing carry the miss run
+        assert list(acc) == [0] and n_darts == 51 and S.whole_batches(51, 7)[0] == 8
+
+
+def test_cube_r005_needs_more_than_one_group_of_rounds():
+    case, xyz, tri, r, acc, n_darts, reason = _run("cube_r005")
+    batch = case["batch"]
+    assert (len(acc), n_darts, reason) == (1380, 22422, 2) and (acc < batch).sum() == 1339
+    assert batch < n_darts < 2 * batch == case["horizon"]            # the run ends inside the second batch
+    b = S.batched_run(xyz, r, case["max_points"], case["stall_limit"], batch)
+    assert np.array_equal(b["acc"], acc) and (b["n_darts"], b["stop_reason"], b["n_batches"]) == (n_darts, reason, 2)
+    assert b["rounds_max"] == 10 > 8                                  # the library runs its rounds in groups of 8
+
+
+def test_edge_cell_maps():
+    # a box without height; the same far from the origin in Float32
+    for name in ("plate", "plate_far"):
+        for dtype in S.case_dtypes(name):
+            case, xyz, tri, r, acc, n_darts, reason = _run(name, dtype)
+            v, _ = S.mesh_of(name, dtype)
+            assert v[:, 2].min() == v[:, 2].max() == (0.0 if name == "plate" else 1000.0)
+            assert np.abs(xyz[:, 2] - v[0, 2]).max() <= (0.0 if name == "plate" else 4 * np.spacing(F32(1000.0)))
+            # (three products and two sums round: far from the origin a dart may leave the plane, and with it the box)
+            assert name == "plate" or (xyz[:, 2] != v[0, 2]).any()
+            assert (len(acc), n_darts, reason) == (469, 14960, 1) and n_darts <= case["horizon"]
+    assert S.case_dtypes("plate_far") == [F32] and S.mesh_of("plate_far", F32)[0].min() == 1000.0
+    # the stretched cube: the extra triangle has no area and is never picked, so the darts are cube_f075's, but the box
+    # is 3e5 long and a millionth of that is more than r
+    for dtype in S.DTYPES:
+        case, xyz, tri, r, acc, n_darts, reason = _run("cube_stretched", dtype)
+        _, xyz0, tri0, r0, acc0, nd0, why0 = _run("cube_f075", dtype)
+        v, t = S.mesh_of("cube_stretched", dtype)
+        cum, total = S.areas_of("cube_stretched", dtype)
+        assert len(t) == 13 and cum[12] == cum[11] and total == 6.0 and not (tri == 12).any()
+        assert np.array_equal(xyz, xyz0) and np.array_equal(tri, tri0) and np.array_equal(r, r0)
+        assert np.array_equal(acc, acc0) and (n_darts, reason) == (nd0, why0) == (17394, 1)
+        ext = float(v.max(axis=0)[0] - v.min(axis=0)[0])
+        assert ext == 3e5 and ext / 1e6 > float(r[0]) == float(dtype(0.75) * dtype(0.15))
 
 
 def test_darts_are_the_uniform_stream(wtp):

@@ -10,7 +10,7 @@ F32, F64 = V.F32, V.F64
 
 
 def _run(name, dtype=F32):
-    case = V.CASES[name]
+    case = V.case_of(name)
     return (case,) + V.model_run(name, dtype) + V.seeds_of(name, dtype)
 
 
@@ -100,6 +100,55 @@ def test_case_properties():
     assert 300 <= len(acc_b) <= 3000 and why_b == 1 and nin_b == nd_b
     est = V.bbox_volume("box_stall200", F32) * nin_b / nd_b
     assert abs(est - 15625.0) <= 1e-3 * 15625.0                         # the box mesh fills its bounding box
+
+
+# ---- the edge cases of test_gpu_sampler_edges.py: the numbers its runs rely on -------------------------------------------
+@pytest.mark.parametrize("dtype", V.DTYPES)
+def test_needle_runs_end_beyond_the_256th_tile_of_the_stop_scan(dtype):
+    v, t = V.mesh_of("needle", dtype)
+    lo, hi = V.box_of("needle", dtype)
+    assert (lo == 0).all() and (hi == 1).all() and len(t) == 4       # the bounding box is the unit cube
+    vol = sum(np.linalg.det(v.astype(F64)[tri]) for tri in t) / 6
+    assert abs(vol - 0.12 * 0.12 / 6) <= 1e-9                           # positive: the inside is inside
+    xyz, inside, r = V.needle_darts(dtype)
+    assert xyz.dtype == dtype and len(xyz) == 3 << 20
+    assert inside[:1 << 20].sum() == 2496 and inside.sum() == 7492      # 0.24 % of the darts
+    # max_points = 618: tile 340 of a batch of 2^20 darts
+    case, mx, mi, mr, acc, n_darts, reason, n_in, sx, sr = _run("needle", dtype)
+    assert len(mx) == 1 << 20 and np.array_equal(mx, xyz[:1 << 20]) and len(sx) == 0
+    assert (len(acc), n_darts, reason, n_in) == (618, 697597, 2, 1677) and n_darts // 2048 == 340
+    # stall_limit = 8929, one more than the longest miss run in front of the tile behind the carry: tile 273
+    case, _, _, _, acc_s, nd_s, why_s, nin_s, _, _ = _run("needle_stall", dtype)
+    assert (len(acc_s), nd_s, why_s, nin_s) == (571, 560383, 1, 1355) and nd_s // 2048 == 273
+    miss = np.diff(np.concatenate([[-1], acc_s])) - 1
+    assert miss.max() == 8928 == case["stall_limit"] - 1 and (acc_s < 528384).sum() == 557
+    assert min(n_darts, nd_s) >= V.SCAN_CARRY_FROM == 526336            # both stops need the scan's carry
+    # batch = 0: the run ends in a batch of 2^20 darts, the tenth
+    case, cx, ci, cr, acc_c, nd_c, why_c, nin_c, _, _ = _run("needle_clamp", dtype)
+    assert len(cx) == 3 << 20 and (len(acc_c), nd_c, why_c, nin_c) == (900, 2594928, 2, 6135)
+    assert nd_c > V.CLAMPED_FROM == 2093056 and V.whole_batches(nd_c, 0) == (10, V.CLAMPED_FROM + 2 ** 20)
+    assert np.array_equal(acc_c[:618], acc) and np.array_equal(acc_c[:571], acc_s)
+
+
+def test_needle_in_one_batch_equals_the_serial_loop():
+    for name in ("needle", "needle_stall"):
+        case, xyz, inside, r, acc, n_darts, reason, n_in, sx, sr = _run(name)
+        b = V.batched_run(xyz, inside, r, sx, sr, V.max_points_of(case), case["stall_limit"], 1 << 20)
+        assert np.array_equal(b["acc"], acc) and (b["n_darts"], b["stop_reason"], b["n_inside"]) == (n_darts, reason, n_in)
+        assert b["n_batches"] == 1
+
+
+@pytest.mark.parametrize("name", ["cube_stall200", "cube_const10"])
+def test_batches_that_end_with_the_run(name):
+    case, xyz, inside, r, acc, n_darts, reason, n_in, sx, sr = _run(name)
+    for batch in (n_darts - 1, n_darts, n_darts + 1):
+        nb, whole = V.whole_batches(n_darts, batch)
+        assert nb == -(-n_darts // batch)
+        if whole > case["horizon"]:
+            xyz, inside, r = V.darts(name, F32, 0, whole)
+        b = V.batched_run(xyz[:whole], inside[:whole], r[:whole], sx, sr, V.max_points_of(case), case["stall_limit"], batch)
+        assert np.array_equal(b["acc"], acc) and b["n_batches"] == nb
+        assert (b["n_darts"], b["stop_reason"], b["n_inside"]) == (n_darts, reason, n_in)
 
 
 def test_darts_are_the_uniform_stream(wtp):

@@ -10,7 +10,11 @@ The model, in the mesh's type T:
             holds for no seed and no accepted q; before each dart the run ends at max_points accepted (2) or
             stall_limit misses in a row (1); seeds are never tested against each other and never returned
   batched() the library's batch algorithm in plain Python: darts outside the mesh and darts in conflict with a seed or
-            an accepted point are culled, Jacobi rounds over the rest, stop scan in dart order"""
+            an accepted point are culled, Jacobi rounds over the rest, stop scan in dart order; batch = 0 is the
+            library's own schedule, and the round count is the library's when the darts are those of whole batches
+
+EDGE_CASES are the cases of test_gpu_sampler_edges.py: runs that end beyond the 256th tile of the stop scan.  case_of()
+finds a case of either table."""
 from __future__ import annotations
 
 import functools
@@ -20,7 +24,7 @@ import numpy as np
 
 import oracle
 from surface_sampling_cases import F32, F64, DTYPES, SEED, GOLD, LAW_POINTS, _splitmix64, _conflicts, cube, law_h
-from surface_sampling_cases import _lower_conflicts
+from surface_sampling_cases import _lower_conflicts, batch_sizes, whole_batches, jacobi_rounds  # noqa: F401
 
 
 # ---- meshes and seeds ---------------------------------------------------------------------------------------------
@@ -49,6 +53,13 @@ def face_grid(m, scale=(1.0, 1.0, 1.0), axes=(0, 1, 2)):
             p[:, (ax + 1) % 3], p[:, (ax + 2) % 3] = a, b
             out.append(p * np.asarray(scale))
     return np.concatenate(out)
+
+
+def needle():
+    """A thin tetrahedron from the origin to (1, 1, 1): its bounding box is the unit cube, of which it fills 0.24 %."""
+    v = np.array([(0, 0, 0), (1, 1, 1), (0.12, 0, 0), (0, 0.12, 0)], dtype=F64)
+    t = np.array([(0, 1, 2), (0, 3, 1), (0, 2, 3), (1, 3, 2)], dtype=np.int32)
+    return v, np.ascontiguousarray(t[:, ::-1])  # each row reversed: the normals point outwards
 
 
 # ---- the cases --------------------------------------------------------------------------------------------------------
@@ -81,9 +92,28 @@ CASES = {
                          dtypes=[F32]),  # 1254 / 10167
 }
 
+# The stop scan works in tiles of 2048 positions and carries its counts from one chunk of 256 tiles to the next, so the
+# carry matters from position 256 * 2048 + 2048 = 526 336 on: the needle's runs end beyond it.  2496 of the first 2^20
+# darts are inside (7492 of 3 * 2^20); 557 of the 705 darts accepted among the first 2^20 lie before dart 528 384, and
+# the longest miss run before it is 8928.  Float32 and Float64 agree in every number.
+_NEEDLE = dict(mesh=needle, spacing=("const", 0.012), factor=1.0, horizon=1 << 20)
+SCAN_CARRY_FROM = 257 * 2048
+EDGE_CASES = {
+    "needle": dict(_NEEDLE, max_points=618, stall_limit=1_000_000),  # 618 / 697597, inside 1677: tile 340
+    "needle_stall": dict(_NEEDLE, stall_limit=8929),  # 571 / 560383, inside 1355: tile 273
+    # batch = 0: the ninth batch is the first of 2^20 darts; from dart 4096 * 511 = 2 093 056 on, the tenth batch, doubling
+    # again is what the library's clamp prevents
+    "needle_clamp": dict(_NEEDLE, max_points=900, stall_limit=1_000_000, horizon=3 << 20),  # 900 / 2594928, inside 6135
+}
+CLAMPED_FROM = 4096 * 511
+
+
+def case_of(name):
+    return CASES[name] if name in CASES else EDGE_CASES[name]
+
 
 def case_dtypes(name):
-    return CASES[name].get("dtypes", DTYPES)
+    return case_of(name).get("dtypes", DTYPES)
 
 
 def max_points_of(case):
@@ -92,14 +122,14 @@ def max_points_of(case):
 
 @functools.lru_cache(maxsize=None)
 def mesh_of(name, dtype):
-    v, t = CASES[name]["mesh"]()
+    v, t = case_of(name)["mesh"]()
     return np.ascontiguousarray(v.astype(dtype)), np.ascontiguousarray(t)
 
 
 @functools.lru_cache(maxsize=None)
 def seeds_of(name, dtype):
     """(seed positions (n, 3), their r) in `dtype`; n may be 0."""
-    case = CASES[name]
+    case = case_of(name)
     s = case["seeds"]() if "seeds" in case else np.zeros((0, 3))
     s = np.ascontiguousarray(s.astype(dtype))
     r = np.dtype(dtype).type(case["factor"]) * law_h(case["spacing"], s) if len(s) else np.zeros(0, dtype=dtype)
@@ -110,7 +140,7 @@ def seeds_of(name, dtype):
 
 def library_spacing(wtp, name, dtype):
     """The case's spacing as the package takes it."""
-    sp = CASES[name]["spacing"]
+    sp = case_of(name)["spacing"]
     if sp[0] == "const":
         return sp[1]
     if sp[0] == "bl":
@@ -146,7 +176,7 @@ def inside_of(name, dtype, xyz):
 
 def darts(name, dtype, first, n, seed=SEED):
     """Darts first .. first + n - 1 of the case: (xyz (n, 3) dtype, inside bool, r dtype)."""
-    case = CASES[name]
+    case = case_of(name)
     xyz = positions(name, dtype, first, n, seed)
     r = np.dtype(dtype).type(case["factor"]) * law_h(case["spacing"], xyz)
     return xyz, inside_of(name, dtype, xyz), r
@@ -179,15 +209,16 @@ def serial(xyz, inside, r, sx, sr, max_points, stall_limit):
 
 
 # ---- the model: the batch algorithm -----------------------------------------------------------------------------------
-def batched(xyz, inside, r, sx, sr, max_points, stall_limit, batch):
-    """The same run decided in batches of `batch` darts: (accepted, n_darts, stop_reason, n_inside, rounds_max)."""
+def batched_run(xyz, inside, r, sx, sr, max_points, stall_limit, batch):
+    """The same run decided in batches of `batch` darts (0: the library's schedule): dict(acc, n_darts, stop_reason,
+    n_inside, rounds_max, n_batches)."""
     n = len(xyz)
     acc = np.zeros(0, dtype=np.int64)
-    misses, first, rounds_max, n_in = 0, 0, 0, 0
-    while True:
+    misses, first, rounds_max, n_in, n_batches = 0, 0, 0, 0, 0
+    for size in batch_sizes(batch):
         if first >= n:
             raise ValueError(f"the run needs more than {n} darts")
-        B = min(batch, n - first)
+        B = min(size, n - first)
         bx, br, bi = xyz[first:first + B], r[first:first + B], inside[first:first + B]
         px, pr = np.concatenate([sx, xyz[acc]]), np.concatenate([sr, r[acc]])  # seeds first, then the accepted darts
         live = bi.copy()
@@ -196,23 +227,10 @@ def batched(xyz, inside, r, sx, sr, max_points, stall_limit, batch):
                 live[i] = False
         ids = np.nonzero(live)[0]
         rows, cols = _lower_conflicts(bx[ids], br[ids])
-        st = np.zeros(len(ids), dtype=np.int8)  # 0 undecided, 1 accepted, 2 rejected
-        rounds = 0
-        while True:
-            rounds += 1
-            prev = st[cols]
-            by_acc = np.bincount(rows[prev == 1], minlength=len(ids)) > 0
-            pending = np.bincount(rows[prev == 0], minlength=len(ids)) > 0
-            und = st == 0
-            st[und & by_acc] = 2
-            st[und & ~by_acc & ~pending] = 1
-            if not (st == 0).any():
-                break
-            if rounds > B:
-                raise AssertionError("a batch needs at most as many rounds as it has darts")
-        rounds_max = max(rounds_max, rounds)
+        taken_by_rounds, rounds = jacobi_rounds(rows, cols, len(ids), B)
+        n_batches, rounds_max = n_batches + 1, max(rounds_max, rounds)
         flag = np.zeros(B, dtype=bool)
-        flag[ids[st == 1]] = True
+        flag[ids[taken_by_rounds]] = True
         taken, new, reason = B, [], 0
         for i in range(B + 1):  # the stop scan, position B included; the counts it carries are of accepted darts alone
             if len(acc) + len(new) >= max_points:
@@ -231,15 +249,32 @@ def batched(xyz, inside, r, sx, sr, max_points, stall_limit, batch):
         n_in += int(bi[:taken].sum())
         acc = np.concatenate([acc, np.array(new, dtype=np.int64)])
         if reason:
-            return acc, first + taken, reason, n_in, rounds_max
+            return dict(acc=acc, n_darts=first + taken, stop_reason=reason, n_inside=n_in, rounds_max=rounds_max,
+                        n_batches=n_batches)
         first += B
+
+
+def batched(xyz, inside, r, sx, sr, max_points, stall_limit, batch):
+    """batched_run() as (accepted, n_darts, stop_reason, n_inside, rounds_max)."""
+    b = batched_run(xyz, inside, r, sx, sr, max_points, stall_limit, batch)
+    return b["acc"], b["n_darts"], b["stop_reason"], b["n_inside"], b["rounds_max"]
+
+
+@functools.lru_cache(maxsize=None)
+def needle_darts(dtype):
+    """The first 3 * 2^20 darts of the needle cases (they share mesh, spacing and stream), computed once."""
+    out = darts("needle_clamp", dtype, 0, 3 << 20)
+    for a in out:
+        a.setflags(write=False)
+    return out
 
 
 @functools.lru_cache(maxsize=None)
 def model_run(name, dtype):
     """(xyz, inside, r of the case's horizon of darts, accepted, n_darts, stop_reason, n_inside) by serial(), once."""
-    case = CASES[name]
-    xyz, inside, r = darts(name, dtype, 0, case["horizon"])
+    case = case_of(name)
+    xyz, inside, r = (a[:case["horizon"]] for a in needle_darts(dtype)) if case["mesh"] is needle else \
+        darts(name, dtype, 0, case["horizon"])
     sx, sr = seeds_of(name, dtype)
     acc, n_darts, reason, n_in = serial(xyz, inside, r, sx, sr, max_points_of(case), case["stall_limit"])
     for a in (xyz, inside, r, acc):
