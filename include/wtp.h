@@ -375,7 +375,7 @@ int wtp_mesh_sample_darts(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double 
  * depend on batch or on arrival order and uses no floating-point atomics: two calls return the same bits, and a smaller
  * max_points returns a prefix.  A run that ends with no point returns WTP_OK with n_points = 0.
  *   bbox_volume n_inside / n_darts is the run's own estimate of the domain's volume.  The stream is uniform over the box:
- * there is no thinning by h, no node octree, no max_growth limiter and no 2-D.
+ * there is no thinning by h, no node octree and no max_growth limiter.  The 2-D fill is wtp_loops_fill below.
  *   WTP_ERR_ARG: a spacing value that is not finite and > 0 at a seed (naming the seed) or at an inside dart the run takes
  * (naming the smallest such dart; such a value at any other dart is no error); a seed coordinate that is not finite;
  * n_seeds < 0, or seeds NULL with n_seeds > 0; and every row of wtp_mesh_sample: factor, stall_limit, max_points, seed,
@@ -466,6 +466,86 @@ int wtp_mesh_front_get_dev(wtp_ctx* ctx, void* d_xyz_out, void* d_h_out);
 int wtp_mesh_front_candidates(wtp_ctx* ctx, const wtp_spacing_desc* spacing, uint64_t seed, const void* parents_xyz,
                               int64_t n_parents, int64_t first_parent, int64_t n, void* xyz_out, uint8_t* inside_out,
                               void* r_out);
+
+/* ---- boundary-loop geometry index of a 2-D domain ---------------------------------------------------
+ * Replaces SegmentIndex(T, loops) + the SegmentQuadtree queries (src/octree/segment_quadtree.jl:115-238 and the queries
+ * behind isinside): the 2-D twin of wtp_mesh_set / wtp_mesh_query.  xy: nv x 2 of dtype (the index's machine type T);
+ * loop_start: n_loops + 1 offsets, loop l being rows [loop_start[l], loop_start[l + 1]) in order around the loop, either
+ * orientation, explicitly closed (last vertex = first) or not.  One index per context, replaced by the next call.  The
+ * host build, in T, term by term, no contraction:
+ *   Dedup, per loop: tol = max(8 eps(T) diag, floatmin(T)), diag = sqrt(e_x^2 + e_y^2) of the loop's own bounding-box
+ * extent e; a vertex with sqrt(dx^2 + dy^2) <= tol from the last kept one is dropped, then trailing vertices within tol of
+ * the first.
+ *   Validate: the shoelace area centred on the loop's first vertex o, sa = (sum over i in loop order of
+ * (a_x b_y - b_x a_y), a = v_i - o, b = v_{i+1} - o) / 2; |sa| < max(T(1e-10) e_x e_y, 4 (T(n) eps(T)) (e_x^2 + e_y^2)) over the
+ * cleaned loop's extent is WTP_ERR_ARG, as are fewer than 3 vertices before or after the dedup (both naming the loop),
+ * n_loops < 1, a coordinate that is not finite and offsets that do not run upward from 0 to nv.
+ *   Orient: depth = the number of OTHER cleaned loops that contain the loop's first vertex p by the even-odd crossing
+ * rule (an edge a -> b with (a_y > p_y) != (b_y > p_y) crosses when a_x + ((p_y - a_y) / (b_y - a_y)) (b_x - a_x) > p_x); even
+ * depth wants sa > 0 (counter-clockwise: an outer boundary), odd depth sa < 0 (a hole); a loop that disagrees is reversed.
+ *   Segments: segment i of the concatenated oriented loops runs from vertex i to the next vertex of its loop, cyclically;
+ * its normal is (d_y, -d_x) / sqrt(d_x^2 + d_y^2), out of the domain; a vertex's pseudonormal is the sum of its two segments'
+ * normals.  The box is {min, max} over all vertices, a flat axis widened by max(100 eps(T), T(1e-10)) either way.
+ * wtp_loops_set and wtp_loops_clear void a resident sample, fill or front, as wtp_mesh_set does.  */
+int wtp_loops_set(wtp_ctx* ctx, const void* xy, int64_t nv, const int64_t* loop_start, int64_t n_loops, int dtype);
+int wtp_loops_clear(wtp_ctx* ctx);
+/* {min xy, max xy} as doubles and the number of segments; either may be NULL.  */
+int wtp_loops_bounds(wtp_ctx* ctx, double bbox_out[4], int64_t* n_segments_out);
+/* Per query point p (host array n x 2 of dtype, converted once to T, results converted back); every output may be NULL.
+ * DEFINED as the brute-force minimum over the segments, in T, no contraction.  Per segment (a, b): ab = b - a,
+ * den = ab_x^2 + ab_y^2, t = ((p - a)_x ab_x + (p - a)_y ab_y) / den; t <= 0: cp = a (feature: vertex a); t >= 1: cp = b
+ * (vertex b); else cp = a + t ab per component (the segment itself); dv = p - cp, d2 = dv_x^2 + dv_y^2.  The nearest segment
+ * is the smallest (d2, segment index) (the reference keeps whichever its traversal meets first: unpinned).  With n the
+ * feature's normal (the segment's, or the vertex's pseudonormal), s = dv_x n_x + dv_y n_y:
+ *   sd_out       +sqrt(d2) for s > 0, 0 for s == 0, -sqrt(d2) for s < 0: negative inside
+ *   seg_out      the nearest segment, 0-based
+ *   closest_out  n x 2, cp of that segment
+ *   inside_out   p inside the box (no coordinate below lo or above hi) and sd < 0
+ * WTP_ERR_ARG: a query coordinate that is not finite (checked on the host).  WTP_ERR_STATE: no index set.  */
+int wtp_loops_query(wtp_ctx* ctx, const void* xy, int64_t n, int dtype, void* sd_out, int32_t* seg_out, void* closest_out,
+                    uint8_t* inside_out);
+
+/* ---- graded Poisson-disk fill of a 2-D domain's area -----------------------------------------------
+ * Replaces the point placement of discretize(bnd2d, spacing) (_generate_bridson with N = 2,
+ * src/discretization/algorithms/octree.jl:816-902): wtp_mesh_fill's contract with the z terms removed.  All arithmetic
+ * is in the index's type T, no contraction:
+ *   Dart j = 0, 1, ... (64-bit) of seed s < 2^24: w_a = splitmix64((s << 40) + 3 j + a), u_a = T(float(w_a >> 40) 2^-24),
+ * a = 0, 1 (point j of wtp_gen_uniform_dev's dim-2 stream, which keeps the stride of 3), position c_a = lo_a + u_a (hi_a - lo_a)
+ * with {lo, hi} the index's box (wtp_loops_bounds), in T.
+ *   r = T(factor) h(c), the spacing law evaluated at (x, y) in T against boundary_xyz of n_boundary x 2.  Kinds: CONSTANT,
+ * LOGLIKE, BOUNDARY_LAYER.
+ *   A dart is inside iff wtp_loops_query's inside flag holds for c.  Only an inside dart is a candidate; the spacing value
+ * of a dart that is not inside is never looked at.
+ *   Points p and q conflict when (dx^2 + dy^2) < m m, m = min(r_p, r_q).
+ *   Seeds: n_seeds points (host, n_seeds x 2 of T; NULL / 0 for none), r = T(factor) h(seed) under the same law.  They
+ * occupy space from the start, are never tested against each other, are not returned and may lie on or outside the box.
+ *   Run.  Darts are taken in order.  Before each dart the run ends if max_points darts have been accepted (stop_reason 2)
+ * or the last stall_limit darts were all rejected (stop_reason 1); n_darts counts the darts taken and n_inside those of
+ * them that were inside.  A dart is accepted iff it is a candidate and conflicts with no seed and no earlier accepted dart;
+ * any other dart is a miss, one outside the domain included.  The result is the accepted darts in dart order; it does not
+ * depend on batch or on arrival order and uses no floating-point atomics: two calls return the same bits, and a smaller
+ * max_points returns a prefix.  A run that ends with no point returns WTP_OK with n_points = 0.
+ *   info is a wtp_fill_info whose bbox_volume is the box's AREA: bbox_volume n_inside / n_darts is the run's own estimate
+ * of the domain's area.  No thinning by h, no per-leaf placement, no node quadtree, no max_growth limiter.
+ *   WTP_ERR_ARG: the rows of wtp_mesh_fill (a bad spacing value at a seed or at an inside dart the run takes, a seed
+ * coordinate that is not finite, n_seeds, factor, stall_limit, max_points, seed, batch, kind WTP_SPACING_PER_POINT) but
+ * for the mesh's area.  WTP_ERR_STATE: no loops set; wtp_loops_fill_get* without a resident area fill; another boundary's
+ * law while a relax session evaluates its own.  WTP_ERR_INTERNAL as for wtp_mesh_sample.  The dtype is the index's.
+ *   State.  The area fill shares the samplers' device buffers: once its arguments have passed it voids a resident sample,
+ * fill or front, and each of those voids it; the wrong *_get* is WTP_ERR_STATE.  wtp_loops_set and wtp_loops_clear void
+ * whatever is resident.  */
+int wtp_loops_fill(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, const void* seeds, int64_t n_seeds,
+                   int64_t max_points, int64_t stall_limit, uint64_t seed, int64_t batch, wtp_fill_info* info);
+/* n_points rows (xy_out n x 2 and r_out of the index's dtype); every output may be NULL.  dart_out: the dart index each
+ * point came from.  */
+int wtp_loops_fill_get(wtp_ctx* ctx, void* xy_out, void* r_out, int64_t* dart_out);
+/* The same into device memory.  */
+int wtp_loops_fill_get_dev(wtp_ctx* ctx, void* d_xy_out, void* d_r_out);
+/* Read-out, no acceptance: darts first .. first + n - 1 as the rule above makes them (host outputs, may be NULL): xy_out
+ * n x 2, inside_out one byte per dart, r as computed for every dart.  Leaves a resident result of the index's dtype
+ * untouched; one of the other dtype (a mesh's, where mesh and loops differ in type) is voided, for the buffers change type.  */
+int wtp_loops_fill_darts(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, uint64_t seed, int64_t first,
+                         int64_t n, void* xy_out, uint8_t* inside_out, void* r_out);
 
 /* ---- consumers of the k-NN rows ------------------------------------
  * Replaces compute_normals(points; k) / update_normals! (src/normals.jl:15-69): per point the

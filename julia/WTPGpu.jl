@@ -150,6 +150,44 @@ function fill_volume(sd::SpacingDesc, seeds, ::Type{T}; factor = 0.75, max_point
     return vol, rs, info
 end
 
+# ---- the 2-D geometry index (src/octree/segment_quadtree.jl) and the 2-D Bridson placement on the device ----------------
+# (include/wtp.h: wtp_loops_set, wtp_loops_query, wtp_loops_fill)
+# loops: a vector of loops, each a Vector{SVector{2,T}} in order around the loop (what SegmentIndex(T, loops, unit) takes)
+function loops_set(loops::Vector{Vector{SVector{2, T}}}) where {T}
+    xy = reduce(vcat, loops); start = Int64.(cumsum([0; length.(loops)]))
+    check(context(), ccall((:wtp_loops_set, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Cint),
+        context(), xy, length(xy), start, length(loops), dtype(T)))
+    return nothing
+end
+
+# isinside(p, quadtree) for a vector of SVector{2,T}
+function loops_inside(xs::Vector{SVector{2, T}}) where {T}
+    inside = Vector{UInt8}(undef, length(xs))
+    check(context(), ccall((:wtp_loops_query, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Ptr{Int32}, Ptr{Cvoid}, Ptr{UInt8}),
+        context(), xs, length(xs), dtype(T), C_NULL, C_NULL, C_NULL, inside))
+    return inside .!= 0
+end
+
+# sd: the SpacingDesc of a ConstantSpacing, LogLike or BoundaryLayerSpacing over 2-D boundary points; seeds: the
+# boundary points (may be empty), of the loops' eltype T.  Returns (volume points as SVector{2,T}, their r, info);
+# info.bbox_volume is the area of the loops' box.
+function fill_area(sd::SpacingDesc, seeds, ::Type{T}; factor = 0.75, max_points::Int = 10_000_000, stall_limit::Int = 2000,
+                   seed::Integer = 0) where {T}
+    xs = isempty(seeds) ? SVector{2, T}[] : raw(seeds)
+    info = FillInfo()
+    check(context(), ccall((:wtp_loops_fill, lib), Cint,
+        (Ptr{Cvoid}, Ref{SpacingDesc}, Float64, Ptr{Cvoid}, Int64, Int64, Int64, UInt64, Int64, Ref{FillInfo}),
+        context(), sd, Float64(factor), isempty(xs) ? C_NULL : xs, length(xs), max_points, stall_limit, UInt64(seed), 0, info))
+    n = info.n_points
+    vol = Vector{SVector{2, T}}(undef, n); rs = Vector{T}(undef, n)
+    check(context(), ccall((:wtp_loops_fill_get, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}),
+        context(), vol, rs, C_NULL))
+    info.stop_reason == 2 &&
+        @warn "Bridson front truncated by max_points before saturation — parts of the domain may be unfilled" max_points
+    return vol, rs, info
+end
+
 # ---- src/normals.jl:75-161 and src/surface_operations.jl:58-94: the graph part on the device ------------------------
 # (include/wtp.h: wtp_orient_normals, wtp_normal_components)
 mutable struct NormalGraphInfo

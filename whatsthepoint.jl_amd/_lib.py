@@ -86,7 +86,7 @@ class SampleInfo(C.Structure):
 
 
 class FillInfo(C.Structure):
-    """wtp_fill_info: what wtp_mesh_fill reports about a run."""
+    """wtp_fill_info: what wtp_mesh_fill and wtp_loops_fill report about a run."""
     _fields_ = [("n_points", C.c_int64), ("n_darts", C.c_int64), ("n_inside", C.c_int64), ("n_seeds", C.c_int64),
                 ("batch", C.c_int64), ("stop_reason", C.c_int32), ("n_batches", C.c_int32), ("rounds_max", C.c_int32),
                 ("host_syncs", C.c_int32), ("bbox_volume", C.c_double), ("r_min", C.c_double), ("r_max", C.c_double)]
@@ -161,6 +161,14 @@ SIGNATURES = {
     "wtp_mesh_front_get": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "wtp_mesh_front_get_dev": (_i, [_vp, _vp, _vp]),
     "wtp_mesh_front_candidates": (_i, [_vp, C.POINTER(SpacingDesc), C.c_uint64, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "wtp_loops_set": (_i, [_vp, _vp, _i64, _vp, _i64, _i]),
+    "wtp_loops_clear": (_i, [_vp]),
+    "wtp_loops_bounds": (_i, [_vp, _vp, C.POINTER(_i64)]),
+    "wtp_loops_query": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
+    "wtp_loops_fill": (_i, [_vp, C.POINTER(SpacingDesc), _d, _vp, _i64, _i64, _i64, C.c_uint64, _i64, C.POINTER(FillInfo)]),
+    "wtp_loops_fill_get": (_i, [_vp, _vp, _vp, _vp]),
+    "wtp_loops_fill_get_dev": (_i, [_vp, _vp, _vp]),
+    "wtp_loops_fill_darts": (_i, [_vp, C.POINTER(SpacingDesc), _d, C.c_uint64, _i64, _i64, _vp, _vp, _vp]),
     "wtp_relax_set_wall": (_i, [_vp, _i64, _d]),
     "wtp_relax_get_wall": (_i, [_vp, _vp, _vp, _vp, _i]),
     "wtp_relax_set_wall_flags": (_i, [_vp, _vp, _vp]),

@@ -364,11 +364,30 @@ struct MeshState {
     double total_area = 0;         // cum[nt - 1]
 };
 
+// closed boundary loops of a 2-D domain (wtp_loops.hip): search-tree nodes over the oriented segments, with the feature
+// normals the sign needs in every node
+struct LoopsState {
+    DevBuf nodes, io;
+    int64_t ns = 0;                        // segments (= vertices of the cleaned loops); 0: no index
+    int dtype = -1;
+    double bbox[4] = {0, 0, 0, 0};         // {min xy, max xy} (_compute_bbox_raw_2d)
+    double scale = 0;                      // largest |coordinate| of the box
+};
+
+// What a sampler run needs to know of its domain, passed down from the entry point: the box the cell map lies over (and
+// the fill's darts are drawn from), the index's dtype, its dimension (rows are {x, y, z, r} either way; dim 2 keeps
+// z = 0 and a box whose third axis is [0, 0]) and which inside test a fill launches.
+struct SampleDomain {
+    double lo[3], hi[3];
+    int dtype, dim;
+    bool loops;                            // launch_loops_inside instead of launch_mesh_inside
+};
+
 // Poisson-disk surface sampling (wtp_sample.hip; its streams: wtp_sample_streams.hip): the accepted samples and their cell
 // table stay on the device between wtp_mesh_sample and the wtp_mesh_sample_get* calls; the batch buffers are reused by
 // every batch and by the dart read-out.  wtp_mesh_fill and wtp_mesh_front run in the same buffers (their seeds at the
 // front of the accepted array), so one result is resident at a time.
-enum class SampleKind { none, sample, fill, front };
+enum class SampleKind { none, sample, fill, front, area };
 struct SampleState {
     SampleKind kind = SampleKind::none; // the run whose result of the current mesh is resident; fill's and front's lie
                                    // behind n_seeds seed rows, and front's `dart` holds candidate indices
@@ -540,6 +559,7 @@ struct wtp_ctx {
     wtp::DevBuf diag;          // diagnostic builds only
     wtp::DevBuf ins_in, ins_elems, ins_partial, ins_out; // isinside filter
     wtp::MeshState mesh;
+    wtp::LoopsState loops;
     wtp::SampleState sample;
     wtp::DevBuf sp_hint;       // variable spacings: nearest tree node of each snapshot point at the last sweep
     wtp::KdTree kd;
@@ -716,21 +736,28 @@ constexpr int kSmThreads = 256;
 inline int sm_stride_grid(int64_t n) { return grid_for(n, kSmThreads, 8192); }
 template <typename T> int ensure_batch(wtp_ctx* ctx, int64_t B);
 template <typename T> int sample_unpack(wtp_ctx* ctx, const void* pts, int64_t n, T* d_xyz, T* d_r);
+// the first two of every `stride` values of src into xy (n x 2): Pt rows (stride 4) or the batch's xyz (stride 3)
+template <typename T> int sample_unpack_xy(wtp_ctx* ctx, const T* src, int stride, int64_t n, T* d_xy);
 // Of wtp_sample_streams.hip: a batch of darts or candidates, the seeds, the front's own-h pass, the streams' read-outs.
 template <typename T>
-int enqueue_darts(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, uint64_t seed, int64_t first, int64_t n, bool fill);
+int enqueue_darts(wtp_ctx* ctx, const SampleDomain& dom, const wtp_spacing_desc* sp, double factor, uint64_t seed, int64_t first,
+                  int64_t n, bool fill);
 template <typename T>
 int enqueue_candidates(wtp_ctx* ctx, uint64_t seed, const Pt<T>* parents, int64_t par0, int64_t first, int64_t B, int per);
-template <typename T> int fill_seeds(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, const T* seeds, int64_t ns);
+template <typename T>
+int fill_seeds(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, const T* seeds, int64_t ns, int dim);
 template <typename T> int front_own_h(wtp_ctx* ctx, const wtp_spacing_desc* sp, int64_t n, int64_t n_new);
 template <typename T>
-int sample_darts(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, uint64_t seed, int64_t first, int64_t n, bool fill,
-                 T* xyz_out, int32_t* tri_out, uint8_t* inside_out, T* r_out);
+int sample_darts(wtp_ctx* ctx, const SampleDomain& dom, const wtp_spacing_desc* sp, double factor, uint64_t seed, int64_t first,
+                 int64_t n, bool fill, T* xyz_out, int32_t* tri_out, uint8_t* inside_out, T* r_out);
 template <typename T>
 int front_candidates(wtp_ctx* ctx, const wtp_spacing_desc* sp, uint64_t seed, const T* parents, int64_t np, int64_t first_parent,
                      int per, T* xyz_out, uint8_t* inside_out, T* r_out);
 // wtp_mesh_query's inside flag for n device points of the mesh's own type (wtp_mesh.hip): the domain test of wtp_mesh_fill
 template <typename T> int launch_mesh_inside(wtp_ctx* ctx, const T* d_xyz, int64_t n, uint8_t* d_inside);
+// wtp_loops_query's inside flag for n device rows of 3 columns (z ignored) of the index's own type (wtp_loops.hip): the
+// domain test of wtp_loops_fill
+template <typename T> int launch_loops_inside(wtp_ctx* ctx, const T* d_xyz, int64_t n, uint8_t* d_inside);
 // the mesh's inside/outside class grid with cells of about `cell` (kept if one about as fine exists), and the number of
 // cells such a grid has: one exact test each, which launch_mesh_inside then saves every point of a one-sided cell
 int mesh_ensure_classes(wtp_ctx* ctx, double cell);

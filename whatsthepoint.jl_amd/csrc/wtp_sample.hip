@@ -415,6 +415,14 @@ __global__ void sample_unpack_kernel(const Pt<T>* __restrict__ pts, int64_t n, T
     }
 }
 
+// the first two of every `stride` values: the area fill's read-back
+template <typename T>
+__global__ void sample_unpack_xy_kernel(const T* __restrict__ src, int stride, int64_t n, T* __restrict__ xy) {
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step)
+        xy[2 * i] = src[stride * i], xy[2 * i + 1] = src[stride * i + 1];
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------------
 void sample_invalidate(wtp_ctx* ctx) {
     ctx->sample.kind = SampleKind::none;
@@ -478,8 +486,10 @@ static int grow_keep(wtp_ctx* ctx, DevBuf& b, size_t keep, size_t bytes) {
 
 static int sm_grid(int64_t n) { return grid_for(n, kSmThreads, 1 << 20); }
 
-static int check_sample_args(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, uint64_t seed) {
-    if (ctx->mesh.nt < 1) return fail(ctx, WTP_ERR_STATE, "no mesh: call wtp_mesh_set first");
+// loops: a run over the boundary loops of wtp_loops_set instead of the mesh
+static int check_sample_args(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, uint64_t seed, bool loops = false) {
+    if (loops && ctx->loops.ns < 1) return fail(ctx, WTP_ERR_STATE, "no loops: call wtp_loops_set first");
+    if (!loops && ctx->mesh.nt < 1) return fail(ctx, WTP_ERR_STATE, "no mesh: call wtp_mesh_set first");
     if (!sp) return fail(ctx, WTP_ERR_ARG, "spacing is NULL");
     if (!(factor > 0) || !std::isfinite(factor)) return fail(ctx, WTP_ERR_ARG, "factor must be positive");
     if (seed >= (1ull << 24)) return fail(ctx, WTP_ERR_ARG, "seed must be below 2^24 (the stream's key layout)");
@@ -490,7 +500,7 @@ static int check_sample_args(wtp_ctx* ctx, const wtp_spacing_desc* sp, double fa
         const int rc = check_spacing_law(ctx, sp);
         if (rc) return rc;
     }
-    if (!(ctx->mesh.total_area > 0) || !std::isfinite(ctx->mesh.total_area))
+    if (!loops && (!(ctx->mesh.total_area > 0) || !std::isfinite(ctx->mesh.total_area)))
         return fail(ctx, WTP_ERR_ARG, "mesh has zero surface area");
     return WTP_OK;
 }
@@ -521,7 +531,7 @@ template <typename T> static int ensure_rows(wtp_ctx* ctx, int64_t keep, int64_t
 // only), cells over the mesh's box; the n_acc rows the accepted array already holds (seeds) enter its table now that
 // cells exist.  One host read.
 template <typename T>
-static int first_batch_map(wtp_ctx* ctx, int64_t B, int64_t n_acc, CellMap<T>* map_out, double* cell_edge) {
+static int first_batch_map(wtp_ctx* ctx, const SampleDomain& dom, int64_t B, int64_t n_acc, CellMap<T>* map_out, double* cell_edge) {
     SampleState& S = ctx->sample;
     SampleCtl* d_ctl = (SampleCtl*)S.ctl.p;
     SampleCtl* pin = (SampleCtl*)ctx->host_pinned;
@@ -531,7 +541,7 @@ static int first_batch_map(wtp_ctx* ctx, int64_t B, int64_t n_acc, CellMap<T>* m
     WTP_HIP(ctx, hipMemcpyAsync(pin, d_ctl, sizeof(SampleCtl), hipMemcpyDeviceToHost, ctx->stream));
     if ((rc = sync(ctx))) return rc;
     double ext = 0;
-    for (int a = 0; a < 3; ++a) ext = std::max(ext, ctx->mesh.bbox[3 + a] - ctx->mesh.bbox[a]);
+    for (int a = 0; a < 3; ++a) ext = std::max(ext, dom.hi[a] - dom.lo[a]);
     double c = ext;
     if (pin->rmin != kEmpty)
         c = std::sqrt(__builtin_bit_cast(double, pin->rmin) * __builtin_bit_cast(double, pin->rmax));
@@ -539,8 +549,8 @@ static int first_batch_map(wtp_ctx* ctx, int64_t B, int64_t n_acc, CellMap<T>* m
     if (!(c > 0) || !std::isfinite(c)) c = 1;
     CellMap<T> map{};
     for (int a = 0; a < 3; ++a) {
-        map.org[a] = (T)ctx->mesh.bbox[a];
-        map.nc[a] = (int32_t)std::min(1048575.0, std::floor((ctx->mesh.bbox[3 + a] - ctx->mesh.bbox[a]) / c) + 1);
+        map.org[a] = (T)dom.lo[a];
+        map.nc[a] = (int32_t)std::min(1048575.0, std::floor((dom.hi[a] - dom.lo[a]) / c) + 1);
     }
     map.inv_c = (T)(1.0 / c);
     *map_out = map;
@@ -553,8 +563,25 @@ static int first_batch_map(wtp_ctx* ctx, int64_t B, int64_t n_acc, CellMap<T>* m
     return WTP_OK;
 }
 
+// the two domains a run can have: the mesh of wtp_mesh_set, the boundary loops of wtp_loops_set
+static SampleDomain mesh_domain(const wtp_ctx* ctx) {
+    SampleDomain d{};
+    for (int a = 0; a < 3; ++a) d.lo[a] = ctx->mesh.bbox[a], d.hi[a] = ctx->mesh.bbox[3 + a];
+    d.dtype = ctx->mesh.dtype, d.dim = 3, d.loops = false;
+    return d;
+}
+
+static SampleDomain loops_domain(const wtp_ctx* ctx) {
+    SampleDomain d{};
+    for (int a = 0; a < 2; ++a) d.lo[a] = ctx->loops.bbox[a], d.hi[a] = ctx->loops.bbox[2 + a];
+    d.lo[2] = d.hi[2] = 0; // every row keeps z = 0: one layer of cells, and dz * dz adds an exact zero to every distance
+    d.dtype = ctx->loops.dtype, d.dim = 2, d.loops = true;
+    return d;
+}
+
 // what a run carries from batch to batch
 template <typename T> struct Run {
+    SampleDomain dom{};        // the run's domain, as its entry point described it
     CellMap<T> map{};          // made by the first batch (first_batch_map)
     bool have_map = false, classes = false;
     double cell_edge = 0;
@@ -583,7 +610,7 @@ template <typename T, bool kFront> static int decide_batch(wtp_ctx* ctx, Run<T>&
     SampleCtl* pin = (SampleCtl*)ctx->host_pinned;
     int rc;
     if (!run.have_map) {
-        if ((rc = first_batch_map<T>(ctx, a.B, run.n, &run.map, &run.cell_edge))) return rc;
+        if ((rc = first_batch_map<T>(ctx, run.dom, a.B, run.n, &run.map, &run.cell_edge))) return rc;
         run.have_map = true;
     }
     const CellMap<T>& map = run.map;
@@ -641,18 +668,19 @@ struct RunInfo {
 };
 
 // Run begin, up to the control block's upload: nothing is resident any more, the law's tree, batch buffers for B darts
-// of the mesh's type, and the ns seeds (r = T(factor) h, every one checked) in front of an accepted array with room for
+// of the domain's type, and the ns seeds (r = T(factor) h, every one checked) in front of an accepted array with room for
 // `room` more rows.
 template <typename T>
-static int run_begin(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, const T* seeds, int64_t ns, int64_t B, int64_t room,
-                     Run<T>* run) {
+static int run_begin(wtp_ctx* ctx, const SampleDomain& dom, const wtp_spacing_desc* sp, double factor, const T* seeds, int64_t ns,
+                     int64_t B, int64_t room, Run<T>* run) {
     SampleState& S = ctx->sample;
     const int dtype = sizeof(T) == 4 ? WTP_F32 : WTP_F64;
     int rc;
+    run->dom = dom;
     run->syncs0 = ctx->n_syncs;
     run->n = run->ns = ns;
     sample_invalidate(ctx);
-    if (spacing_on_device(sp->kind) && (rc = ensure_kd(ctx, sp, 3, dtype))) return rc;
+    if (spacing_on_device(sp->kind) && (rc = ensure_kd(ctx, sp, dom.dim, dtype))) return rc;
     if ((rc = ensure_pinned(ctx, sizeof(SampleCtl)))) return rc;
     if (S.dtype != dtype) S.cap = 0, S.bcap = 0; // the rows have another size
     if ((rc = ensure_batch<T>(ctx, B))) return rc;
@@ -661,7 +689,7 @@ static int run_begin(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, co
         bool replaced = false;
         if (ns + room >= (int64_t(1) << 31) - 1) return fail(ctx, WTP_ERR_ARG, "seeds + batch exceed the int32 index space");
         if ((rc = ensure_rows<T>(ctx, 0, ns + room, &replaced))) return rc;
-        if ((rc = fill_seeds<T>(ctx, sp, factor, seeds, ns))) return rc;
+        if ((rc = fill_seeds<T>(ctx, sp, factor, seeds, ns, dom.dim))) return rc;
     }
     SampleCtl* pin = (SampleCtl*)ctx->host_pinned;
     *pin = SampleCtl{};
@@ -731,22 +759,24 @@ template <typename T> static int run_finish(wtp_ctx* ctx, const Run<T>& run, Sam
     return WTP_OK;
 }
 
-// The run of wtp_mesh_sample (fill = false) or wtp_mesh_fill (fill = true, with ns seeds in the mesh's type): batches of
-// consecutive darts, doubled from kBatchFirst to kBatchMax unless `batch` fixes their size.
+// The run of wtp_mesh_sample (kind sample), wtp_mesh_fill (fill) or wtp_loops_fill (area); the last two over the darts of
+// the domain's box, with ns seeds in the domain's type: batches of consecutive darts, doubled from kBatchFirst to
+// kBatchMax unless `batch` fixes their size.
 template <typename T>
-static int sample_run(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, int64_t max_points, int64_t stall_limit,
-                      uint64_t seed, int64_t batch, bool fill, const T* seeds, int64_t ns, RunInfo* info) {
+static int sample_run(wtp_ctx* ctx, const SampleDomain& dom, const wtp_spacing_desc* sp, double factor, int64_t max_points,
+                      int64_t stall_limit, uint64_t seed, int64_t batch, SampleKind kind, const T* seeds, int64_t ns, RunInfo* info) {
     SampleState& S = ctx->sample;
+    const bool fill = kind != SampleKind::sample;
     Run<T> run;
     int64_t B = batch > 0 ? batch : kBatchFirst, first = 0;
     int rc;
-    if ((rc = run_begin<T>(ctx, sp, factor, seeds, ns, B, B, &run))) return rc;
+    if ((rc = run_begin<T>(ctx, dom, sp, factor, seeds, ns, B, B, &run))) return rc;
     const SampleCtl* pin = (const SampleCtl*)ctx->host_pinned; // decide_batch leaves the last group's control block there
     for (;;) {
         if (run.n + B >= (int64_t(1) << 31) - 1) return fail(ctx, WTP_ERR_ARG, "samples + batch exceed the int32 index space");
         if ((rc = ensure_batch<T>(ctx, B))) return rc;
-        if ((rc = batch_prepare<T>(ctx, run, first, B, fill))) return rc; // only the fill tests darts against the mesh
-        if ((rc = enqueue_darts<T>(ctx, sp, factor, seed, first, B, fill))) return rc;
+        if ((rc = batch_prepare<T>(ctx, run, first, B, fill && !dom.loops))) return rc; // only the fill tests darts against the mesh
+        if ((rc = enqueue_darts<T>(ctx, dom, sp, factor, seed, first, B, fill))) return rc;
         const BatchArgs args{B, run.n, first, ns, max_points, stall_limit, fill ? (const uint8_t*)S.b_in.p : (const uint8_t*)nullptr,
                              fill ? (const int32_t*)nullptr : (const int32_t*)S.b_tri.p, 0, 1};
         if ((rc = decide_batch<T, false>(ctx, run, args))) return rc;
@@ -757,7 +787,7 @@ static int sample_run(wtp_ctx* ctx, const wtp_spacing_desc* sp, double factor, i
         if (batch == 0) B = std::min(2 * B, kBatchMax);
     }
     info->batch = B;
-    return run_finish<T>(ctx, run, fill ? SampleKind::fill : SampleKind::sample, info);
+    return run_finish<T>(ctx, run, kind, info);
 }
 
 // The run of wtp_mesh_front: parents in queue order, batches of whole parents that were in the queue when the batch began.
@@ -785,7 +815,7 @@ static int front_run(wtp_ctx* ctx, const wtp_spacing_desc* sp, int per, const T*
     const int64_t par_max = batch > 0 ? std::min(batch, par_cap) : par_cap;
     int64_t B = std::min(ns, par_max) * per;
     Run<T> run;
-    if ((rc = run_begin<T>(ctx, sp, 1.0, seeds, ns, pow2_at_least(std::max(B, kBatchFirst)), std::min(B, max_points), &run)))
+    if ((rc = run_begin<T>(ctx, mesh_domain(ctx), sp, 1.0, seeds, ns, pow2_at_least(std::max(B, kBatchFirst)), std::min(B, max_points), &run)))
         return rc; // (factor 1: a seed's w = T(1) h = h)
     SampleCtl* pin = (SampleCtl*)ctx->host_pinned; // decide_batch leaves the last group's control block there
     int64_t q0 = 0; // parents expanded so far; run.n is the queue's length
@@ -829,9 +859,16 @@ template <typename T> int sample_unpack(wtp_ctx* ctx, const void* pts, int64_t n
     return WTP_OK;
 }
 
-#define INST(T)                                            \
-    template int ensure_batch<T>(wtp_ctx*, int64_t);       \
-    template int sample_unpack<T>(wtp_ctx*, const void*, int64_t, T*, T*);
+template <typename T> int sample_unpack_xy(wtp_ctx* ctx, const T* src, int stride, int64_t n, T* d_xy) {
+    hipLaunchKernelGGL(sample_unpack_xy_kernel<T>, dim3(sm_stride_grid(n)), dim3(kSmThreads), 0, ctx->stream, src, stride, n, d_xy);
+    WTP_HIP(ctx, hipGetLastError());
+    return WTP_OK;
+}
+
+#define INST(T)                                                            \
+    template int ensure_batch<T>(wtp_ctx*, int64_t);                       \
+    template int sample_unpack<T>(wtp_ctx*, const void*, int64_t, T*, T*); \
+    template int sample_unpack_xy<T>(wtp_ctx*, const T*, int, int64_t, T*);
 INST(float)
 INST(double)
 #undef INST
@@ -852,8 +889,8 @@ static int check_size_args(wtp_ctx* ctx, int64_t max_points, int64_t batch, cons
 
 // the argument rows wtp_mesh_sample and wtp_mesh_fill share
 static int check_run_args(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, int64_t max_points, int64_t stall_limit,
-                          uint64_t seed, int64_t batch, const void* seeds, int64_t n_seeds) {
-    const int rc = check_sample_args(ctx, spacing, factor, seed);
+                          uint64_t seed, int64_t batch, const void* seeds, int64_t n_seeds, bool loops = false) {
+    const int rc = check_sample_args(ctx, spacing, factor, seed, loops);
     if (rc) return rc;
     if (stall_limit < 1) return fail(ctx, WTP_ERR_ARG, "stall_limit must be positive");
     return check_size_args(ctx, max_points, batch, seeds, n_seeds);
@@ -868,7 +905,8 @@ WTP_API int wtp_mesh_sample(wtp_ctx* ctx, const wtp_spacing_desc* spacing, doubl
     RunInfo ri{};
     rc = by_dtype(ctx->mesh.dtype, [&](auto t) {
         using T = decltype(t);
-        return sample_run<T>(ctx, spacing, factor, max_points, stall_limit, seed, batch, false, (const T*)nullptr, 0, &ri);
+        return sample_run<T>(ctx, mesh_domain(ctx), spacing, factor, max_points, stall_limit, seed, batch, SampleKind::sample,
+                             (const T*)nullptr, 0, &ri);
     });
     if (rc || !info) return rc;
     info->n_points = ri.n_points, info->n_darts = ri.n_darts, info->batch = ri.batch;
@@ -886,8 +924,8 @@ static int check_resident(wtp_ctx* ctx, SampleKind k, const char* missing) {
 }
 
 // xyz and r of the resident rows behind the seeds, into host arrays (through the context's scratch block) or, dev, into
-// device arrays; either may be absent
-static int rows_out(wtp_ctx* ctx, bool dev, void* xyz_out, void* r_out) {
+// device arrays; either may be absent.  cols = 2: the area fill's xy rows
+static int rows_out(wtp_ctx* ctx, bool dev, void* xyz_out, void* r_out, int cols = 3) {
     SampleState& S = ctx->sample;
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     if (!xyz_out && !r_out) return WTP_OK;
@@ -898,10 +936,13 @@ static int rows_out(wtp_ctx* ctx, bool dev, void* xyz_out, void* r_out) {
     char* d_r = dev ? (char*)r_out : d_xyz + ts * 3 * n;
     rc = by_dtype(S.dtype, [&](auto t) {
         using T = decltype(t);
-        return sample_unpack<T>(ctx, (const Pt<T>*)S.pts.p + S.n_seeds, S.n, (T*)d_xyz, (T*)d_r);
+        const Pt<T>* rows = (const Pt<T>*)S.pts.p + S.n_seeds;
+        if (cols == 3) return sample_unpack<T>(ctx, rows, S.n, (T*)d_xyz, (T*)d_r);
+        if (d_xyz && S.n > 0 && sample_unpack_xy<T>(ctx, (const T*)rows, 4, S.n, (T*)d_xyz)) return (int)WTP_ERR_HIP;
+        return d_r ? sample_unpack<T>(ctx, rows, S.n, (T*)nullptr, (T*)d_r) : (int)WTP_OK;
     });
     if (rc || dev) return rc;
-    if (xyz_out) WTP_HIP(ctx, hipMemcpyAsync(xyz_out, d_xyz, ts * 3 * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (xyz_out) WTP_HIP(ctx, hipMemcpyAsync(xyz_out, d_xyz, ts * cols * n, hipMemcpyDeviceToHost, ctx->stream));
     if (r_out) WTP_HIP(ctx, hipMemcpyAsync(r_out, d_r, ts * n, hipMemcpyDeviceToHost, ctx->stream));
     return WTP_OK;
 }
@@ -941,7 +982,7 @@ WTP_API int wtp_mesh_sample_darts(wtp_ctx* ctx, const wtp_spacing_desc* spacing,
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     return by_dtype(ctx->mesh.dtype, [&](auto t) {
         using T = decltype(t);
-        return sample_darts<T>(ctx, spacing, factor, seed, first, n, false, (T*)xyz_out, tri_out, nullptr, (T*)r_out);
+        return sample_darts<T>(ctx, mesh_domain(ctx), spacing, factor, seed, first, n, false, (T*)xyz_out, tri_out, nullptr, (T*)r_out);
     });
 }
 
@@ -955,7 +996,8 @@ WTP_API int wtp_mesh_fill(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double 
     RunInfo ri{};
     rc = by_dtype(ctx->mesh.dtype, [&](auto t) {
         using T = decltype(t);
-        return sample_run<T>(ctx, spacing, factor, max_points, stall_limit, seed, batch, true, (const T*)seeds, n_seeds, &ri);
+        return sample_run<T>(ctx, mesh_domain(ctx), spacing, factor, max_points, stall_limit, seed, batch, SampleKind::fill,
+                             (const T*)seeds, n_seeds, &ri);
     });
     if (rc || !info) return rc;
     const double* b = ctx->mesh.bbox;
@@ -992,7 +1034,7 @@ WTP_API int wtp_mesh_fill_darts(wtp_ctx* ctx, const wtp_spacing_desc* spacing, d
     WTP_HIP(ctx, hipSetDevice(ctx->device));
     return by_dtype(ctx->mesh.dtype, [&](auto t) {
         using T = decltype(t);
-        return sample_darts<T>(ctx, spacing, factor, seed, first, n, true, (T*)xyz_out, nullptr, inside_out, (T*)r_out);
+        return sample_darts<T>(ctx, mesh_domain(ctx), spacing, factor, seed, first, n, true, (T*)xyz_out, nullptr, inside_out, (T*)r_out);
     });
 }
 
@@ -1062,5 +1104,60 @@ WTP_API int wtp_mesh_front_candidates(wtp_ctx* ctx, const wtp_spacing_desc* spac
         using T = decltype(t);
         return front_candidates<T>(ctx, spacing, seed, (const T*)parents_xyz, n_parents, first_parent, (int)n, (T*)xyz_out,
                                    inside_out, (T*)r_out);
+    });
+}
+
+// ---- the area fill: wtp_mesh_fill's run over the boundary loops of wtp_loops_set -----------------------
+static const char kNoArea[] = "no area fill: call wtp_loops_fill first";
+
+WTP_API int wtp_loops_fill(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, const void* seeds, int64_t n_seeds,
+                           int64_t max_points, int64_t stall_limit, uint64_t seed, int64_t batch, wtp_fill_info* info) {
+    if (!ctx) return WTP_ERR_ARG;
+    int rc = check_run_args(ctx, spacing, factor, max_points, stall_limit, seed, batch, seeds, n_seeds, true);
+    if (rc) return rc;
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    RunInfo ri{};
+    const SampleDomain dom = loops_domain(ctx);
+    rc = by_dtype(dom.dtype, [&](auto t) {
+        using T = decltype(t);
+        return sample_run<T>(ctx, dom, spacing, factor, max_points, stall_limit, seed, batch, SampleKind::area, (const T*)seeds,
+                             n_seeds, &ri);
+    });
+    if (rc || !info) return rc;
+    info->n_points = ri.n_points, info->n_darts = ri.n_darts, info->n_inside = ri.n_inside, info->n_seeds = n_seeds;
+    info->batch = ri.batch;
+    info->stop_reason = ri.stop_reason;
+    info->n_batches = ri.n_batches, info->rounds_max = ri.rounds_max, info->host_syncs = ri.host_syncs;
+    info->bbox_volume = (dom.hi[0] - dom.lo[0]) * (dom.hi[1] - dom.lo[1]);
+    info->r_min = ri.r_min, info->r_max = ri.r_max;
+    return WTP_OK;
+}
+
+WTP_API int wtp_loops_fill_get(wtp_ctx* ctx, void* xy_out, void* r_out, int64_t* dart_out) {
+    int rc = check_resident(ctx, SampleKind::area, kNoArea);
+    if (rc || (rc = rows_out(ctx, false, xy_out, r_out, 2))) return rc;
+    const SampleState& S = ctx->sample;
+    if (dart_out)
+        WTP_HIP(ctx, hipMemcpyAsync(dart_out, (const int64_t*)S.dart.p + S.n_seeds, 8 * (size_t)S.n, hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
+}
+
+WTP_API int wtp_loops_fill_get_dev(wtp_ctx* ctx, void* d_xy_out, void* d_r_out) {
+    int rc = check_resident(ctx, SampleKind::area, kNoArea);
+    if (rc || (rc = rows_out(ctx, true, d_xy_out, d_r_out, 2))) return rc;
+    return sync(ctx);
+}
+
+WTP_API int wtp_loops_fill_darts(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, uint64_t seed, int64_t first,
+                                 int64_t n, void* xy_out, uint8_t* inside_out, void* r_out) {
+    if (!ctx) return WTP_ERR_ARG;
+    int rc = check_sample_args(ctx, spacing, factor, seed, true);
+    if (rc || (rc = check_dart_range(ctx, first, n))) return rc;
+    if (n == 0) return WTP_OK;
+    WTP_HIP(ctx, hipSetDevice(ctx->device));
+    const SampleDomain dom = loops_domain(ctx);
+    return by_dtype(dom.dtype, [&](auto t) {
+        using T = decltype(t);
+        return sample_darts<T>(ctx, dom, spacing, factor, seed, first, n, true, (T*)xy_out, nullptr, inside_out, (T*)r_out);
     });
 }

@@ -47,6 +47,7 @@ class Context:
         self._h = h
         self.device = device
         self._mesh_key = None   # identity of the mesh resident in this context (octree.py)
+        self._loops_key = None  # (segments, dtype) of the boundary loops resident in this context (quadtree.py)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -490,6 +491,108 @@ class Context:
         L.check(self._h, rc)
         del keep
         return xyz, inside.astype(bool), r
+
+    # ---- boundary-loop index of a 2-D domain (src/octree/segment_quadtree.jl; wtp_loops_set) and its area fill -------
+    def loops_set(self, loops):
+        """loops: a list of (n_l, 2) arrays, each one closed loop in order (either orientation, closed or not); the
+        first one's float32 / float64 dtype is the index's machine type."""
+        loops = [np.asarray(l) for l in loops]
+        if not loops or any(l.ndim != 2 or l.shape[1] != 2 for l in loops):
+            raise L.WtpArgumentError("boundary loops must be a non-empty list of (n, 2) arrays")
+        dt = loops[0].dtype if loops[0].dtype in (np.float32, np.float64) else np.dtype(np.float64)
+        xy = np.ascontiguousarray(np.concatenate(loops, axis=0), dtype=dt)
+        start = np.concatenate([[0], np.cumsum([len(l) for l in loops])]).astype(np.int64)
+        self._loops_key = None
+        self._loops_owner = None
+        L.check(self._h, self._lib.wtp_loops_set(self._h, _vp(xy), len(xy), _vp(start), len(loops), _dtype_code(dt)))
+        self._loops_key = (self.loops_bounds()[2], np.dtype(dt))
+
+    def loops_clear(self):
+        L.check(self._h, self._lib.wtp_loops_clear(self._h))
+        self._loops_key = None
+        self._loops_owner = None
+
+    def loops_bounds(self):
+        """(min xy, max xy, number of segments) of the resident loops."""
+        out = np.empty(4, dtype=np.float64)
+        ns = C.c_int64(0)
+        L.check(self._h, self._lib.wtp_loops_bounds(self._h, _vp(out), C.byref(ns)))
+        return out[:2].copy(), out[2:].copy(), int(ns.value)
+
+    def loops_query(self, pts, want=("sd", "seg", "closest", "inside")):
+        """Nearest-segment queries for (n, 2) points; returns a dict with the requested outputs."""
+        pts = _cloud(pts)
+        if pts.shape[1] != 2:
+            raise L.WtpArgumentError("loop queries are 2-D")
+        n, dt = len(pts), pts.dtype
+        out = {}
+        if "sd" in want:
+            out["sd"] = np.empty(n, dtype=dt)
+        if "seg" in want:
+            out["seg"] = np.empty(n, dtype=np.int32)
+        if "closest" in want:
+            out["closest"] = np.empty((n, 2), dtype=dt)
+        if "inside" in want:
+            out["inside"] = np.zeros(n, dtype=np.uint8)
+        rc = self._lib.wtp_loops_query(self._h, _vp(pts), n, _dtype_code(dt), _vp(out.get("sd")), _vp(out.get("seg")),
+                                       _vp(out.get("closest")), _vp(out.get("inside")))
+        L.check(self._h, rc)
+        if "inside" in out:
+            out["inside"] = out["inside"].astype(bool)
+        return out
+
+    def _loops_dtype(self):
+        return self._loops_key[1] if self._loops_key else np.dtype(np.float64)
+
+    def _area_spacing(self, spacing):
+        if isinstance(spacing, dict):
+            return _law_desc(spacing, self._loops_dtype(), 2)
+        sd = L.SpacingDesc()
+        sd.kind, sd.constant = L.WTP_SPACING_CONSTANT, float(spacing)
+        return sd, None
+
+    def loops_fill(self, spacing, factor: float = 0.75, seeds=None, max_points: int = 10_000_000, stall_limit: int = 2000,
+                   seed: int = 0, batch: int = 0, spacing_desc=None):
+        """wtp_loops_fill on the loops of loops_set: the serial dart thrower over the seeded stream of the loops' box,
+        decided in batches on the device.  seeds: (n, 2) points that occupy space from the start (converted to the
+        index's dtype), or None.  Returns the info dict; the points stay on the device (loops_fill_get)."""
+        sd, keep = (spacing_desc, None) if spacing_desc is not None else self._area_spacing(spacing)
+        s = None
+        if seeds is not None and len(seeds):
+            s = np.ascontiguousarray(seeds, dtype=self._loops_dtype())
+            if s.ndim != 2 or s.shape[1] != 2:
+                raise L.WtpArgumentError("seeds must have shape (n, 2)")
+        info = L.FillInfo()
+        rc = self._lib.wtp_loops_fill(self._h, C.byref(sd), float(factor), _vp(s), 0 if s is None else len(s), int(max_points),
+                                      int(stall_limit), C.c_uint64(int(seed)), int(batch), C.byref(info))
+        L.check(self._h, rc)
+        del keep
+        return _info_dict(info)
+
+    def loops_fill_get(self, n: int, want=("xy", "r", "dart")):
+        """The n = info['n_points'] points of the last loops_fill as a dict of host arrays (index dtype)."""
+        dt = self._loops_dtype()
+        spec = dict(xy=((n, 2), dt), r=(n, dt), dart=(n, np.int64))
+        out = {k: np.empty(sh, dtype=d) for k, (sh, d) in spec.items() if k in want}
+        rc = self._lib.wtp_loops_fill_get(self._h, _vp(out.get("xy")), _vp(out.get("r")), _vp(out.get("dart")))
+        L.check(self._h, rc)
+        return out
+
+    def loops_fill_get_dev(self, d_xy_ptr: int = 0, d_r_ptr: int = 0):
+        """wtp_loops_fill_get_dev: the points into device arrays given as addresses (0 = absent)."""
+        rc = self._lib.wtp_loops_fill_get_dev(self._h, C.c_void_p(d_xy_ptr or None), C.c_void_p(d_r_ptr or None))
+        L.check(self._h, rc)
+
+    def loops_fill_darts(self, spacing, factor: float, seed: int, first: int, n: int):
+        """wtp_loops_fill_darts: darts first .. first + n - 1 as the area fill makes them: (xy, inside, r)."""
+        sd, keep = self._area_spacing(spacing)
+        dt = self._loops_dtype()
+        xy, inside, r = np.empty((n, 2), dtype=dt), np.zeros(n, dtype=np.uint8), np.empty(n, dtype=dt)
+        rc = self._lib.wtp_loops_fill_darts(self._h, C.byref(sd), float(factor), C.c_uint64(int(seed)), int(first), int(n),
+                                            _vp(xy), _vp(inside), _vp(r))
+        L.check(self._h, rc)
+        del keep
+        return xy, inside.astype(bool), r
 
     def set_stream(self, stream_handle=None):
         """Run the library on a caller-owned HIP stream (handle as an int; 0 = the device's default

@@ -8,6 +8,7 @@ polygon validation and error behaviour stay on the host and follow the reference
   2-D  points / PointSurface / PointCloud      winding number over the ordered boundary points
   3-D  PointCloud / PointBoundary              Green's-function sum over (centroid, normal, area)
   3-D  PointSurface                            TypeError (the reference has no such method)
+  SegmentQuadtree / TriangleOctree             the index's own signed-distance test
 """
 from __future__ import annotations
 
@@ -52,6 +53,11 @@ def _test_array(testpoints, dim):
 
 def isinside(testpoints, obj, ctx=None):
     """bool (one point) or bool[n] (an (n, dim) array): is the point inside the closed domain?"""
+    from .octree import TriangleOctree
+    from .quadtree import SegmentQuadtree
+
+    if isinstance(obj, (SegmentQuadtree, TriangleOctree)):  # the geometry indices answer themselves
+        return obj.isinside(testpoints, ctx=ctx)
     ctx = ctx or default_context()
     if isinstance(obj, PointCloud):
         obj = obj.boundary

@@ -118,6 +118,37 @@ def fill_volume(mesh, spacing, *, seeds=None, factor: float = 0.75, max_points: 
     return vol
 
 
+def fill_area(loops, spacing, *, seeds=None, factor: float = 0.75, max_points: int = 10_000_000, stall_limit: int = 2000,
+              seed: int = synth.SEED, batch: int = 0, ctx=None):
+    """Graded Poisson-disk points inside a 2-D domain -> PointVolume of 2-D points: the placement of the reference's
+    default 2-D discretize (Orthtree(bnd; spacing), _generate_bridson with N = 2,
+    src/discretization/algorithms/octree.jl:816-902).
+
+    loops: a SegmentQuadtree, one (n, 2) loop or a list of loops (outer boundaries and holes, by nesting parity).
+    Everything else as for fill_volume, with (n, 2) seeds.  The returned volume carries the run's wtp_fill_info as
+    `fill_info` (with `area_estimate` = bbox_volume * n_inside / n_darts added, bbox_volume being the box's area) and
+    the points' r as `fill_r`."""
+    from .cloud import PointVolume
+    from .quadtree import SegmentQuadtree
+
+    _check_positive(factor=factor, stall_limit=stall_limit, max_points=max_points)
+    law = _sampler_spacing(spacing)
+    tree = loops if isinstance(loops, SegmentQuadtree) else SegmentQuadtree(loops, ctx=ctx)
+    c = tree._resident(ctx)
+    info = c.loops_fill(law, factor, seeds, max_points, stall_limit, int(seed) & 0xFFFFFF, batch)
+    n = int(info["n_points"])
+    if n == 0:
+        raise WtpArgumentError("area fill produced no points — check spacing vs domain size")
+    if info["stop_reason"] == 2:
+        warnings.warn("Area fill truncated by max_points before saturation — parts of the domain may be unfilled "
+                      f"(max_points = {max_points})")
+    got = c.loops_fill_get(n, want=("xy", "r"))
+    info["area_estimate"] = info["bbox_volume"] * info["n_inside"] / info["n_darts"]
+    vol = PointVolume(got["xy"])
+    vol.fill_info, vol.fill_r = info, got["r"]
+    return vol
+
+
 class SlakKosec:
     """SlakKosec(n = 10) (src/discretization/algorithms/slak_kosec.jl:59-67): the advancing front with n candidates per
     expanded point, for discretize(..., alg=SlakKosec(n)).  The mesh is discretize's own argument."""
@@ -165,13 +196,18 @@ def front_volume(mesh, spacing, *, seeds, n: int = 10, max_points: int = 10_000_
 _EXTRAS = {"fill": ("fill_info", "fill_r"), "front": ("front_info", "front_h", "front_parent")}
 
 
-def discretize(boundary, spacing, mesh, *, alg=None, factor: float = None, max_points: int = 10_000_000,
+def discretize(boundary, spacing, mesh=None, *, alg=None, factor: float = None, max_points: int = 10_000_000,
                stall_limit: int = None, seed: int = synth.SEED, ctx=None):
     """discretize(bnd, spacing; alg, max_points) -> PointCloud(boundary, volume); the boundary itself is returned
     unchanged.  alg = None: Orthtree(mesh; spacing, placement = :bridson), the boundary's points being the seeds of
     fill_volume (factor 0.75, stall_limit 2000 unless given).  alg = SlakKosec(n): the advancing front from the boundary's
-    points (front_volume), which has no factor and no stall_limit."""
+    points (front_volume), which has no factor and no stall_limit.
+
+    A 2-D boundary takes the reference's 2-D default, Orthtree(bnd; spacing) (src/discretization/discretization.jl:63):
+    mesh = None indexes the boundary's surfaces as loops (SegmentQuadtree.from_boundary), or mesh is a SegmentQuadtree;
+    the placement is fill_area with the boundary's points as seeds.  2-D has no SlakKosec."""
     from .cloud import PointBoundary, PointCloud
+    from .quadtree import SegmentQuadtree
 
     if alg is not None and not isinstance(alg, SlakKosec):
         raise WtpArgumentError(f"alg must be None or SlakKosec(n), not {type(alg).__name__}")
@@ -180,7 +216,22 @@ def discretize(boundary, spacing, mesh, *, alg=None, factor: float = None, max_p
                                "and ends when no point is left to expand")
     if not isinstance(boundary, PointBoundary):
         boundary = PointBoundary(boundary)
-    if alg is None:
+    dim = boundary.points().shape[1]
+    if dim == 2 and alg is not None:
+        raise WtpArgumentError(f"2D discretization supports the Orthtree fill only (the default: drop `alg`); got {alg!r}")
+    if dim == 2 and mesh is not None and not isinstance(mesh, SegmentQuadtree):
+        raise WtpArgumentError(f"this geometry index is 3D ({type(mesh).__name__}) and cannot fill a 2D boundary — pass "
+                               "mesh=None or SegmentQuadtree.from_boundary(boundary), which indexes the boundary loops")
+    if dim == 3 and isinstance(mesh, SegmentQuadtree):
+        raise WtpArgumentError("this geometry index is 2D (SegmentQuadtree) and cannot fill a 3D boundary — pass the "
+                               "surface mesh or its TriangleOctree")
+    if dim == 3 and mesh is None:
+        raise WtpArgumentError("a 3D boundary needs its surface mesh: pass a TriangleOctree or a (vertices, triangles) pair")
+    if dim == 2:
+        tree = mesh if mesh is not None else SegmentQuadtree.from_boundary(boundary, ctx=ctx)
+        vol = fill_area(tree, spacing, seeds=boundary.points(), factor=0.75 if factor is None else factor,
+                        max_points=max_points, stall_limit=2000 if stall_limit is None else stall_limit, seed=seed, ctx=ctx)
+    elif alg is None:
         vol = fill_volume(mesh, spacing, seeds=boundary.points(), factor=0.75 if factor is None else factor,
                           max_points=max_points, stall_limit=2000 if stall_limit is None else stall_limit, seed=seed,
                           ctx=ctx)
