@@ -547,6 +547,119 @@ int wtp_loops_fill_get_dev(wtp_ctx* ctx, void* d_xy_out, void* d_r_out);
 int wtp_loops_fill_darts(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double factor, uint64_t seed, int64_t first,
                          int64_t n, void* xy_out, uint8_t* inside_out, void* r_out);
 
+/* ---- spacing-driven node octree over the mesh ------------------------------------------------------
+ * Replaces build_node_octree + classify_node_octree (src/octree/spacing_criterion.jl:88-215, src/octree/spatial_octree.jl)
+ * and what the Orthtree algorithm reads off the tree: _estimate_volume_points, _bridson_h_min, _leaf_spacing_field
+ * (src/discretization/algorithms/octree.jl:590-662) and find_leaf.  3-D, over the mesh of wtp_mesh_set, every term in the
+ * mesh's type T, no contraction.  Classes are the reference's: 0 EXTERIOR, 1 BOUNDARY, 2 INTERIOR.
+ *   Root (triangle_octree.jl:391-398) from wtp_mesh_bounds' {lo, hi}: centre = (lo + hi) T(0.5), half = ((hi - lo) T(0.5)) T(1.02),
+ * origin = centre - half, top = centre + half, root_size = the largest of top_a - origin_a; diagonal = sqrt((e_x^2 + e_y^2) + e_z^2)
+ * with e_a = (origin_a + root_size) - origin_a; absolute_min = diagonal T(node_min_ratio).
+ *   Box (depth d, cell c), 0 <= c_a < 2^d (spatial_octree.jl:107-128): h_box = root_size / T(2^d), lo_a = origin_a + T(c_a) h_box,
+ * hi_a = lo_a + h_box, centre_a = origin_a + (T(2 c_a + 1) h_box) / T(2).  The children of a box are the 8 boxes
+ * (d + 1, 2 c + bits(m)), bit a of m along axis a.  Depth is capped at 20: a box at depth 20 is never subdivided (a stated
+ * deviation, so that a leaf's key fits 64 bits).
+ *   cls(p, tol) (classify_point, triangle_octree.jl:71-92): EXTERIOR if some p_a < lo_a - tol or p_a > hi_a + tol of the mesh's
+ * vertex box (wtp_mesh_bounds); otherwise, with sd the signed distance wtp_mesh_query gives, BOUNDARY if |sd| <= tol, else
+ * INTERIOR if sd < 0, else EXTERIOR.  The distance is exact, so there is no class cache.
+ *   touch(box): some triangle's axis-aligned bounding box overlaps the closed box, both ends inclusive (_boxes_overlap); it
+ * stands for any_leaf_overlapping over the reference's geometry tree and is the brute-force answer.
+ *   Refinement (_subdivide_node_octree!), from the root: a box is subdivided iff d < 20, h_box > absolute_min,
+ * h_local = h(centre) > eps(T), h_box > T(alpha) h_local, and it may contain interior: with tol = max(T(1e-8), h_box T(1e-6)),
+ * some of the 27 probes of _box_probe_points (m = (lo + hi) / T(2) per axis; the point m, the 8 corners, the 6 face centres, the
+ * 12 edge midpoints) has cls(p, tol) != EXTERIOR, or else touch(box).  h is the spacing law in T (CONSTANT: T(constant)).
+ *   Balance (balance_octree! + needs_balancing): a leaf (d, c) is subdivided iff d < 20, h_box > absolute_min and for some face
+ * direction the box (d, c +- e_a), if inside the root, is an internal box one of whose EIGHT children is internal.  Rounds
+ * in which every leaf decides on the tree the round began with are repeated until one splits nothing; balance_rounds counts
+ * them, that last one included.  Splitting only adds boxes, so the result is the reference's in-place fixed point.
+ * WTP_ERR_INTERNAL if round 100 still splits.  (The size test can_subdivide never decides here: a neighbour's internal child
+ * at depth d + 1 was subdivided, so h_box(d + 1) > absolute_min, and h_box(d) is larger still.  It is kept as the reference
+ * has it.)
+ *   Leaf class (_classify_leaf_conservative): cls at the box's centre and its 8 corners, tol as above: BOUNDARY if any is
+ * BOUNDARY or they disagree, else their common class; then a leaf with touch(box) is BOUNDARY whatever the vote, since
+ * INTERIOR leaves are trusted downstream without an inside test.
+ *   Leaf order: ascending Morton key (x lowest bit) of the leaf's lower corner at depth 20; the index wtp_node_tree_locate
+ * reports.  h of a leaf is max(h(centre), sqrt(eps(T))) (_leaf_spacing_field).
+ *   info: the counts; n_boxes, internal boxes included; depth_max and n_levels = depth_max + 1; integral = the sum over the
+ * non-exterior leaves of ((h_box h_box) h_box) / ((h h) h), each term in T, accumulated in double in an unspecified but
+ * reproducible order; max_points_auto = ceil(1.5 integral) (_estimate_volume_points); h_min = the smallest h of a non-exterior
+ * leaf (_bridson_h_min), 0 when there is none; host_syncs <= n_levels + balance_rounds + 4.  origin, root_size and
+ * absolute_min, the root as held, have no counterpart in the reference's return values: they are an addition, so that a
+ * caller can compute the leaves' boxes from their cells.
+ *   Kinds: CONSTANT, LOGLIKE, BOUNDARY_LAYER.  WTP_ERR_ARG: kind WTP_SPACING_PER_POINT or unknown, alpha not finite or <= 0,
+ * node_min_ratio not in (0, 1], a spacing value at a box or leaf centre that is NaN or infinite (a value <= eps(T) only
+ * stops refinement, as in the reference), a tree of more than 2^28 leaves.  WTP_ERR_STATE: no mesh; another boundary's law
+ * while a relax session evaluates its own.
+ *   State.  The tree lives in buffers of its own: it voids no sample, fill or front and none of them voids it.
+ * wtp_mesh_set and wtp_mesh_clear drop it, and so does a failed build.  */
+typedef struct wtp_node_tree_info {
+    int64_t n_leaves, n_interior, n_boundary, n_exterior, n_boxes;
+    int32_t depth_max, n_levels, balance_rounds, host_syncs;
+    double integral, h_min;
+    int64_t max_points_auto;
+    double origin[3], root_size, absolute_min; /* the root as held, T values as doubles */
+} wtp_node_tree_info;
+int wtp_node_tree_build(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double alpha, double node_min_ratio,
+                        wtp_node_tree_info* info_out);
+/* The n_leaves leaves in leaf order; every output may be NULL: cell_out n x 3, depth_out, class_out, h_out of the mesh's
+ * dtype.  WTP_ERR_STATE without a tree.  */
+int wtp_node_tree_get(wtp_ctx* ctx, int32_t* cell_out, int32_t* depth_out, int8_t* class_out, void* h_out);
+/* find_leaf (spatial_octree.jl:223-234) for n host points (n x 3 of dtype, converted once to T): from the root, at every
+ * internal box p_a >= centre_a picks the upper child along axis a.  leaf_out: the leaf's index in leaf order; -1 for a point
+ * with some p_a < origin_a or p_a > origin_a + root_size, or not a number (the reference would index out of its tree).  */
+int wtp_node_tree_locate(wtp_ctx* ctx, const void* xyz, int64_t n, int dtype, int64_t* leaf_out);
+int wtp_node_tree_clear(wtp_ctx* ctx);
+
+/* ---- per-leaf placements over the node octree -------------------------------------------------------
+ * Replaces the :random, :jittered and :lattice placements of _discretize_volume (src/discretization/algorithms/octree.jl:
+ * 325-458, 977-1039) over the resident tree.  The reference draws from rand(); here every draw is a seeded counter-based
+ * value, so the result is DEFINED by the rules below and two calls return the same bits.  placement: 0 random, 1 jittered,
+ * 2 lattice.  Leaves are named by their index in leaf order.
+ *   Weights.  w_i = double(((h_box h_box) h_box) / ((h h) h)), the leaf's term of the integral, computed in T.  The INTERIOR
+ * leaves form one group and the BOUNDARY leaves the other, each in leaf order; W_int and W_ns are the groups' sums of w in
+ * double, in an unspecified but reproducible order.  They are reported, and everything below is defined from the reported
+ * values.  W_int + W_ns <= 0 (no leaf in or on the domain): WTP_OK with n_points = 0.
+ *   Split.  n_interior = round_half_even(double(max_points) (W_int / (W_int + W_ns))), n_ns = max_points - n_interior,
+ * n_candidates = round_half_even(double(n_ns) boundary_oversampling), all in double.
+ *   Draws.  key(stage, j, a) = (seed << 40) + 3 (stage 2^36 + j) + a modulo 2^64; r(stage, j, a) = splitmix64(key), the
+ * function of wtp_gen_uniform_dev; u(stage, j, a) = T(float(r >> 40) 2^-24), its value.  Stages: 0 interior points,
+ * 1 near-surface candidates, 2 deficit points, 3 the leftover picks of the interior counts, 4 those of the candidates'
+ * counts, 5 the deficit's leaf picks.  Picks use a = 0.
+ *   pick(F, x): with cum the inclusive running sums of the integers F_i over all leaves (F_i = 0 outside the group) and
+ * F_total = cum of the last leaf, the first leaf i with cum_i > mulhi64(x, F_total) (the high 64 bits of the product).
+ * If F_total = 0, F_i = 1 for every leaf of the group instead: the uniform rule of the reference's fill(inv(n)) branch.
+ *   Counts of a group for `count` points (_allocate_counts_by_volume), with W the group's reported sum: expected_i =
+ * double(count) (w_i / W), base_i = floor(expected_i), leftover = max(0, count - sum base_i), F_i = floor((expected_i -
+ * base_i) 2^32) as an integer; count_i = base_i + the number of t < leftover with pick(F, r(stage, t, 0)) = i.  The
+ * counts add up to `count` exactly (to sum base_i if that is larger, which needs rounding to conspire and is not
+ * expected).  A group of no leaves gets count 0 by the split.
+ *   Points of a leaf with count n, in T, {lo, hi} the leaf's box as the tree computes it, e = hi - lo per axis.  The leaf's
+ * k-th point (k < n) has the global index j = (the counts of the leaves before it) + k within its stage.  Random:
+ * lo_a + u(stage, j, a) e_a.  Jittered and lattice: g = the smallest integer with g^3 >= n; cell = e / T(g); the point's cell
+ * is c = (k mod g, (k / g) mod g, k / g^2) (the first n of CartesianIndices, first axis fastest); cell_min_a = lo_a +
+ * T(c_a) cell_a; lattice: cell_min_a + cell_a / T(2); jittered: cell_min_a + u(stage, j, a) cell_a.
+ *   Result, in this order.  (1) The n_interior interior points (stage 0), with no inside test.  (2) Of the n_candidates
+ * near-surface candidates (stage 1), those whose wtp_mesh_query inside flag holds, in candidate order, as long as the
+ * result holds fewer than max_points; n_accepted counts them.  (3) If the result is still short and W_int > 0, n_deficit =
+ * max_points - (n_interior + n_accepted) more points: point t lies in the leaf pick(F, r(5, t, 0)) with F_i =
+ * floor((w_i / W_int) 2^32) over the interior leaves, at lo_a + u(2, t, a) e_a.  With W_int > 0 the result has exactly
+ * max_points points; without an interior leaf it may have fewer, with n_deficit = 0.
+ *   WTP_ERR_ARG: a bad placement code, max_points < 1 or > 2^31, boundary_oversampling not finite or <= 0 or so large that
+ * n_candidates exceeds 2^31, seed >= 2^24.  WTP_ERR_STATE: no mesh, no tree; wtp_node_place_get* without a placement.
+ *   State.  The placement lives in buffers of its own beside the tree's: it voids no sample, fill or front and none voids
+ * it.  A tree build (successful or not), wtp_node_tree_clear, wtp_mesh_set and wtp_mesh_clear drop it.  */
+typedef struct wtp_node_place_info {
+    int64_t n_points, n_interior, n_candidates, n_accepted, n_deficit;
+    double W_int, W_ns;
+    int32_t placement, host_syncs;
+} wtp_node_place_info;
+int wtp_node_place(wtp_ctx* ctx, int placement, int64_t max_points, double boundary_oversampling, uint64_t seed,
+                   wtp_node_place_info* info_out);
+/* n_points rows: xyz_out n x 3 of the mesh's dtype, leaf_out each point's leaf; either may be NULL.  */
+int wtp_node_place_get(wtp_ctx* ctx, void* xyz_out, int64_t* leaf_out);
+/* The same into device memory.  */
+int wtp_node_place_get_dev(wtp_ctx* ctx, void* d_xyz_out, int64_t* d_leaf_out);
+
 /* ---- consumers of the k-NN rows ------------------------------------
  * Replaces compute_normals(points; k) / update_normals! (src/normals.jl:15-69): per point the
  * eigenvector of the smallest eigenvalue of the covariance of its k nearest points (self

@@ -188,6 +188,57 @@ function fill_area(sd::SpacingDesc, seeds, ::Type{T}; factor = 0.75, max_points:
     return vol, rs, info
 end
 
+# ---- the spacing-driven node octree (src/octree/spacing_criterion.jl:88-215) on the device ---------------------------------
+# (include/wtp.h: wtp_node_tree_build, wtp_node_tree_get, wtp_node_tree_locate; the mesh is the one wtp_mesh_set holds)
+mutable struct NodeTreeInfo
+    n_leaves::Int64; n_interior::Int64; n_boundary::Int64; n_exterior::Int64; n_boxes::Int64
+    depth_max::Int32; n_levels::Int32; balance_rounds::Int32; host_syncs::Int32
+    integral::Float64; h_min::Float64; max_points_auto::Int64
+    origin::NTuple{3, Float64}; root_size::Float64; absolute_min::Float64
+    NodeTreeInfo() = new()
+end
+
+# build_node_octree + classify_node_octree: sd as for fill_volume, alpha and node_min_ratio as Orthtree holds them.
+# Returns (cells as SVector{3,Int32} (0-based), depths, classes (LEAF_EXTERIOR 0, LEAF_BOUNDARY 1, LEAF_INTERIOR 2),
+# h = max(h(centre), sqrt(eps(T))) per leaf, info); info.max_points_auto is _estimate_volume_points, info.h_min _bridson_h_min.
+function node_tree(sd::SpacingDesc, ::Type{T}; alpha = 2.0, node_min_ratio = 1.0e-6) where {T}
+    info = NodeTreeInfo()
+    check(context(), ccall((:wtp_node_tree_build, lib), Cint, (Ptr{Cvoid}, Ref{SpacingDesc}, Float64, Float64, Ref{NodeTreeInfo}),
+        context(), sd, Float64(alpha), Float64(node_min_ratio), info))
+    n = info.n_leaves
+    cell = Vector{SVector{3, Int32}}(undef, n); depth = Vector{Int32}(undef, n); cls = Vector{Int8}(undef, n); h = Vector{T}(undef, n)
+    check(context(), ccall((:wtp_node_tree_get, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int8}, Ptr{Cvoid}),
+        context(), cell, depth, cls, h))
+    return cell, depth, cls, h, info
+end
+
+# find_leaf for a vector of SVector{3,T}: 1-based indices into node_tree's leaf order, 0 for a point outside the root box
+function node_tree_locate(xs::Vector{SVector{3, T}}) where {T}
+    leaf = Vector{Int64}(undef, length(xs))
+    check(context(), ccall((:wtp_node_tree_locate, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Cint, Ptr{Int64}),
+        context(), xs, length(xs), dtype(T), leaf))
+    return leaf .+ 1
+end
+
+mutable struct NodePlaceInfo
+    n_points::Int64; n_interior::Int64; n_candidates::Int64; n_accepted::Int64; n_deficit::Int64
+    W_int::Float64; W_ns::Float64; placement::Int32; host_syncs::Int32
+    NodePlaceInfo() = new()
+end
+
+# the placements :random, :jittered, :lattice over the tree of node_tree (include/wtp.h: wtp_node_place).  Returns
+# (points as SVector{3,T}, each point's leaf (1-based, node_tree's order), info).
+function node_place(placement::Symbol, max_points::Int, ::Type{T}; boundary_oversampling = 2.0, seed::Integer = 0) where {T}
+    code = Dict(:random => 0, :jittered => 1, :lattice => 2)[placement]
+    info = NodePlaceInfo()
+    check(context(), ccall((:wtp_node_place, lib), Cint, (Ptr{Cvoid}, Cint, Int64, Float64, UInt64, Ref{NodePlaceInfo}),
+        context(), code, max_points, Float64(boundary_oversampling), UInt64(seed), info))
+    n = info.n_points
+    vol = Vector{SVector{3, T}}(undef, n); leaf = Vector{Int64}(undef, n)
+    check(context(), ccall((:wtp_node_place_get, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}), context(), vol, leaf))
+    return vol, leaf .+ 1, info
+end
+
 # ---- src/normals.jl:75-161 and src/surface_operations.jl:58-94: the graph part on the device ------------------------
 # (include/wtp.h: wtp_orient_normals, wtp_normal_components)
 mutable struct NormalGraphInfo

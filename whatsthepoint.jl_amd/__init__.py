@@ -19,8 +19,9 @@ from .octree import TriangleOctree, has_consistent_normals, signed_volume
 from .quadtree import SegmentQuadtree
 from .normals import compute_normals, update_normals, orient_normals, split_surface, combine_surfaces
 from .limiter import gradient_limit_field
-from .sampling import (sample_surface, fill_volume, fill_area, front_volume, SlakKosec, discretize, generate_shadows,
+from .sampling import (sample_surface, fill_volume, fill_area, front_volume, SlakKosec, Orthtree, discretize, generate_shadows,
                        ShadowPoints)
-from . import synth, stl, octree, quadtree, sampling
+from .nodetree import NodeOctree
+from . import synth, stl, octree, quadtree, sampling, nodetree
 
 __all__ = [n for n in dir() if not n.startswith("_")]

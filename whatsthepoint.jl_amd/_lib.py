@@ -99,6 +99,21 @@ class FrontInfo(C.Structure):
                 ("rounds_max", C.c_int32), ("host_syncs", C.c_int32), ("r_min", C.c_double), ("r_max", C.c_double)]
 
 
+class NodeTreeInfo(C.Structure):
+    """wtp_node_tree_info: what wtp_node_tree_build reports about the tree."""
+    _fields_ = [("n_leaves", C.c_int64), ("n_interior", C.c_int64), ("n_boundary", C.c_int64), ("n_exterior", C.c_int64),
+                ("n_boxes", C.c_int64), ("depth_max", C.c_int32), ("n_levels", C.c_int32), ("balance_rounds", C.c_int32),
+                ("host_syncs", C.c_int32), ("integral", C.c_double), ("h_min", C.c_double), ("max_points_auto", C.c_int64),
+                ("origin", C.c_double * 3), ("root_size", C.c_double), ("absolute_min", C.c_double)]
+
+
+class NodePlaceInfo(C.Structure):
+    """wtp_node_place_info: what wtp_node_place reports about a placement."""
+    _fields_ = [("n_points", C.c_int64), ("n_interior", C.c_int64), ("n_candidates", C.c_int64), ("n_accepted", C.c_int64),
+                ("n_deficit", C.c_int64), ("W_int", C.c_double), ("W_ns", C.c_double), ("placement", C.c_int32),
+                ("host_syncs", C.c_int32)]
+
+
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                           C.POINTER(C.c_void_p), C.POINTER(C.c_int64))
@@ -169,6 +184,13 @@ SIGNATURES = {
     "wtp_loops_fill_get": (_i, [_vp, _vp, _vp, _vp]),
     "wtp_loops_fill_get_dev": (_i, [_vp, _vp, _vp]),
     "wtp_loops_fill_darts": (_i, [_vp, C.POINTER(SpacingDesc), _d, C.c_uint64, _i64, _i64, _vp, _vp, _vp]),
+    "wtp_node_tree_build": (_i, [_vp, C.POINTER(SpacingDesc), _d, _d, C.POINTER(NodeTreeInfo)]),
+    "wtp_node_tree_get": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "wtp_node_tree_locate": (_i, [_vp, _vp, _i64, _i, _vp]),
+    "wtp_node_tree_clear": (_i, [_vp]),
+    "wtp_node_place": (_i, [_vp, _i, _i64, _d, C.c_uint64, C.POINTER(NodePlaceInfo)]),
+    "wtp_node_place_get": (_i, [_vp, _vp, _vp]),
+    "wtp_node_place_get_dev": (_i, [_vp, _vp, _vp]),
     "wtp_relax_set_wall": (_i, [_vp, _i64, _d]),
     "wtp_relax_get_wall": (_i, [_vp, _vp, _vp, _vp, _i]),
     "wtp_relax_set_wall_flags": (_i, [_vp, _vp, _vp]),

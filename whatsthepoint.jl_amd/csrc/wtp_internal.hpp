@@ -421,6 +421,31 @@ struct SampleCtl {
     unsigned long long n_inside;   // wtp_mesh_fill: darts taken so far that were inside the mesh
 };
 
+// spacing-driven node octree over the mesh (wtp_node_tree.hip): the leaves as one array of 64-bit keys, always in leaf
+// (Morton) order: a split puts the 8 children where their parent stood.  Everything else is scratch of a build or a
+// read-out; nothing here is shared with the samplers.
+struct NodeTreeState {
+    bool valid = false;
+    int dtype = -1;
+    int64_t n = 0;                 // leaves
+    int cur = 0;                   // keys[cur] holds them
+    DevBuf keys[2], front[2];      // leaf keys; positions of the boxes the current level decides on
+    DevBuf cnt, off, scan_tmp;     // boxes each leaf turns into (1 or 8), their exclusive scan
+    DevBuf ctr, h, tol, lohi;      // per box of a pass: centre, h(centre), probe tolerance, {lo, hi}
+    DevBuf flag, need, touch;      // per box of a pass: passed the size tests / split; wants the touch walk; its answer
+    DevBuf pts, pcls;              // a chunk's probe points and their classes
+    DevBuf cls, hout;              // per leaf: class, max(h(centre), sqrt(eps))
+    DevBuf red;                    // counters and the integral's block partials
+    DevBuf io;                     // wtp_node_tree_locate: points in, leaves out
+    wtp_node_tree_info info{};
+    // wtp_node_place: the resident placement (points, each point's leaf) and the scratch of a run
+    bool placed = false;
+    DevBuf p_xyz, p_leaf;          // the result: n x 3 of the tree's dtype, int64 leaves
+    DevBuf p_w, p_cnt, p_cum, p_f, p_fcum, p_tile; // per leaf: weights of both groups, counts, their sums, F, its sums; scan tiles
+    DevBuf p_cand, p_cleaf, p_in;  // candidates, their leaves, their inside flags
+    wtp_node_place_info pinfo{};
+};
+
 struct KdTree {
     DevBuf nodes;      // variable spacings: kd-tree over the boundary points (heap order)
     int64_t m = 0;     // nodes in it; the key below identifies the boundary it was built from
@@ -561,6 +586,7 @@ struct wtp_ctx {
     wtp::MeshState mesh;
     wtp::LoopsState loops;
     wtp::SampleState sample;
+    wtp::NodeTreeState ntree;
     wtp::DevBuf sp_hint;       // variable spacings: nearest tree node of each snapshot point at the last sweep
     wtp::KdTree kd;
     int64_t n_syncs = 0;       // host synchronisations of the context's stream so far (wtp_block_info.host_syncs counts with it)
@@ -755,6 +781,16 @@ int front_candidates(wtp_ctx* ctx, const wtp_spacing_desc* sp, uint64_t seed, co
                      int per, T* xyz_out, uint8_t* inside_out, T* r_out);
 // wtp_mesh_query's inside flag for n device points of the mesh's own type (wtp_mesh.hip): the domain test of wtp_mesh_fill
 template <typename T> int launch_mesh_inside(wtp_ctx* ctx, const T* d_xyz, int64_t n, uint8_t* d_inside);
+// classify_point's class (0 exterior, 1 boundary, 2 interior) of n device points of the mesh's own type (wtp_mesh.hip);
+// point i takes the tolerance d_tol[i / per] and is skipped, its class left unwritten, where d_need[i / per] == 0
+template <typename T>
+int launch_mesh_point_class(wtp_ctx* ctx, const T* d_xyz, int64_t n, const T* d_tol, int per, const uint8_t* d_need,
+                            uint8_t* d_cls);
+// does some triangle's bounding box overlap the closed box d_lohi[6 i ..] = {lo, hi}?  Boxes with d_need[i] == 0 are skipped
+template <typename T>
+int launch_mesh_box_touch(wtp_ctx* ctx, const T* d_lohi, int64_t n, const uint8_t* d_need, uint8_t* d_touch);
+// wtp_node_tree.hip: a new or cleared mesh drops the node tree
+void node_tree_invalidate(wtp_ctx* ctx);
 // wtp_loops_query's inside flag for n device rows of 3 columns (z ignored) of the index's own type (wtp_loops.hip): the
 // domain test of wtp_loops_fill
 template <typename T> int launch_loops_inside(wtp_ctx* ctx, const T* d_xyz, int64_t n, uint8_t* d_inside);

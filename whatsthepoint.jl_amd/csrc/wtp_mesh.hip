@@ -615,6 +615,86 @@ mesh_inside_kernel(const T* __restrict__ xyz, int64_t n, MeshView<T> mv, uint8_t
     }
 }
 
+// classify_point (src/octree/triangle_octree.jl:71-92) with the exact distance in place of the class cache: the probes of
+// the node octree (wtp_node_tree.hip).  Point i belongs to box i / per: it takes that box's tolerance, and a box that
+// is not wanted costs nothing.  0 exterior, 1 boundary, 2 interior (LEAF_EXTERIOR .. LEAF_INTERIOR).
+template <typename T>
+__global__ void __launch_bounds__(kMeshThreads)
+mesh_point_class_kernel(const T* __restrict__ xyz, int64_t n, const T* __restrict__ tol_of, int per,
+                        const uint8_t* __restrict__ need_of, MeshView<T> mv, uint8_t* __restrict__ cls_out) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t span = (n + 63) / 64 * 64;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < span; i += stride) {
+        const bool active = i < n;
+        const int64_t ii = active ? i : n - 1;
+        const bool need = active && (!need_of || need_of[ii / per] != 0);
+        const T q[3] = {xyz[3 * ii], xyz[3 * ii + 1], xyz[3 * ii + 2]};
+        const T tol = tol_of[ii / per];
+        bool out = false;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) out = out || (q[a] < mv.lo[a] - tol) || (q[a] > mv.hi[a] + tol);
+        const bool search = need && !out;
+        Nearest<T> r;
+        r.tri = -1;
+        r.d2 = (T)1;
+        if (__any(search)) {
+            int32_t bn = -1;
+            r = mesh_nearest_guess<T>(mv.nodes, mv.m, q, search, mv.scale, search ? mesh_greedy_guess<T>(mv.nodes, mv.m, q) : -1, &bn);
+        }
+        if (!need) continue;
+        uint8_t c = 0;
+        if (search && r.tri >= 0) {
+            const T s = side_of<T>(mv, q, r);
+            const T dist = wsqrt(r.d2);
+            const T sd = s < (T)0 ? -dist : (s > (T)0 ? dist : (T)0);
+            c = (sd < (T)0 ? -sd : sd) <= tol ? 1 : (sd < (T)0 ? 2 : 0);
+        }
+        cls_out[i] = c;
+    }
+}
+
+// touch(box) of the node octree: does some triangle's bounding box overlap the closed box?  One lane per box walks the
+// tree without a stack; a subtree is skipped iff the box of everything below it does not overlap, so the answer is the
+// brute-force one.  At most m node visits.
+template <typename T>
+__global__ void __launch_bounds__(kMeshThreads)
+mesh_box_touch_kernel(const T* __restrict__ lohi, int64_t n, const uint8_t* __restrict__ need_of, const MeshNode<T>* __restrict__ nodes,
+                      int32_t m, uint8_t* __restrict__ touch_out) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        if (need_of && need_of[i] == 0) continue;
+        T lo[3], hi[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) lo[a] = lohi[6 * i + a], hi[a] = lohi[6 * i + 3 + a];
+        bool found = false;
+        uint32_t j = 1;
+        do {
+            const MeshNode<T>& nd = nodes[j - 1];
+            bool apart = false;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) apart = apart || lo[a] > nd.hi[a] || hi[a] < nd.lo[a];
+            if (apart) {
+                j = heap_escape(j, (uint32_t)m);
+                continue;
+            }
+            bool tapart = false;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                T tl = nd.v[a] < nd.v[3 + a] ? nd.v[a] : nd.v[3 + a], th = nd.v[a] < nd.v[3 + a] ? nd.v[3 + a] : nd.v[a];
+                tl = tl < nd.v[6 + a] ? tl : nd.v[6 + a];
+                th = th > nd.v[6 + a] ? th : nd.v[6 + a];
+                tapart = tapart || lo[a] > th || hi[a] < tl;
+            }
+            if (!tapart) {
+                found = true;
+                break;
+            }
+            j = 2 * j <= (uint32_t)m ? 2 * j : heap_escape(j, (uint32_t)m);
+        } while (j != 1);
+        touch_out[i] = found ? 1 : 0;
+    }
+}
+
 // The wall rule after a sweep (src/repel.jl:448-469).  old = the sweep's query buffer (x_i), cur = its
 // output (x_proposed), same slot order.  Boundary points land on the mesh; volume points that left
 // the domain go back to x_i and are flagged.
@@ -714,6 +794,29 @@ template <typename T> int launch_mesh_inside(wtp_ctx* ctx, const T* d_xyz, int64
 }
 template int launch_mesh_inside<float>(wtp_ctx*, const float*, int64_t, uint8_t*);
 template int launch_mesh_inside<double>(wtp_ctx*, const double*, int64_t, uint8_t*);
+
+template <typename T>
+int launch_mesh_point_class(wtp_ctx* ctx, const T* d_xyz, int64_t n, const T* d_tol, int per, const uint8_t* d_need,
+                            uint8_t* d_cls) {
+    if (n < 1) return WTP_OK;
+    hipLaunchKernelGGL((mesh_point_class_kernel<T>), dim3(mesh_grid(n)), dim3(kMeshThreads), 0, ctx->stream, d_xyz, n, d_tol,
+                       per, d_need, make_view<T>(ctx), d_cls);
+    WTP_HIP(ctx, hipGetLastError());
+    return WTP_OK;
+}
+template int launch_mesh_point_class<float>(wtp_ctx*, const float*, int64_t, const float*, int, const uint8_t*, uint8_t*);
+template int launch_mesh_point_class<double>(wtp_ctx*, const double*, int64_t, const double*, int, const uint8_t*, uint8_t*);
+
+template <typename T>
+int launch_mesh_box_touch(wtp_ctx* ctx, const T* d_lohi, int64_t n, const uint8_t* d_need, uint8_t* d_touch) {
+    if (n < 1) return WTP_OK;
+    hipLaunchKernelGGL((mesh_box_touch_kernel<T>), dim3(mesh_grid(n)), dim3(kMeshThreads), 0, ctx->stream, d_lohi, n, d_need,
+                       (const MeshNode<T>*)ctx->mesh.nodes.p, (int32_t)ctx->mesh.nt, d_touch);
+    WTP_HIP(ctx, hipGetLastError());
+    return WTP_OK;
+}
+template int launch_mesh_box_touch<float>(wtp_ctx*, const float*, int64_t, const uint8_t*, uint8_t*);
+template int launch_mesh_box_touch<double>(wtp_ctx*, const double*, int64_t, const uint8_t*, uint8_t*);
 
 template <typename TP>
 int launch_mesh_constrain(wtp_ctx* ctx, const Pt<TP>* old, Pt<TP>* cur, int64_t n, int64_t n_fixed, double offset,
@@ -829,6 +932,7 @@ WTP_API int wtp_mesh_set(wtp_ctx* ctx, const void* vertices, int64_t nv, const i
     ctx->mesh.nt = 0;
     ctx->mesh.cls_ready = false;
     sample_invalidate(ctx);
+    node_tree_invalidate(ctx);
     const int rc = dtype == WTP_F32 ? mesh_set_t<float>(ctx, (const float*)vertices, nv, triangles, nt)
                                     : mesh_set_t<double>(ctx, (const double*)vertices, nv, triangles, nt);
     if (rc) return rc;
@@ -845,6 +949,7 @@ WTP_API int wtp_mesh_clear(wtp_ctx* ctx) {
     ctx->mesh.cls_ready = false;
     ctx->mesh.face_host.clear();
     sample_invalidate(ctx);
+    node_tree_invalidate(ctx);
     return WTP_OK;
 }
 

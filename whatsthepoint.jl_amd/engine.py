@@ -305,11 +305,13 @@ class Context:
         L.check(self._h, self._lib.wtp_mesh_set(self._h, _vp(v), len(v), _vp(t), len(t), _dtype_code(v.dtype)))
         self._mesh_key = (len(v), len(t), v.dtype)
         self._mesh_owner = None   # octree.py marks the TriangleOctree it uploaded
+        self._node_tree_owner = None  # a new mesh drops the node tree (nodetree.py marks the NodeOctree it built)
 
     def mesh_clear(self):
         L.check(self._h, self._lib.wtp_mesh_clear(self._h))
         self._mesh_key = None
         self._mesh_owner = None
+        self._node_tree_owner = None
 
     def mesh_face_normals(self):
         nt = self._mesh_key[1]
@@ -593,6 +595,67 @@ class Context:
         L.check(self._h, rc)
         del keep
         return xy, inside.astype(bool), r
+
+    # ---- spacing-driven node octree over the mesh (the Orthtree algorithm's tree; wtp_node_tree_*) -----------------------
+    def node_tree_build(self, spacing, alpha: float = 2.0, node_min_ratio: float = 1.0e-6, spacing_desc=None):
+        """wtp_node_tree_build on the mesh of mesh_set: refined by the spacing, balanced 2:1, leaves classified.  Returns
+        the info dict (origin as a tuple); the tree stays on the device (node_tree_get, node_tree_locate)."""
+        sd, keep = (spacing_desc, None) if spacing_desc is not None else self._sample_spacing(spacing)
+        info = L.NodeTreeInfo()
+        rc = self._lib.wtp_node_tree_build(self._h, C.byref(sd), float(alpha), float(node_min_ratio), C.byref(info))
+        L.check(self._h, rc)
+        del keep
+        self._node_tree_owner = None
+        out = _info_dict(info)
+        out["origin"] = tuple(info.origin)
+        return out
+
+    def node_tree_get(self, n: int, want=("cell", "depth", "cls", "h")):
+        """The n = info['n_leaves'] leaves in leaf order as a dict of host arrays: cell (n, 3) int32, depth int32,
+        cls int8 (0 exterior, 1 boundary, 2 interior), h of the mesh's dtype."""
+        spec = dict(cell=np.int32, depth=np.int32, cls=np.int8, h=self._mesh_dtype())
+        out = {k: np.empty((n, 3) if k == "cell" else n, dtype=d) for k, d in spec.items() if k in want}
+        rc = self._lib.wtp_node_tree_get(self._h, _vp(out.get("cell")), _vp(out.get("depth")), _vp(out.get("cls")),
+                                         _vp(out.get("h")))
+        L.check(self._h, rc)
+        return out
+
+    def node_tree_locate(self, pts):
+        """wtp_node_tree_locate: the leaf (index in leaf order) of each of (n, 3) points, -1 outside the root box."""
+        pts = _cloud(pts)
+        if pts.shape[1] != 3:
+            raise L.WtpArgumentError("the node tree is 3-D")
+        out = np.empty(len(pts), dtype=np.int64)
+        L.check(self._h, self._lib.wtp_node_tree_locate(self._h, _vp(pts), len(pts), _dtype_code(pts.dtype), _vp(out)))
+        return out
+
+    PLACEMENTS = {"random": 0, "jittered": 1, "lattice": 2}
+
+    def node_place(self, placement, max_points: int, boundary_oversampling: float = 2.0, seed: int = 0):
+        """wtp_node_place over the resident tree: placement "random" | "jittered" | "lattice" (or its code).  Returns the
+        info dict; the points stay on the device (node_place_get)."""
+        code = self.PLACEMENTS.get(placement, placement)
+        if isinstance(code, str):
+            raise L.WtpArgumentError("placement must be :random, :jittered, :lattice, or :bridson")
+        info = L.NodePlaceInfo()
+        rc = self._lib.wtp_node_place(self._h, int(code), int(max_points), float(boundary_oversampling), C.c_uint64(int(seed)),
+                                      C.byref(info))
+        L.check(self._h, rc)
+        return _info_dict(info)
+
+    def node_place_get(self, n: int, want=("xyz", "leaf")):
+        """The n = info['n_points'] points of the last node_place: xyz (n, 3) of the mesh's dtype, leaf int64."""
+        out = self._out_arrays(n, want, dict(xyz=None, leaf=np.int64))
+        L.check(self._h, self._lib.wtp_node_place_get(self._h, _vp(out.get("xyz")), _vp(out.get("leaf"))))
+        return out
+
+    def node_place_get_dev(self, d_xyz_ptr: int = 0, d_leaf_ptr: int = 0):
+        """wtp_node_place_get_dev: the points into device arrays given as addresses (0 = absent)."""
+        L.check(self._h, self._lib.wtp_node_place_get_dev(self._h, C.c_void_p(d_xyz_ptr or None), C.c_void_p(d_leaf_ptr or None)))
+
+    def node_tree_clear(self):
+        self._node_tree_owner = None
+        L.check(self._h, self._lib.wtp_node_tree_clear(self._h))
 
     def set_stream(self, stream_handle=None):
         """Run the library on a caller-owned HIP stream (handle as an int; 0 = the device's default

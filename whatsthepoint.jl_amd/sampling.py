@@ -162,6 +162,46 @@ class SlakKosec:
         return f"SlakKosec(n={self.n})"
 
 
+class Orthtree:
+    """Orthtree(placement="bridson", alpha=2.0, node_min_ratio=None, boundary_oversampling=2.0, factor=0.75)
+    (src/discretization/algorithms/octree.jl:102-170) for discretize(..., alg=Orthtree(...)): the spacing-driven node octree
+    (nodetree.NodeOctree) sizes the run, so that max_points=None means _estimate_volume_points of the tree.  The mesh and
+    the spacing are discretize's own arguments; factor is the reference's bridson_factor.  "bridson" runs fill_volume under the tree's cap;
+    "random", "jittered" and "lattice" are the per-leaf placements (NodeOctree.place), which use neither seeds nor factor.
+    max_growth is accepted only as 0: the limited field needs a spacing kind of its own."""
+
+    PLACEMENTS = ("random", "jittered", "lattice", "bridson")
+
+    def __init__(self, placement: str = "bridson", alpha: float = 2.0, node_min_ratio=None, boundary_oversampling: float = 2.0,
+                 factor: float = 0.75, max_growth: float = 0.0):
+        placement = str(placement).lstrip(":")
+        if not boundary_oversampling > 0:
+            raise WtpArgumentError("boundary_oversampling must be positive")
+        if placement not in self.PLACEMENTS:
+            raise WtpArgumentError("placement must be :random, :jittered, :lattice, or :bridson")
+        if not alpha > 0:
+            raise WtpArgumentError("alpha must be positive")
+        if not factor > 0:
+            raise WtpArgumentError("bridson_factor must be positive")
+        if not max_growth >= 0:
+            raise WtpArgumentError("max_growth must be ≥ 0 (0 disables the limiter)")
+        if max_growth > 0:
+            raise WtpArgumentError("max_growth > 0 is not available: the gradient-limited field is not served as a spacing "
+                                   "law on the device yet (gradient_limit_field limits the leaf values themselves)")
+        if node_min_ratio is not None and not 0 < node_min_ratio <= 1:
+            raise WtpArgumentError("node_min_ratio must be in (0, 1]")
+        self.placement, self.alpha, self.node_min_ratio = placement, float(alpha), node_min_ratio
+        self.boundary_oversampling, self.factor, self.max_growth = float(boundary_oversampling), float(factor), 0.0
+
+    def is_default(self):
+        return (self.placement, self.alpha, self.node_min_ratio, self.boundary_oversampling, self.factor) == (
+            "bridson", 2.0, None, 2.0, 0.75)
+
+    def __repr__(self):
+        return (f"Orthtree(placement={self.placement!r}, alpha={self.alpha}, node_min_ratio={self.node_min_ratio}, "
+                f"boundary_oversampling={self.boundary_oversampling}, factor={self.factor})")
+
+
 def front_volume(mesh, spacing, *, seeds, n: int = 10, max_points: int = 10_000_000, seed: int = synth.SEED,
                  batch: int = 0, ctx=None):
     """Advancing-front points inside a closed triangle mesh -> PointVolume: the placement of
@@ -193,32 +233,52 @@ def front_volume(mesh, spacing, *, seeds, n: int = 10, max_points: int = 10_000_
     return vol
 
 
-_EXTRAS = {"fill": ("fill_info", "fill_r"), "front": ("front_info", "front_h", "front_parent")}
+_EXTRAS = {"fill": ("fill_info", "fill_r"), "front": ("front_info", "front_h", "front_parent"),
+           "place": ("place_info", "place_leaf")}
 
 
-def discretize(boundary, spacing, mesh=None, *, alg=None, factor: float = None, max_points: int = 10_000_000,
+_MAX_POINTS_DEFAULT = 10_000_000
+
+
+def discretize(boundary, spacing, mesh=None, *, alg=None, factor: float = None, max_points: int = _MAX_POINTS_DEFAULT,
                stall_limit: int = None, seed: int = synth.SEED, ctx=None):
     """discretize(bnd, spacing; alg, max_points) -> PointCloud(boundary, volume); the boundary itself is returned
     unchanged.  alg = None: Orthtree(mesh; spacing, placement = :bridson), the boundary's points being the seeds of
     fill_volume (factor 0.75, stall_limit 2000 unless given).  alg = SlakKosec(n): the advancing front from the boundary's
-    points (front_volume), which has no factor and no stall_limit.
+    points (front_volume), which has no factor and no stall_limit.  alg = Orthtree(...): the node octree of the mesh under
+    the spacing is built first (NodeOctree, alpha and node_min_ratio from alg); max_points = None then means the tree's
+    estimate, ceil(1.5 * the spacing integral), and the "bridson" placement runs fill_volume under that cap with alg's
+    factor unless one is given; the placements "random", "jittered" and "lattice" run NodeOctree.place (the volume then
+    carries `place_info` and `place_leaf`).  The cloud's volume carries the tree as `node_tree`.  (The reference sizes its 1.5 headroom
+    for its front, about 1.1 / h^3; the dart thrower at factor 0.75 saturates near 1.7 / h^3, so under the automatic cap a
+    run usually ends by max_points: a prefix of the saturated run, spread over the whole domain.  That is the estimate
+    doing its job, so no truncation warning is raised for it; fill_info["stop_reason"] == 2 still says so.)
 
     A 2-D boundary takes the reference's 2-D default, Orthtree(bnd; spacing) (src/discretization/discretization.jl:63):
     mesh = None indexes the boundary's surfaces as loops (SegmentQuadtree.from_boundary), or mesh is a SegmentQuadtree;
-    the placement is fill_area with the boundary's points as seeds.  2-D has no SlakKosec."""
+    the placement is fill_area with the boundary's points as seeds.  2-D has no SlakKosec and no node quadtree: of the
+    Orthtree objects only the default Orthtree() is taken, as another name for alg = None."""
     from .cloud import PointBoundary, PointCloud
     from .quadtree import SegmentQuadtree
 
-    if alg is not None and not isinstance(alg, SlakKosec):
-        raise WtpArgumentError(f"alg must be None or SlakKosec(n), not {type(alg).__name__}")
+    if alg is not None and not isinstance(alg, (SlakKosec, Orthtree)):
+        raise WtpArgumentError(f"alg must be None, SlakKosec(n) or Orthtree(...), not {type(alg).__name__}")
+    tree_alg = alg if isinstance(alg, Orthtree) else None
+    if max_points is None and tree_alg is None:
+        raise WtpArgumentError("max_points = None asks for the node octree's estimate: pass alg=Orthtree(...)")
+    if tree_alg is not None:
+        alg = None  # the placement below is the default one, sized by the tree
     if alg is not None and (factor is not None or stall_limit is not None):
         raise WtpArgumentError("factor and stall_limit do not apply to SlakKosec: the front tests at the spacing itself "
                                "and ends when no point is left to expand")
     if not isinstance(boundary, PointBoundary):
         boundary = PointBoundary(boundary)
     dim = boundary.points().shape[1]
-    if dim == 2 and alg is not None:
-        raise WtpArgumentError(f"2D discretization supports the Orthtree fill only (the default: drop `alg`); got {alg!r}")
+    if dim == 2 and (alg is not None or (tree_alg is not None and not tree_alg.is_default())):
+        raise WtpArgumentError("2D discretization supports the Orthtree fill only (the default: drop `alg`); got "
+                               f"{(alg or tree_alg)!r}")
+    if dim == 2 and tree_alg is not None:  # Orthtree() is the 2-D default by name; there is no node quadtree to size it
+        tree_alg, max_points = None, _MAX_POINTS_DEFAULT if max_points is None else max_points
     if dim == 2 and mesh is not None and not isinstance(mesh, SegmentQuadtree):
         raise WtpArgumentError(f"this geometry index is 3D ({type(mesh).__name__}) and cannot fill a 2D boundary — pass "
                                "mesh=None or SegmentQuadtree.from_boundary(boundary), which indexes the boundary loops")
@@ -227,22 +287,47 @@ def discretize(boundary, spacing, mesh=None, *, alg=None, factor: float = None, 
                                "surface mesh or its TriangleOctree")
     if dim == 3 and mesh is None:
         raise WtpArgumentError("a 3D boundary needs its surface mesh: pass a TriangleOctree or a (vertices, triangles) pair")
-    if dim == 2:
+    node_tree, auto_cap = None, False
+    if tree_alg is not None:
+        from .nodetree import NodeOctree
+
+        mesh = _as_octree(mesh, ctx, True)
+        node_tree = NodeOctree(mesh, spacing, alpha=tree_alg.alpha, node_min_ratio=tree_alg.node_min_ratio, ctx=ctx)
+        if max_points is None:
+            auto_cap = True
+            max_points = node_tree.estimate_volume_points()
+            if max_points < 1:
+                raise WtpArgumentError("the node octree has no leaf inside or on the domain: nothing to fill — check the "
+                                       "spacing vs domain size and the mesh's orientation")
+        if factor is None:
+            factor = tree_alg.factor
+    kind = "fill" if alg is None else "front"
+    if dim == 3 and tree_alg is not None and tree_alg.placement != "bridson":
+        kind = "place"  # a per-leaf placement: no seeds, no factor, no stall_limit (the reference's have none either)
+        vol = node_tree.place(tree_alg.placement, max_points, tree_alg.boundary_oversampling, seed, ctx=ctx)
+        if len(vol) == 0:
+            raise WtpArgumentError("the placement produced no points — check spacing vs domain size and mesh orientation")
+    elif dim == 2:
         tree = mesh if mesh is not None else SegmentQuadtree.from_boundary(boundary, ctx=ctx)
         vol = fill_area(tree, spacing, seeds=boundary.points(), factor=0.75 if factor is None else factor,
                         max_points=max_points, stall_limit=2000 if stall_limit is None else stall_limit, seed=seed, ctx=ctx)
     elif alg is None:
-        vol = fill_volume(mesh, spacing, seeds=boundary.points(), factor=0.75 if factor is None else factor,
-                          max_points=max_points, stall_limit=2000 if stall_limit is None else stall_limit, seed=seed,
-                          ctx=ctx)
+        with warnings.catch_warnings():
+            if auto_cap:  # ending at the tree's own estimate is the run's plan, not a truncation to warn of
+                warnings.filterwarnings("ignore", message="Volume fill truncated by max_points")
+            vol = fill_volume(mesh, spacing, seeds=boundary.points(), factor=0.75 if factor is None else factor,
+                              max_points=max_points, stall_limit=2000 if stall_limit is None else stall_limit, seed=seed,
+                              ctx=ctx)
     else:
         vol = front_volume(mesh, spacing, seeds=boundary.points(), n=alg.n, max_points=max_points, seed=seed, ctx=ctx)
     bp = boundary.points()
     if vol.points().dtype != bp.dtype:  # the cloud keeps the boundary's type (the mesh's decided the run)
-        extras = {k: getattr(vol, k) for k in _EXTRAS["fill" if alg is None else "front"]}
+        extras = {k: getattr(vol, k) for k in _EXTRAS[kind]}
         vol = type(vol)(vol.points().astype(bp.dtype))
         for k, v in extras.items():
             setattr(vol, k, v)
+    if node_tree is not None:
+        vol.node_tree = node_tree
     return PointCloud(boundary, vol)
 
 
