@@ -582,7 +582,8 @@ int wtp_loops_fill_darts(wtp_ctx* ctx, const wtp_spacing_desc* spacing, double f
  * reports.  h of a leaf is max(h(centre), sqrt(eps(T))) (_leaf_spacing_field).
  *   info: the counts; n_boxes, internal boxes included; depth_max and n_levels = depth_max + 1; integral = the sum over the
  * non-exterior leaves of ((h_box h_box) h_box) / ((h h) h), each term in T, accumulated in double in an unspecified but
- * reproducible order; max_points_auto = ceil(1.5 integral) (_estimate_volume_points); h_min = the smallest h of a non-exterior
+ * reproducible order; max_points_auto = ceil(1.5 integral) (_estimate_volume_points), INT64_MAX where that is 2^63 or more
+ * (a leaf whose h was clamped can weigh 1e20 in Float64); h_min = the smallest h of a non-exterior
  * leaf (_bridson_h_min), 0 when there is none; host_syncs <= n_levels + balance_rounds + 4.  origin, root_size and
  * absolute_min, the root as held, have no counterpart in the reference's return values: they are an addition, so that a
  * caller can compute the leaves' boxes from their cells.

@@ -42,8 +42,9 @@ def _cavity():
 
 
 # ---- the cases --------------------------------------------------------------------------------------------------------
-# spacing: ("const", h) | ("bl", at_wall, bulk, layer_thickness, boundary points or a function dtype -> points).  h is
-# chosen so that h_box = 1.02 / 2^d (2.04 / 2^d for the cavity) never equals alpha h.
+# spacing: ("const", h) | ("bl", at_wall, bulk, layer_thickness, points) | ("loglike", base, growth, points), the points an
+# array or a function dtype -> points.  h is chosen so that h_box = 1.02 / 2^d (2.04 / 2^d for the cavity) never equals
+# alpha h.
 def chain_cells(depth=6):
     """Cells of a chain of nested boxes, depth k = 0 .. depth - 1: the root, its child (0, 0, 0), then always the child
     (1, 1, 1), so that every box of the chain touches the faces of its parent's siblings."""
@@ -83,32 +84,67 @@ CASES = {
     # the chain again, but absolute_min = 0.05 diagonal = 0.088 ends it at depth 4 (h_box = 0.064) where the law wants 6
     "min_ratio_stop": dict(mesh=cube, spacing=_CHAIN, alpha=2.0, ratio=0.05),
     "cube_far": dict(mesh=lambda: cube(shift=1000.0), spacing=("const", 0.1), alpha=2.0, ratio=1.0e-6, dtypes=[F32]),
+    # LogLike: h = 0.3 d / (0.24 + d) falls to zero at its point, so h_box > 0.5 h holds all the way down: the depth cap
+    # (absolute_min is 1.8e-9, below h_box(20) = 9.7e-7) is what ends the refinement about the point.  In Float32 the
+    # deepest leaves' h lies under sqrt(eps) = 3.5e-4 and is clamped; in Float64 (1.5e-8) none is.
+    "deep_loglike": dict(mesh=cube, spacing=("loglike", 0.3, 1.2, lambda dtype: np.full((1, 3), 0.3, dtype=dtype)), alpha=0.5,
+                         ratio=1.0e-9),
+    # the law's point is the centre of the chain's depth-3 box: d = 0 there, h = 0 <= eps, the box refuses to split while
+    # its siblings go on to depth 5, and the balance has to split it
+    "loglike_on_centre": dict(mesh=cube, spacing=("loglike", 0.3, 1.2, lambda dtype: chain_points(dtype, 4)[3:4]), alpha=0.5,
+                              ratio=1.0e-9),
+    # the same point under alpha = 1: the depth-3 box stays a leaf, INTERIOR, with h clamped to sqrt(eps).  In Float64 its
+    # weight (0.1275 / 1.5e-8)^3 = 6e20 leaves every other interior leaf an integer share floor(w / W 2^32) of zero
+    "loglike_heavy_leaf": dict(mesh=cube, spacing=("loglike", 0.3, 1.2, lambda dtype: chain_points(dtype, 4)[3:4]), alpha=1.0,
+                               ratio=1.0e-9),
+    # ... and the root's centre: the tree is the root alone
+    "loglike_root_centre": dict(mesh=cube, spacing=("loglike", 0.3, 1.2, lambda dtype: chain_points(dtype, 1)[0:1]), alpha=0.5,
+                                ratio=1.0e-9),
 }
+# Cases too large for the set model and the parametrised tests (build_arrays below; test_gpu_node_tree_edges.py), Float32.
+BIG_CASES = {
+    # 36 864 internal boxes at depth 6: the level-7 pass is 294 912 = 2^18 + 32 768 boxes, the tree 309 968 leaves
+    "slab_fine": dict(mesh=lambda: cube((1.0, 1.0, 0.14)), spacing=("const", 0.006), alpha=2.0, ratio=1.0e-6, dtypes=[F32]),
+    # the same slab under LogLike(0.006, 1.2) about a point whose level-7 boxes come in the second chunk of that front:
+    # h falls below h_box(7) / 2 within 0.0095 of it, so a few boxes of the ragged chunk, and none of the full one, pass the
+    # size tests and are probed; the refinement goes on about the point until absolute_min ends it
+    "slab_fine_point": dict(mesh=lambda: cube((1.0, 1.0, 0.14)), spacing=("loglike", 0.006, 1.2, np.array([[0.9, 0.9, 0.07]])),
+                            alpha=2.0, ratio=1.0e-6, dtypes=[F32]),
+    # uniform at depth 7: 2 097 152 leaves, 8 full chunks
+    "cube_depth7": dict(mesh=cube, spacing=("const", 0.006), alpha=2.0, ratio=1.0e-6, dtypes=[F32]),
+}
+CHUNK = 1 << 18                                                       # kNtChunk of csrc/wtp_node_tree.hip
+
+
+def case_of(name):
+    return CASES[name] if name in CASES else BIG_CASES[name]
 
 
 def case_dtypes(name):
-    return CASES[name].get("dtypes", DTYPES)
+    return case_of(name).get("dtypes", DTYPES)
 
 
 @functools.lru_cache(maxsize=None)
 def mesh_of(name, dtype):
-    v, t = CASES[name]["mesh"]()
+    v, t = case_of(name)["mesh"]()
     return np.ascontiguousarray(v.astype(dtype)), np.ascontiguousarray(t)
 
 
 def spacing_of(name, dtype):
     """The case's spacing with its boundary points as an array of `dtype`."""
-    sp = CASES[name]["spacing"]
+    sp = case_of(name)["spacing"]
     if sp[0] == "const":
         return sp
-    pts = sp[4](dtype) if callable(sp[4]) else sp[4]
-    return sp[:4] + (np.ascontiguousarray(np.asarray(pts, dtype=dtype)),)
+    pts = sp[-1](dtype) if callable(sp[-1]) else sp[-1]
+    return sp[:-1] + (np.ascontiguousarray(np.asarray(pts, dtype=dtype)),)
 
 
 def library_spacing(wtp, name, dtype):
     sp = spacing_of(name, dtype)
     if sp[0] == "const":
         return sp[1]
+    if sp[0] == "loglike":
+        return wtp.LogLike(sp[3], sp[1], sp[2])
     return wtp.BoundaryLayerSpacing(sp[4], sp[1], sp[2], sp[3])
 
 
@@ -118,11 +154,16 @@ def law_h(sp, c):
     if sp[0] == "const":
         return np.full(len(c), T(sp[1]), dtype=c.dtype)
     d2 = None
-    for q in np.asarray(sp[4], dtype=c.dtype):
+    for q in np.asarray(sp[-1], dtype=c.dtype):
         dx, dy, dz = c[:, 0] - q[0], c[:, 1] - q[1], c[:, 2] - q[2]
         e = (dx * dx + dy * dy) + dz * dz
         d2 = e if d2 is None else np.minimum(d2, e)
     d = np.sqrt(d2)
+    if sp[0] == "loglike":                                            # base d / (a + d), a = base (1 - (growth - 1))
+        base, growth = T(sp[1]), T(sp[2])
+        inv_growth = T(1) - (growth - T(1))
+        a = base * inv_growth
+        return base * d / (a + d)
     p0, p1, p2 = T(sp[1]), T(sp[2]), T(sp[3])
     center, width = p2 / T(2), p2 / T(6)
     with np.errstate(over="ignore"):
@@ -414,6 +455,15 @@ def model_run(name, dtype):
     return build(v, t, lambda p: law_h(sp, p), case["alpha"], case["ratio"])
 
 
+@functools.lru_cache(maxsize=None)
+def model_run_arrays(name, dtype):
+    """The same through build_arrays; the only model of BIG_CASES["slab_fine"]."""
+    case = case_of(name)
+    v, t = mesh_of(name, dtype)
+    sp = spacing_of(name, dtype)
+    return build_arrays(v, t, lambda p: law_h(sp, p), case["alpha"], case["ratio"])
+
+
 def locate_points(model):
     """Points that try find_leaf: every leaf centre; the child-splitting planes of the root and of a deepest internal box,
     where >= decides; the root's faces and corners; points outside the root and a NaN."""
@@ -598,3 +648,320 @@ def on_cell_centres(model, xyz, leaf):
         f = (xyz[sel].astype(F64) - lo) / ((hi - lo).astype(F64) / g) - 0.5
         ok[sel] = (np.abs(f - np.rint(f)) < 1e-3).all(axis=1) & (np.rint(f) >= 0).all(axis=1) & (np.rint(f) < g).all(axis=1)
     return ok
+
+
+# ---- the same two models on arrays ------------------------------------------------------------------------------------
+# build() and place() above are the definition.  Their sets of tuples and per-point Python integers cannot replay 3e5
+# leaves or 1e6 points in a test's time; build_arrays() and place_arrays() follow the same words of include/wtp.h on
+# numpy arrays and are proved equal to them, byte for byte, by test_node_tree_cases.py.
+def box_code(d, c):
+    """One uint64 per box (d[n], c[n, 3]): its Morton code at its own depth, a one behind it, zeros up to depth 20 (the
+    library's key).  Distinct boxes have distinct codes."""
+    d, c = np.asarray(d, dtype=np.int64), np.asarray(c, dtype=np.int64).reshape(-1, 3)
+    m = _spread(c[:, 0]) | (_spread(c[:, 1]) << np.uint64(1)) | (_spread(c[:, 2]) << np.uint64(2))
+    return ((m << np.uint64(1)) | np.uint64(1)) << (np.uint64(3) * (MAX_DEPTH - d).astype(np.uint64))
+
+
+def _children(c):
+    """(8 n, 3): the children of cells c (n, 3), each parent's eight together in child order."""
+    m = np.array(_CORNERS, dtype=np.int64)
+    return (2 * np.asarray(c, dtype=np.int64)[:, None, :] + m[None]).reshape(-1, 3)
+
+
+def refine_arrays(root, geo, h_fn, alpha):
+    """refine() level by level on arrays.  Returns (leaf depths, leaf cells, internal depths, internal cells, facts);
+    facts["fronts"] = boxes looked at per level, facts["wanted"] = per level, which of them passed the size tests."""
+    T = root["T"]
+    eps = np.finfo(T).eps
+    ld, lc, idp, ic, fronts, wanted = [], [], [], [], [], []
+    c = np.zeros((1, 3), dtype=np.int64)
+    touch_only, d = 0, 0
+    while len(c):
+        fronts.append(len(c))
+        lo, hi, ctr = bounds(root, d, c)
+        hb = h_box(root, d)
+        h = np.asarray(h_fn(np.ascontiguousarray(ctr)), dtype=T)
+        assert np.isfinite(h).all()
+        size_ok = np.full(len(c), d < MAX_DEPTH and hb > root["absmin"]) & (h > eps) & (hb > T(alpha) * h)
+        split = np.zeros(len(c), dtype=bool)
+        idx = np.nonzero(size_ok)[0]
+        wanted.append(idx)
+        for i0 in range(0, len(idx), CHUNK):
+            part = idx[i0:i0 + CHUNK]
+            pts = probe_points(lo[part], hi[part], PROBES)
+            k = geo.cls(pts.reshape(-1, 3), np.repeat(np.full(len(part), tol_of(root, d), dtype=T), 27)).reshape(-1, 27)
+            seen = (k != EXT).any(axis=1)
+            rest = part[~seen]
+            touched = geo.touch(lo[rest], hi[rest]) if len(rest) else np.zeros(0, dtype=bool)
+            split[part[seen]] = True
+            split[rest[touched]] = True
+            touch_only += int(touched.sum())
+        ld.append(np.full(int((~split).sum()), d, dtype=np.int64)), lc.append(c[~split])
+        idp.append(np.full(int(split.sum()), d, dtype=np.int64)), ic.append(c[split])
+        c, d = _children(c[split]), d + 1
+    return np.concatenate(ld), np.concatenate(lc), np.concatenate(idp), np.concatenate(ic), dict(touch_only=touch_only, fronts=fronts, wanted=wanted)
+
+
+def needs_balancing_arrays(d, c, int_d, int_c):
+    """needs_balancing() of every leaf (d[n], c[n, 3]): a face neighbour of its own depth is internal and has an internal
+    child, which is to say that it is the parent of an internal box.  Set membership over sorted codes."""
+    deep = int_d >= 1
+    parents = np.unique(box_code(int_d[deep] - 1, int_c[deep] >> 1))
+    out = np.zeros(len(d), dtype=bool)
+    for a in range(3):
+        for s in (-1, 1):
+            nc = c.copy()
+            nc[:, a] += s
+            ok = (nc[:, a] >= 0) & (nc[:, a] < (np.int64(1) << d))
+            out[ok] |= np.isin(box_code(d[ok], nc[ok]), parents)
+    return out
+
+
+def balance_arrays(root, ld, lc, idp, ic):
+    """balance_jacobi() on arrays.  Returns (leaf depths, leaf cells, internal depths, internal cells, rounds, n_split,
+    n_blocked)."""
+    may = np.array([can_subdivide(root, d) for d in range(MAX_DEPTH + 1)], dtype=bool)
+    rounds = n_split = n_blocked = 0
+    while True:
+        rounds += 1
+        assert rounds <= 100
+        want = needs_balancing_arrays(ld, lc, idp, ic)
+        todo = want & may[ld]
+        n_blocked += int(want.sum() - todo.sum())
+        if not todo.any():
+            return ld, lc, idp, ic, rounds, n_split, n_blocked
+        idp, ic = np.concatenate([idp, ld[todo]]), np.concatenate([ic, lc[todo]])
+        ld, lc = np.concatenate([ld[~todo], np.repeat(ld[todo] + 1, 8)]), np.concatenate([lc[~todo], _children(lc[todo])])
+        n_split += int(todo.sum())
+
+
+def finish(root, geo, spacing_fn, d, c, slices=1 << 19):
+    """Leaf order, classes, h, the terms and the info's sums of the leaves (d, c), as build() ends; the classes in slices
+    of at most `slices` boxes."""
+    dtype = root["org"].dtype
+    T = dtype.type
+    o = np.argsort(morton_start(d, c), kind="stable")
+    d, c = np.asarray(d, dtype=np.int32)[o], np.asarray(c, dtype=np.int32).reshape(-1, 3)[o]
+    parts = [classify(root, geo, d[i:i + slices], c[i:i + slices]) for i in range(0, len(d), slices)]
+    cls, vote, touched = (np.concatenate([p[k] for p in parts]) for k in range(3))
+    ctr = _centres(root, d, c)
+    hraw = np.asarray(spacing_fn(np.ascontiguousarray(ctr)), dtype=dtype)
+    assert np.isfinite(hraw).all()
+    h = np.maximum(hraw, np.sqrt(np.finfo(T).eps).astype(dtype))
+    hb = (root["size"] / (np.int64(1) << np.arange(MAX_DEPTH + 1)).astype(dtype))[d]
+    live = cls != EXT
+    terms = ((hb * hb) * hb) / ((h * h) * h)
+    return dict(depth=d, cell=c, cls=cls, vote=vote, touched=touched, h=h, hraw=hraw, terms=terms,
+                integral=math.fsum(terms[live].astype(F64).tolist()), h_min=float(h[live].min()) if live.any() else 0.0)
+
+
+def build_arrays(verts, tris, spacing_fn, alpha, ratio, sd_fn=None, bbox=None):
+    """build() on arrays.  The result has no sets: internal boxes are model["internal_depth"], ["internal_cell"]."""
+    dtype = verts.dtype
+    geo = Geometry(verts, tris, sd_fn, bbox)
+    root = root_of(geo.lo, geo.hi, dtype, ratio)
+    ld0, lc0, id0, ic0, facts = refine_arrays(root, geo, spacing_fn, alpha)
+    ld, lc, idp, ic, rounds, n_split, n_blocked = balance_arrays(root, ld0, lc0, id0, ic0)
+    f = finish(root, geo, spacing_fn, ld, lc)
+    d, cls = f["depth"], f["cls"]
+    info = dict(n_leaves=len(d), n_interior=int((cls == INT).sum()), n_boundary=int((cls == BND).sum()),
+                n_exterior=int((cls == EXT).sum()), n_boxes=len(ld) + len(idp), depth_max=int(d.max()),
+                n_levels=int(d.max()) + 1, balance_rounds=rounds, integral=f["integral"], h_min=f["h_min"],
+                origin=tuple(float(x) for x in root["org"]), root_size=float(root["size"]), absolute_min=float(root["absmin"]))
+    facts.update(balance_splits=n_split, balance_blocked=n_blocked, demoted=int((f["touched"] & (f["vote"] != BND)).sum()),
+                 demoted_interior=int((f["touched"] & (f["vote"] == INT)).sum()), depth_before_balance=int(ld0.max()))
+    return dict(cell=f["cell"], depth=d, cls=cls, h=f["h"], info=info, facts=facts, root=root, geo=geo, terms=f["terms"],
+                internal_depth=idp, internal_cell=ic, leaves0_depth=ld0, leaves0_cell=lc0)
+
+
+def uniform_tree(verts, tris, h, depth, ratio, sd_fn=None, bbox=None):
+    """The tree whose leaves are every cell of `depth`, under a constant spacing h, in closed form: no refinement is run.
+    Leaves in Morton order, one balance round, classes from classify() in slices."""
+    dtype = verts.dtype
+    geo = Geometry(verts, tris, sd_fn, bbox)
+    root = root_of(geo.lo, geo.hi, dtype, ratio)
+    n = 8 ** depth
+    code = np.arange(n, dtype=np.uint64)
+    c = np.stack([_compact(code >> np.uint64(a)) for a in range(3)], axis=1).astype(np.int32)
+    f = finish(root, geo, lambda p: np.full(len(p), dtype.type(h), dtype=dtype), np.full(n, depth, dtype=np.int32), c)
+    assert np.array_equal(f["cell"], c)
+    cls = f["cls"]
+    info = dict(n_leaves=n, n_interior=int((cls == INT).sum()), n_boundary=int((cls == BND).sum()), n_exterior=int((cls == EXT).sum()),
+                n_boxes=n + (n - 1) // 7, depth_max=depth, n_levels=depth + 1, balance_rounds=1, integral=f["integral"],
+                h_min=f["h_min"], origin=tuple(float(x) for x in root["org"]), root_size=float(root["size"]),
+                absolute_min=float(root["absmin"]))
+    return dict(cell=c, depth=f["depth"], cls=cls, h=f["h"], info=info, root=root, geo=geo, terms=f["terms"])
+
+
+def _compact(x):
+    """Every third bit of x, from bit 0 (the inverse of _spread)."""
+    x = np.asarray(x, dtype=np.uint64) & np.uint64(0x1249249249249249)
+    for s, m in ((2, 0x10C30C30C30C30C3), (4, 0x100F00F00F00F00F), (8, 0x1F0000FF0000FF), (16, 0x1F00000000FFFF), (32, 0x1FFFFF)):
+        x = (x ^ (x >> np.uint64(s))) & np.uint64(m)
+    return x
+
+
+def leaf_bounds(model, idx):
+    """(lo, hi) of the leaves idx[n] as bounds() computes them, one row per entry."""
+    root = model["root"]
+    dtype = root["org"].dtype
+    hb = (root["size"] / (np.int64(1) << np.arange(MAX_DEPTH + 1)).astype(dtype))[model["depth"][idx]]
+    lo = root["org"] + model["cell"][idx].astype(np.int64).astype(dtype) * hb[:, None]
+    return lo, lo + hb[:, None]
+
+
+def in_leaf_arrays(model, xyz, leaf):
+    lo, hi = leaf_bounds(model, leaf)
+    return ((xyz >= lo) & (xyz <= hi)).all(axis=1)
+
+
+def zero_shares(model, group):
+    """How many leaves of class `group` have the integer share floor(w / W 2^32) == 0, and how many leaves it has."""
+    w = model["terms"].astype(np.float64)[model["cls"] == group]
+    return int((np.floor((w / math.fsum(w)) * 4294967296.0) == 0).sum()), len(w)
+
+
+def rows_in(a, b):
+    """Per row of a (n, 3): is it, byte for byte, a row of b?  A 64-bit hash of the rows' words finds the few rows that
+    may be (np.isin over integers); those are then compared as bytes, so the answer is exact."""
+    def words(x):
+        return np.ascontiguousarray(x).view(np.uint32).reshape(len(x), 3 * x.dtype.itemsize // 4).astype(np.uint64)
+
+    def key(x):
+        h = np.zeros(len(x), dtype=np.uint64)
+        for col in words(x).T:
+            h = splitmix64_arrays(h ^ col)
+        return h
+
+    assert a.dtype == b.dtype
+    ka, kb = key(a), key(b)
+    maybe = np.isin(ka, kb)
+    out = np.zeros(len(a), dtype=bool)
+    if maybe.any():
+        have = {r.tobytes() for r in b[np.isin(kb, ka[maybe])]}
+        out[np.nonzero(maybe)[0]] = [r.tobytes() in have for r in a[maybe]]
+    return out
+
+
+_U = np.uint64
+
+
+def splitmix64_arrays(z):
+    z = z + _U(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> _U(30))) * _U(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> _U(27))) * _U(0x94D049BB133111EB)
+    return z ^ (z >> _U(31))
+
+
+def draw_arrays(seed, stage, j, a):
+    """r(stage, j, a) for j a uint64 array; sums and products wrap at 2^64 as the header's do."""
+    return splitmix64_arrays(_U(seed << 40) + _U(3) * (_U(stage << 36) + np.asarray(j, dtype=np.uint64)) + _U(a))
+
+
+def mulhi64(x, y):
+    """floor(x y / 2^64) for a uint64 array x and one y < 2^64, by 32-bit halves."""
+    lo32 = _U(0xFFFFFFFF)
+    y = _U(y)
+    x0, x1, y0, y1 = x & lo32, x >> _U(32), y & lo32, y >> _U(32)
+    mid = x1 * y0 + ((x0 * y0) >> _U(32))
+    mid2 = x0 * y1 + (mid & lo32)
+    return x1 * y1 + (mid >> _U(32)) + (mid2 >> _U(32))
+
+
+def uniform_arrays(dtype, seed, stage, j, a):
+    return ((draw_arrays(seed, stage, j, a) >> _U(40)).astype(np.float32) * np.float32(2.0 ** -24)).astype(dtype)
+
+
+def grid_divisions_arrays(n):
+    """The smallest g with g^3 >= n, per entry of the int64 array n >= 1."""
+    g = np.maximum(np.rint(np.cbrt(n.astype(F64))).astype(np.int64), 1)
+    for _ in range(3):
+        g = np.where(g ** 3 < n, g + 1, g)
+    for _ in range(3):
+        g = np.where((g - 1) ** 3 >= n, g - 1, g)
+    assert ((g ** 3 >= n) & ((g - 1) ** 3 < n)).all()
+    return g
+
+
+def pick_arrays(cum, f_total, x):
+    return np.searchsorted(cum, mulhi64(x, f_total), side="right")
+
+
+def group_counts_arrays(w, W, member, count, seed, stage):
+    counts = np.zeros(len(w), dtype=np.int64)
+    if count < 1:
+        return counts
+    expected = float(count) * (w / W)
+    base = np.floor(expected)
+    counts += base.astype(np.int64)
+    leftover = max(0, count - int(counts.sum()))
+    cum, f_total = pick_table(np.floor((expected - base) * 4294967296.0).astype(np.uint64))
+    if f_total == 0:
+        cum, f_total = pick_table(member.astype(np.uint64))
+    if leftover:
+        picks = pick_arrays(cum, f_total, draw_arrays(seed, stage, np.arange(leftover, dtype=np.uint64), 0))
+        counts += np.bincount(picks, minlength=len(w))
+    return counts
+
+
+def group_points_arrays(model, counts, placement, seed, stage):
+    dtype = model["root"]["org"].dtype
+    T = dtype.type
+    cum = np.cumsum(counts)
+    total = int(cum[-1]) if len(cum) else 0
+    j = np.arange(total, dtype=np.int64)
+    leaf = np.searchsorted(cum, j, side="right").astype(np.int64)
+    lo, hi = leaf_bounds(model, leaf)
+    e = hi - lo
+    if placement != 2:
+        u = np.stack([uniform_arrays(dtype, seed, stage, j, a) for a in range(3)], axis=1)
+    if placement == 0:
+        return lo + u * e, leaf
+    n = counts[leaf]
+    k = j - (cum[leaf] - n)
+    g = grid_divisions_arrays(np.maximum(counts, 1))[leaf]
+    cell = np.stack([k % g, (k // g) % g, k // (g * g)], axis=1).astype(dtype)
+    cs = e / g.astype(dtype)[:, None]
+    cmin = lo + cell * cs
+    return (cmin + cs / T(2) if placement == 2 else cmin + u * cs), leaf
+
+
+def place_arrays(model, placement, max_points, oversampling, seed, inside_fn, W=None):
+    """place() on arrays: the same returns, byte for byte."""
+    placement = PLACEMENTS.get(placement, placement)
+    w = model["terms"].astype(np.float64)
+    interior, near = model["cls"] == INT, model["cls"] == BND
+    w_int, w_ns = np.where(interior, w, 0.0), np.where(near, w, 0.0)
+    W_int, W_ns = W if W is not None else (math.fsum(w_int), math.fsum(w_ns))
+    dtype = model["root"]["org"].dtype
+    info = dict(n_points=0, n_interior=0, n_candidates=0, n_accepted=0, n_deficit=0, W_int=W_int, W_ns=W_ns, placement=placement)
+    if not W_int + W_ns > 0:
+        return dict(xyz=np.zeros((0, 3), dtype=dtype), leaf=np.zeros(0, dtype=np.int64), info=info, candidates=None)
+    n_int = int(np.rint(float(max_points) * (W_int / (W_int + W_ns))))
+    n_ns = max_points - n_int
+    n_cand = int(np.rint(float(n_ns) * oversampling))
+    c_int = group_counts_arrays(w_int, W_int, interior, n_int, seed, ST_PICK_INTERIOR)
+    assert c_int.sum() == n_int and not c_int[~interior].any()
+    xyz, leaf = group_points_arrays(model, c_int, placement, seed, ST_INTERIOR)
+    c_ns = group_counts_arrays(w_ns, W_ns, near, n_cand, seed, ST_PICK_CANDIDATES)
+    assert c_ns.sum() == n_cand and not c_ns[~near].any()
+    cand, cleaf = group_points_arrays(model, c_ns, placement, seed, ST_CANDIDATES)
+    inside = np.asarray(inside_fn(cand), dtype=bool) if len(cand) else np.zeros(0, dtype=bool)
+    take = np.nonzero(inside)[0][:max_points - n_int]
+    parts_x, parts_l = [xyz, cand[take]], [leaf, cleaf[take]]
+    so_far = n_int + len(take)
+    n_def = 0
+    if so_far < max_points and W_int > 0:
+        n_def = max_points - so_far
+        share = np.floor((w_int / W_int) * 4294967296.0).astype(np.uint64)
+        cum, f_total = pick_table(share)
+        if f_total == 0:
+            cum, f_total = pick_table(interior.astype(np.uint64))
+        t = np.arange(n_def, dtype=np.uint64)
+        dl = pick_arrays(cum, f_total, draw_arrays(seed, ST_PICK_DEFICIT, t, 0)).astype(np.int64)
+        lo, hi = leaf_bounds(model, dl)
+        u = np.stack([uniform_arrays(dtype, seed, ST_DEFICIT, t, a) for a in range(3)], axis=1)
+        parts_x.append(lo + u * (hi - lo)), parts_l.append(dl)
+    info.update(n_points=so_far + n_def, n_interior=n_int, n_candidates=n_cand, n_accepted=len(take), n_deficit=n_def)
+    return dict(xyz=np.concatenate(parts_x), leaf=np.concatenate(parts_l), info=info, candidates=(cand, cleaf, inside),
+                counts=(c_int, c_ns))

@@ -1,7 +1,8 @@
 """No-GPU checks of the node octree's model (node_tree_cases.py): every case has the property it is there for; the
 reference's in-place balance sweep and the library's Jacobi rounds reach the same tree; the leaves tile the root box, no
-interior leaf is touched by a triangle's box, find_leaf finds every leaf from its centre; the header declares the entry
-points and the built library and the package export them."""
+interior leaf is touched by a triangle's box, find_leaf finds every leaf from its centre; the models on arrays
+(build_arrays, place_arrays) equal the set and loop models byte for byte; the big cases meet the chunk conditions they
+are there for; the header declares the entry points and the built library and the package export them."""
 import ctypes
 import os
 import re
@@ -88,6 +89,85 @@ def test_every_case_has_the_property_it_is_there_for():
     assert c["facts"]["demoted_interior"] > 0 and 1000 < c["info"]["n_leaves"] < 10000
     f = N.model_run("cube_far", F32)
     assert np.array_equal(f["cell"], N.model_run("cube_uniform", F32)["cell"]) and f["info"]["origin"][0] > 999
+    for dt in N.DTYPES:
+        sqrt_eps = np.sqrt(np.finfo(dt).eps)
+        q = N.model_run("deep_loglike", dt)
+        i, fq = q["info"], q["facts"]
+        assert (i["n_leaves"], i["n_interior"], i["n_boundary"], i["n_exterior"]) == (8352, 7000, 1352, 0)
+        # depth 20 is reached by the refinement, not by the balance
+        assert i["depth_max"] == 20 == fq["depth_before_balance"] and int((q["depth"] == 20).sum()) == 152
+        assert (i["balance_rounds"], fq["balance_splits"], fq["balance_blocked"]) == (6, 218, 0)
+        assert int((q["h"] == sqrt_eps).sum()) == (1564 if dt == F32 else 0)
+        assert i["h_min"] == (float(sqrt_eps) if dt == F32 else float(q["h"].min())) and (q["h"] >= sqrt_eps).all()
+        # the cap and nothing else stops the tree: a depth-20 leaf passes every size test of the criterion but d < 20
+        root, sp = q["root"], N.spacing_of("deep_loglike", dt)
+        deep = q["depth"] == 20
+        hraw = N.law_h(sp, N._centres(root, q["depth"][deep], q["cell"][deep]))
+        hb = N.h_box(root, 20)
+        assert hb > root["absmin"] and ((hraw > np.finfo(dt).eps) & (hb > dt(0.5) * hraw)).any()
+        assert N.h_box(root, 20) > i["absolute_min"] and not N.can_subdivide(root, 20) and N.can_subdivide(root, 19)
+        o = N.model_run("loglike_on_centre", dt)
+        assert (o["info"]["n_leaves"], o["info"]["depth_max"], o["info"]["balance_rounds"]) == (4656, 5, 2)
+        box = (3, N.chain_cells(4)[3])
+        assert N.law_h(N.spacing_of("loglike_on_centre", dt), N.bounds(o["root"], *box)[2])[0] == 0    # d = 0: h = 0 <= eps
+        assert o["facts"]["balance_splits"] == 1 and box in o["leaves0"] and box in o["internal"]
+        assert o["internal"] - o["internal0"] == {box}
+        y = N.model_run("loglike_heavy_leaf", dt)
+        at = np.nonzero((y["depth"] == 3) & (y["cell"] == N.chain_cells(4)[3]).all(axis=1))[0]
+        assert len(at) == 1 and y["cls"][at[0]] == N.INT and y["h"][at[0]] == sqrt_eps and int((y["h"] == sqrt_eps).sum()) == 1
+        assert box in y["leaves0"] and y["facts"]["balance_splits"] == 0 and y["info"]["n_interior"] == 258
+        assert N.zero_shares(y, N.INT) == ((257, 258) if dt == F64 else (0, 258))
+        assert N.zero_shares(q, N.INT) == ((152, 7000) if dt == F32 else (0, 7000))     # Float32: the depth-20 leaves
+        z = N.model_run("loglike_root_centre", dt)
+        assert np.array_equal(N.spacing_of("loglike_root_centre", dt)[3], np.full((1, 3), 0.5, dtype=dt))
+        assert z["info"]["n_leaves"] == 1 and z["h"][0] == sqrt_eps and z["cls"][0] == N.BND
+    assert not np.array_equal(N.model_run("deep_loglike", F32)["h"], N.model_run("deep_loglike", F64)["h"].astype(F32))
+    assert all(np.array_equal(N.model_run("deep_loglike", F32)[k], N.model_run("deep_loglike", F64)[k]) for k in ("cell", "depth", "cls"))
+
+
+def test_the_big_cases_meet_their_chunk_conditions():
+    """slab_fine: the level-7 pass and the leaf count are above one chunk of 2^18 boxes and no multiple of it, so that the
+    probe and the vote pass both run a full chunk and a ragged one.  cube_depth7: 8 full chunks, in closed form."""
+    m = N.model_run_arrays("slab_fine", F32)
+    front, n = m["facts"]["fronts"][7], m["info"]["n_leaves"]
+    print(f"slab_fine: fronts={m['facts']['fronts']} n_leaves={n} by depth={np.bincount(m['depth']).tolist()} facts={m['facts']}")
+    assert front > N.CHUNK and front % N.CHUNK and n > N.CHUNK and n % N.CHUNK
+    assert len(m["facts"]["fronts"]) == 8 and m["info"]["balance_rounds"] > 1 and m["facts"]["balance_splits"] > 0
+    assert min(m["info"][k] for k in ("n_interior", "n_boundary", "n_exterior")) > 0
+    key = N.morton_start(m["depth"], m["cell"])
+    assert (key[1:] > key[:-1]).all() and m["info"]["n_boxes"] == n + (n - 1) // 7
+    assert int((np.float64(1) / 8 ** m["depth"].astype(np.int64)).sum() * 8 ** 7) == 8 ** 7       # the leaves tile the root (exact: powers of two)
+    assert not N.needs_balancing_arrays(m["depth"].astype(np.int64), m["cell"].astype(np.int64), m["internal_depth"],
+                                        m["internal_cell"]).any()
+    # slab_fine_point: boxes that pass the size tests in the ragged chunk of the level-7 front and in no other place of
+    # it, so that a chunk reading the first chunk's flags probes none of them; they split
+    p = N.model_run_arrays("slab_fine_point", F32)
+    wanted = p["facts"]["wanted"][7]
+    print(f"slab_fine_point: fronts={p['facts']['fronts']} wanted at level 7={wanted.tolist()} n_leaves={p['info']['n_leaves']}")
+    assert p["facts"]["fronts"][:8] == m["facts"]["fronts"] and p["facts"]["fronts"][8] == 8 * len(wanted) > 0
+    assert (wanted >= N.CHUNK).all() and p["info"]["n_leaves"] > n and p["info"]["n_leaves"] % N.CHUNK and p["info"]["depth_max"] > 7
+    c = N.BIG_CASES["cube_depth7"]
+    root = N.root_of(np.zeros(3), np.ones(3), F32, c["ratio"])
+    assert N.h_box(root, 6) > F32(c["alpha"]) * F32(c["spacing"][1]) >= N.h_box(root, 7) and 8 ** 7 == 8 * N.CHUNK
+    assert 2 * N.h_box(root, 7) > F32(0.01) > N.h_box(root, 7)       # the outer shell of depth-7 cells lies in the 1 % margin
+
+
+@pytest.mark.parametrize("name,dtype", ALL, ids=IDS)
+def test_the_tree_on_arrays_equals_the_set_model(name, dtype):
+    m, a = N.model_run(name, dtype), N.model_run_arrays(name, dtype)
+    for k in ("cell", "depth", "cls", "h", "terms"):
+        assert a[k].dtype == m[k].dtype and a[k].tobytes() == m[k].tobytes(), k
+    assert a["info"] == m["info"] and all(a["facts"][k] == m["facts"][k] for k in m["facts"])
+    assert set(zip(a["internal_depth"].tolist(), map(tuple, a["internal_cell"].tolist()))) == m["internal"]
+    assert set(zip(a["leaves0_depth"].tolist(), map(tuple, a["leaves0_cell"].tolist()))) == m["leaves0"]
+    # needs_balancing, leaf by leaf, on the tree before its balance
+    d0, c0 = a["leaves0_depth"], a["leaves0_cell"]
+    want = np.array([N.needs_balancing((int(x), tuple(int(v) for v in y)), m["internal0"]) for x, y in zip(d0, c0)], dtype=bool)
+    idp = np.array([b[0] for b in m["internal0"]], dtype=np.int64)
+    ic = np.array([b[1] for b in m["internal0"]], dtype=np.int64).reshape(-1, 3)
+    assert np.array_equal(N.needs_balancing_arrays(d0, c0, idp, ic), want)
+    assert np.array_equal(N.in_leaf_arrays(m, N._centres(m["root"], m["depth"], m["cell"]), np.arange(len(m["depth"]))),
+                          np.ones(len(m["depth"]), dtype=bool))
 
 
 def test_keys_round_trip_and_order():
@@ -181,6 +261,53 @@ def test_placement_returns_max_points_inside_the_named_leaves(name, dtype, max_p
     assert (m["cls"][got["leaf"][ni + na:]] == N.INT).all()
     if placement == "lattice" and ni:
         assert N.on_cell_centres(m, got["xyz"][:ni], got["leaf"][:ni]).all()
+
+
+PLACE_ROWS = [("cube_uniform", F32, 700), ("corner_graded", F64, 333), ("slab", F64, 200), ("cavity", F32, 10), ("cube_uniform", F64, 1),
+              ("cube_shallow", F32, 50), ("deep_loglike", F32, 1000), ("deep_loglike", F64, 1000), ("deep_loglike", F64, 3),
+              ("loglike_heavy_leaf", F64, 1000), ("loglike_heavy_leaf", F32, 333)]
+
+
+@pytest.mark.parametrize("placement", list(N.PLACEMENTS))
+@pytest.mark.parametrize("name,dtype,max_points", PLACE_ROWS)
+def test_the_placement_on_arrays_equals_the_loop_model(name, dtype, max_points, placement):
+    m = N.model_run(name, dtype)
+    for seed in (11, 0, 2 ** 24 - 1)[:3 if max_points == 333 else 1]:
+        want = N.place(m, placement, max_points, 2.0, seed, N.oracle_inside(name, dtype))
+        got = N.place_arrays(m, placement, max_points, 2.0, seed, N.oracle_inside(name, dtype))
+        assert got["info"] == want["info"]
+        for k in ("xyz", "leaf"):
+            assert got[k].dtype == want[k].dtype and got[k].tobytes() == want[k].tobytes(), k
+        for x, y in zip(got["candidates"], want["candidates"]):
+            assert x.dtype == y.dtype and x.tobytes() == y.tobytes()
+        assert np.array_equal(N.in_leaf_arrays(m, got["xyz"], got["leaf"]), N.in_leaf(m, want["xyz"], want["leaf"]))
+
+
+def test_the_integer_helpers_on_arrays_equal_python_integers():
+    rng = np.random.default_rng(9)
+    x = np.concatenate([rng.integers(0, 2 ** 64, 500, dtype=np.uint64), np.array([0, 1, 2 ** 32 - 1, 2 ** 32, 2 ** 64 - 1], dtype=np.uint64)])
+    for y in (0, 1, 2 ** 32 - 1, 2 ** 32, 2 ** 63 + 12345, 2 ** 64 - 1, 4294967296 * 7000):
+        assert N.mulhi64(x, y).tolist() == [(int(v) * y) >> 64 for v in x]
+    for seed, stage in ((0, 0), (1234, 3), (2 ** 24 - 1, 5)):
+        j = np.array([0, 1, 255, 2 ** 20 + 3, 2 ** 31, 2 ** 36 - 1], dtype=np.uint64)
+        for a in range(3):
+            assert N.draw_arrays(seed, stage, j, a).tolist() == [N.draw(seed, stage, int(v), a) for v in j]
+            assert N.uniform_arrays(F32, seed, stage, j, a).tolist() == [float(N.uniform(F32, seed, stage, int(v), a)) for v in j]
+    n = np.concatenate([np.arange(1, 1100), np.array([10 ** 6 - 1, 10 ** 6, 10 ** 6 + 1, 2 ** 31])]).astype(np.int64)
+    assert N.grid_divisions_arrays(n)[:1099].tolist() == [N.grid_divisions(int(v)) for v in n[:1099]]
+    assert N.grid_divisions_arrays(n)[1099:].tolist() == [100, 100, 101, 1291]
+    for dt in (F32, F64):
+        a = rng.integers(0, 4, (500, 3)).astype(dt)
+        a[0] = (0.0, -0.0, np.nan)
+        b = np.concatenate([a[::7], rng.integers(0, 4, (40, 3)).astype(dt) + dt(0.5)])
+        have = {r.tobytes() for r in b}
+        assert N.rows_in(a, b).tolist() == [r.tobytes() in have for r in a] and N.rows_in(a, b).any() and not N.rows_in(a, b).all()
+        assert not N.rows_in(a, b[:0]).any() and len(N.rows_in(a[:0], b)) == 0
+    d = rng.integers(0, 21, 300)
+    c = np.array([rng.integers(0, 1 << int(v), 3) if v else (0, 0, 0) for v in d])
+    code = N.box_code(d, c)
+    assert len(np.unique(code)) == len({(int(a), tuple(b)) for a, b in zip(d, c.tolist())})
+    assert np.array_equal(N._compact(N._spread(c[:, 0])), c[:, 0].astype(np.uint64))
 
 
 def test_header_library_and_package_export_the_placements(wtp):

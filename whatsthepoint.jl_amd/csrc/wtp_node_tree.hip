@@ -548,7 +548,8 @@ static int node_tree_build_t(wtp_ctx* ctx, const wtp_spacing_desc* sp, double al
     double integral = 0;
     for (int b = 0; b < blocks; ++b) integral += R.part[b];
     I.integral = integral;
-    I.max_points_auto = (int64_t)std::ceil(1.5 * integral);
+    const double auto_cap = std::ceil(1.5 * integral); // h clamped to sqrt(eps) in a coarse box: up to 1e24 in Float64
+    I.max_points_auto = auto_cap >= 9223372036854775808.0 ? INT64_MAX : (int64_t)auto_cap;
     I.h_min = 0;
     if (R.hmin_bits != ~0ull) memcpy(&I.h_min, &R.hmin_bits, sizeof(double));
     for (int a = 0; a < 3; ++a) I.origin[a] = (double)root.org[a];
